@@ -1,12 +1,22 @@
 #!/usr/bin/env python3
 """Headline benchmark: GAE forward+backward samples/s at T=1024, B=65536 fp32 (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 N = 1 runs in this process.  N > 1: if the process was not started by a launcher (no RANK in the environment) it starts
-its own ranks -- it re-executes itself under ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N
---master-addr 127.0.0.1`` -- so a plain ``python bench.py --gpus 8`` works; under ``torch.distributed.run`` it uses the
-ranks it was given.  One rank per GPU over RCCL.
+its own ranks -- a child process ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1``
+running this file, whose exit status it returns -- so a plain ``python bench.py --gpus 8`` works; under
+``torch.distributed.run`` it uses the ranks it was given.  One rank per GPU over RCCL.
+
+A plain run does only what the headline needs: set-up, the pre-roll and W warmup steps, the K timed steps, the outputs
+(``--dump-outputs``), the JSON line.  Everything else the line can carry -- ``roofline``, ``scaling_detail``, ``suite``,
+``cpu_baseline`` and, for N > 1, the graph4 launch mode -- is measured only with ``--full`` (null otherwise);
+``--skip-cpu-baseline``, ``--no-scaling-detail`` and ``--no-suite`` drop single parts of a ``--full`` run.
+
+``--dump-outputs DIR`` writes, after the timed steps, what the last timed step returned to its caller on rank 0 --
+``adv`` (T, B), ``grad_value`` (T+1, B), ``grad_reward`` (T, B) -- as ``DIR/<name>.npy`` (float32).  Above 60 MB in all,
+every array keeps the same seeded sample of batch columns (listed in the line's ``outputs``).  The inputs come from
+seeded generators, so two runs with the same arguments compute on identical inputs.
 
 A "step" is one pass of the hot path over one batch of synthetic input: ``adv = GAE(value, reward)`` followed by the
 backward pass for both gradients, through the drop-in ``hpc_rll.rl_utils.gae.GAE`` module (HIP kernels behind the C
@@ -144,7 +154,8 @@ def cpu_baseline(T, B, gamma, lam, budget_s=12.0):
 
 
 def self_launch(args):
-    """`python bench.py --gpus N` without a launcher: start N ranks of this file on this node and hand over."""
+    """`python bench.py --gpus N` without a launcher: run N ranks of this file on this node in a child launcher and exit
+    with its status (a process that has initialised the GPU must not exec another program in its place)."""
     import socket
     one_device = os.environ.get("HPC_RLL_BENCH_ONE_DEVICE") == "1"
     if not one_device and torch.cuda.device_count() < args.gpus:
@@ -157,7 +168,7 @@ def self_launch(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execvpe(cmd[0], cmd, env)
+    sys.exit(subprocess.run(cmd, env=env).returncode)
 
 
 class SclkSampler:
@@ -230,7 +241,13 @@ def main():
     ap.add_argument("--graph", action="store_true", help="same as --launch graph")
     ap.add_argument("--no-scaling-detail", action="store_true", help="skip the extra weak/strong legs (profiler runs)")
     ap.add_argument("--no-suite", action="store_true", help="skip the configs[2..4] suite (N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure roofline, scaling_detail, suite, cpu_baseline and (N > 1) the graph4 launch mode")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's adv / grad_value / grad_reward (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if not torch.cuda.is_available():
         sys.exit("bench.py needs a GPU: the hpc_rll product path has no CPU fallback")
@@ -276,10 +293,8 @@ def main():
             dist.init_process_group(backend, rank=rank, world_size=world)
     assert world == args.gpus, f"--gpus {args.gpus} but WORLD_SIZE={world}"
 
-    import hpc_rl_utils as U
     import hpc_rll
     from hpc_rll.rl_utils.gae import GAE
-    lib = ctypes.CDLL(os.path.join(ROOT, "di-hpc_amd", "hpc_rll", "_lib", "libhpc_rll_hip.so"))   # already loaded: diagnostics
 
     scaling = args.scaling if args.scaling != "auto" else ("strong" if world > 1 else "weak")
     launch_arg = "graph" if args.graph else args.launch
@@ -306,34 +321,42 @@ def main():
         (profiles/r05_gae_gaps.txt) shows 0.0 us between the two kernels INSIDE a graph launch and 8.5 us of idle GPU between
         two consecutive graph launches (direct launches: 0.0 us both ways, but the module + autograd host path then costs
         ~87 us per step); at B = 8192 per rank that gap is a fifth of the 35 us step.  Several steps per launch pay it once.
-        The returned callable runs `n` steps: n // GRAPH_STEPS replays of the multi-step graph, the rest on the one-step one."""
+        The returned callable runs `n` steps: n // GRAPH_STEPS replays of the multi-step graph, the rest on the one-step one.
+        The third value returned, outputs(), gives what the last step returned to its caller: (adv, d value, d reward);
+        called once (eager: it hands over the step's own reference to adv)."""
         g = torch.Generator(device=dev).manual_seed(1234 + rank)
         value = torch.randn(T + 1, Bk, device=dev, generator=g).requires_grad_(True)
         reward = torch.randn(T, Bk, device=dev, generator=g).requires_grad_(True)
         grad_adv = torch.randn(T, Bk, device=dev, generator=g)
         gae = GAE(T, Bk).to(dev)
+        last_adv = []
 
         def step():
+            # the previous step's adv is dropped first, as its gradients are: every step allocates what the one before freed
+            last_adv.clear()
             value.grad = None
             reward.grad = None
             adv = gae(value, reward, gamma, lam)
             adv.backward(grad_adv)
+            last_adv.append(adv)
 
         if not graph:
-            return step, (value, reward, grad_adv)
+            return step, (value, reward, grad_adv), lambda: (last_adv.pop().detach(), value.grad, reward.grad)
         # same kernels, same order; only the host-side launch path changes (one hipGraphLaunch per step)
         gs = hpc_rll.graphed(gae, value, reward, gamma, lam, grad_outputs=grad_adv)
         if graph != "graph4":
-            return gs.replay, (value, reward, grad_adv, gs)
+            return gs.replay, (value, reward, grad_adv, gs), lambda: (gs.outputs, *gs.grads)
         gm = hpc_rll.graphed_steps(gae, [(value, reward, gamma, lam)] * GRAPH_STEPS, grad_outputs=[grad_adv] * GRAPH_STEPS)
+        last_graph = []
 
         def run_n(n):
             for _ in range(n // GRAPH_STEPS):
                 gm.replay()
             for _ in range(n % GRAPH_STEPS):
                 gs.replay()
+            last_graph[:] = [(gs.outputs, *gs.grads) if n % GRAPH_STEPS else (gm.outputs[-1], *gm.grads[-1])]
         run_n.multi = True          # timed() hands it the step count instead of calling it once per step
-        return run_n, (value, reward, grad_adv, gs, gm)
+        return run_n, (value, reward, grad_adv, gs, gm), lambda: last_graph[0]
 
     def timed(step, steps, warmup):
         """W untimed steps, barrier + synchronize, EXACTLY `steps` timed steps, barrier + synchronize.
@@ -376,8 +399,8 @@ def main():
         # item 2a).  Every rank takes the same decision (the times are the max over ranks, gathered).
         launch_modes = {}
         best = None
-        for mode in ("eager", "graph", "graph4"):
-            st_m, keep_m = make_step(B, {"eager": False, "graph": True}.get(mode, mode))
+        for mode in ("eager", "graph") + (("graph4",) if args.full else ()):
+            st_m, keep_m, out_m = make_step(B, {"eager": False, "graph": True}.get(mode, mode))
             if getattr(st_m, "multi", False):
                 st_m(n_pre)
             else:
@@ -390,13 +413,13 @@ def main():
             # between them, which is not the metric's "one training step per launch": it is timed and listed
             # (launch_modes), it never leads.  The headline is the faster of the one-step-per-launch modes.
             if mode != "graph4" and (best is None or el_m < best[0]):
-                best = (el_m, per_m, mode, st_m, keep_m)
-            del st_m, keep_m
-        elapsed, per_rank_s, launch, step, keep = best
+                best = (el_m, per_m, mode, st_m, keep_m, out_m)
+            del st_m, keep_m, out_m
+        elapsed, per_rank_s, launch, step, keep, outputs = best
         del best
         value, reward, grad_adv = keep[:3]
     else:
-        step, keep = make_step(B, {"eager": False, "graph": True}.get(launch, launch))
+        step, keep, outputs = make_step(B, {"eager": False, "graph": True}.get(launch, launch))
         value, reward, grad_adv = keep[:3]
         if getattr(step, "multi", False):
             step(n_pre)
@@ -405,55 +428,97 @@ def main():
                 step()
         elapsed, per_rank_s = timed(step, args.steps, args.warmup)
 
-    # ---- per-kernel durations, measured IMMEDIATELY after the timed region (same clocks / thermal state), in the same
-    # alternating fwd/bwd order as the timed region (a kernel repeated back to back would find its inputs in the
-    # 256 MiB Infinity Cache and look faster than it is in the real sequence; rocprofv3 --kernel-trace of this command
-    # sees the same pattern).  Two readings of the same >= 100 launch pairs, all on torch's current stream = the launch
-    # stream: (a) the dispatch's own begin / end timestamps (hpc_rll_ktime_*: start/stop HIP events attached to the
-    # launch itself) -- the kernel's duration as rocprofv3 reports it, used for the roofline figure; (b) hipEventRecord
-    # around every launch -- includes the gap to the neighbouring launch, listed for comparison.
-    v_d, r_d = value.detach(), reward.detach()
-    adv = torch.empty_like(r_d)
-    gv, gr = torch.empty_like(v_d), torch.empty_like(r_d)
-    n_ev = min(max(args.steps, 100), 500)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2 * n_ev + 1)]
-    U.GaeForward([v_d, r_d], [adv], gamma, lam)
-    U.GaeBackward([grad_adv], [gv, gr], gamma, lam)
-    torch.cuda.synchronize()
-    with SclkSampler(dev.index or 0) as sclk:
-        assert lib.hpc_rll_ktime_begin(2 * n_ev) == 0
-        ev[0].record()
-        for i in range(n_ev):
-            U.GaeForward([v_d, r_d], [adv], gamma, lam)
-            ev[2 * i + 1].record()
-            U.GaeBackward([grad_adv], [gv, gr], gamma, lam)
-            ev[2 * i + 2].record()
-        ev[-1].synchronize()
-        kms = (ctypes.c_float * (2 * n_ev))()
-        kkind = (ctypes.c_int * (2 * n_ev))()
-        n_k = lib.hpc_rll_ktime_end(kms, kkind, 2 * n_ev)
-    assert n_k == 2 * n_ev, f"hpc_rll_ktime_end: {n_k}"
-    kf = [kms[i] for i in range(n_k) if kkind[i] == 0]
-    kb = [kms[i] for i in range(n_k) if kkind[i] == 1]
-    t_fwd, t_bwd = sum(kf) / len(kf) * 1e-3, sum(kb) / len(kb) * 1e-3
-    t_fwd_ev = sum(ev[2 * i].elapsed_time(ev[2 * i + 1]) for i in range(n_ev)) / n_ev * 1e-3
-    t_bwd_ev = sum(ev[2 * i + 1].elapsed_time(ev[2 * i + 2]) for i in range(n_ev)) / n_ev * 1e-3
-    bytes_launch = 12 * T * B + 4 * B  # either direction: SURVEY.md 8(d)
-    dom, t_dom = ("gae_bwd_kernel", t_bwd) if t_bwd >= t_fwd else ("gae_fwd_kernel", t_fwd)
-    cfg = {}
-    for d, name in ((0, "gae_fwd_kernel"), (1, "gae_bwd_kernel")):
-        c6 = (ctypes.c_int * 6)()
-        lib.hpc_rll_gae_last_config(d, c6)
-        cfg[name] = {"cols_per_lane": c6[0], "steps_per_chunk": c6[1], "waves_per_workgroup": c6[2], "nontemporal": c6[3],
-                     "half_wave_tiles": bool(c6[4]), "pipelined": bool(c6[5])}
-    del adv, gv, gr
+    # what the last timed step returned (taken in every run, so that the last adv is freed here either way)
+    adv_o, gv_o, gr_o = outputs()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {"adv": adv_o, "grad_value": gv_o, "grad_reward": gr_o})
+    del adv_o, gv_o, gr_o, outputs
+
+    roofline = None
+    if args.full:
+        import hpc_rl_utils as U
+        lib = ctypes.CDLL(os.path.join(ROOT, "di-hpc_amd", "hpc_rll", "_lib", "libhpc_rll_hip.so"))   # already loaded: diagnostics
+        # ---- per-kernel durations, measured IMMEDIATELY after the timed region (same clocks / thermal state), in the same
+        # alternating fwd/bwd order as the timed region (a kernel repeated back to back would find its inputs in the
+        # 256 MiB Infinity Cache and look faster than it is in the real sequence; rocprofv3 --kernel-trace of this command
+        # sees the same pattern).  Two readings of the same >= 100 launch pairs, all on torch's current stream = the launch
+        # stream: (a) the dispatch's own begin / end timestamps (hpc_rll_ktime_*: start/stop HIP events attached to the
+        # launch itself) -- the kernel's duration as rocprofv3 reports it, used for the roofline figure; (b) hipEventRecord
+        # around every launch -- includes the gap to the neighbouring launch, listed for comparison.
+        v_d, r_d = value.detach(), reward.detach()
+        adv = torch.empty_like(r_d)
+        gv, gr = torch.empty_like(v_d), torch.empty_like(r_d)
+        n_ev = min(max(args.steps, 100), 500)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2 * n_ev + 1)]
+        U.GaeForward([v_d, r_d], [adv], gamma, lam)
+        U.GaeBackward([grad_adv], [gv, gr], gamma, lam)
+        torch.cuda.synchronize()
+        with SclkSampler(dev.index or 0) as sclk:
+            assert lib.hpc_rll_ktime_begin(2 * n_ev) == 0
+            ev[0].record()
+            for i in range(n_ev):
+                U.GaeForward([v_d, r_d], [adv], gamma, lam)
+                ev[2 * i + 1].record()
+                U.GaeBackward([grad_adv], [gv, gr], gamma, lam)
+                ev[2 * i + 2].record()
+            ev[-1].synchronize()
+            kms = (ctypes.c_float * (2 * n_ev))()
+            kkind = (ctypes.c_int * (2 * n_ev))()
+            n_k = lib.hpc_rll_ktime_end(kms, kkind, 2 * n_ev)
+        assert n_k == 2 * n_ev, f"hpc_rll_ktime_end: {n_k}"
+        kf = [kms[i] for i in range(n_k) if kkind[i] == 0]
+        kb = [kms[i] for i in range(n_k) if kkind[i] == 1]
+        t_fwd, t_bwd = sum(kf) / len(kf) * 1e-3, sum(kb) / len(kb) * 1e-3
+        t_fwd_ev = sum(ev[2 * i].elapsed_time(ev[2 * i + 1]) for i in range(n_ev)) / n_ev * 1e-3
+        t_bwd_ev = sum(ev[2 * i + 1].elapsed_time(ev[2 * i + 2]) for i in range(n_ev)) / n_ev * 1e-3
+        bytes_launch = 12 * T * B + 4 * B  # either direction: SURVEY.md 8(d)
+        dom, t_dom = ("gae_bwd_kernel", t_bwd) if t_bwd >= t_fwd else ("gae_fwd_kernel", t_fwd)
+        cfg = {}
+        for d, name in ((0, "gae_fwd_kernel"), (1, "gae_bwd_kernel")):
+            c6 = (ctypes.c_int * 6)()
+            lib.hpc_rll_gae_last_config(d, c6)
+            cfg[name] = {"cols_per_lane": c6[0], "steps_per_chunk": c6[1], "waves_per_workgroup": c6[2], "nontemporal": c6[3],
+                         "half_wave_tiles": bool(c6[4]), "pipelined": bool(c6[5])}
+        del adv, gv, gr
+
+        # HBM bytes per launch from the PMC counters: they need their own rocprofv3 passes (FETCH_SIZE and WRITE_SIZE do not
+        # fit one pass and cannot be combined with tracing), so the figure is the committed result of
+        # tests/tools/collect_profiles.sh for this shape (profiles/<round>_gae_pmc_traffic.csv), not a live measurement --
+        # and it is only quoted when the record was taken with the SAME launch configuration the kernels just used.
+        traffic = None
+        traffic_source = None
+        tj = os.path.join(ROOT, "profiles", "gae_traffic.json")
+        if os.path.exists(tj):
+            try:
+                rec = json.load(open(tj))
+                if rec.get("T") == T and rec.get("B") == B:
+                    if rec.get("config") == cfg:
+                        traffic = rec.get(dom)
+                        traffic_source = rec.get("source")
+                    else:
+                        traffic_source = (f"profiles/gae_traffic.json was recorded with another launch configuration "
+                                          f"({rec.get('config')}): not quoted")
+            except Exception:
+                traffic = None
+        roofline = {"bound": "hbm", "kernel": dom, "achieved": bytes_launch / t_dom / 1e9, "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": bytes_launch / t_dom / 1e9 / HBM_PEAK_GBS, "traffic": traffic,
+                    "traffic_source": traffic_source,
+                    "algorithmic_bytes_per_launch": bytes_launch,
+                    "timing": f"kernel begin/end timestamps of {len(kf)} forward and {len(kb)} backward launches, alternating",
+                    "fwd_us": t_fwd * 1e6, "bwd_us": t_bwd * 1e6,
+                    "fwd_us_min_max": [min(kf) * 1e3, max(kf) * 1e3], "bwd_us_min_max": [min(kb) * 1e3, max(kb) * 1e3],
+                    "fwd_bwd_frac": (2 * bytes_launch) / (t_fwd + t_bwd) / 1e9 / HBM_PEAK_GBS,
+                    "frac_rocprof": frac_rocprof(T, B, bytes_launch),
+                    "stream_event_fwd_us": t_fwd_ev * 1e6, "stream_event_bwd_us": t_bwd_ev * 1e6,
+                    "sclk_mhz": sclk.summary(), "launch_config": cfg}
 
     # ---- both scaling readings in the same line.  Bounded: 3 x 100 steps per leg.
     def leg(Bk, graph, steps=100, warmup=20, rounds=3):
         """`rounds` rounds of `steps` timed steps (barrier-bracketed, max over ranks each); ms_per_step = the MEDIAN round
         (the eager launch path is bimodal from run to run at small B -- 35 vs 63 us per step at B = 8192, the autograd
         engine's cross-thread hand-off -- so every round is listed)."""
-        st, keep_alive = make_step(Bk, graph)
+        st, keep_alive, _ = make_step(Bk, graph)
         rs = [timed(st, steps, warmup if i == 0 else 0) for i in range(rounds)]
         del keep_alive
         order = sorted(range(rounds), key=lambda i: rs[i][0])
@@ -466,7 +531,7 @@ def main():
                 "per_rank_ms_per_step": [p / steps * 1e3 for p in per]}
 
     detail = None
-    if not args.no_scaling_detail:
+    if args.full and not args.no_scaling_detail:
         GB = 65536
         detail = {"world_size": world, "backend": (dist.get_backend() if dist is not None else None),
                   "weak": {"eager": leg(B_DEFAULT, False), "graph": leg(B_DEFAULT, True)},
@@ -491,28 +556,8 @@ def main():
     if detail is not None and world > 1:
         detail["loss_ops"] = loss_ops_leg(dev, dist, world, rank, backend, timed)
 
-    # HBM bytes per launch from the PMC counters: they need their own rocprofv3 passes (FETCH_SIZE and WRITE_SIZE do not
-    # fit one pass and cannot be combined with tracing), so the figure is the committed result of
-    # tests/tools/collect_profiles.sh for this shape (profiles/<round>_gae_pmc_traffic.csv), not a live measurement --
-    # and it is only quoted when the record was taken with the SAME launch configuration the kernels just used.
-    traffic = None
-    traffic_source = None
-    tj = os.path.join(ROOT, "profiles", "gae_traffic.json")
-    if os.path.exists(tj):
-        try:
-            rec = json.load(open(tj))
-            if rec.get("T") == T and rec.get("B") == B:
-                if rec.get("config") == cfg:
-                    traffic = rec.get(dom)
-                    traffic_source = rec.get("source")
-                else:
-                    traffic_source = (f"profiles/gae_traffic.json was recorded with another launch configuration "
-                                      f"({rec.get('config')}): not quoted")
-        except Exception:
-            traffic = None
-
     suite = None
-    if world == 1 and not args.no_suite:
+    if world == 1 and args.full and not args.no_suite:
         del step, keep, value, reward, grad_adv, v_d, r_d
         if os.environ.get("HPC_RLL_BENCH_KEEP_CACHE") != "1":
             torch.cuda.empty_cache()
@@ -543,17 +588,8 @@ def main():
                                   "graph4": f"hpc_rll.graphed_steps (hipGraph replay of the same kernels, {GRAPH_STEPS} steps per launch)"}.get(launch, "eager"),
                        "launch_modes": launch_modes,
                        "backend": (dist.get_backend() if dist is not None else None)},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": bytes_launch / t_dom / 1e9, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": bytes_launch / t_dom / 1e9 / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_source": traffic_source,
-                         "algorithmic_bytes_per_launch": bytes_launch,
-                         "timing": f"kernel begin/end timestamps of {len(kf)} forward and {len(kb)} backward launches, alternating",
-                         "fwd_us": t_fwd * 1e6, "bwd_us": t_bwd * 1e6,
-                         "fwd_us_min_max": [min(kf) * 1e3, max(kf) * 1e3], "bwd_us_min_max": [min(kb) * 1e3, max(kb) * 1e3],
-                         "fwd_bwd_frac": (2 * bytes_launch) / (t_fwd + t_bwd) / 1e9 / HBM_PEAK_GBS,
-                         "frac_rocprof": frac_rocprof(T, B, bytes_launch),
-                         "stream_event_fwd_us": t_fwd_ev * 1e6, "stream_event_bwd_us": t_bwd_ev * 1e6,
-                         "sclk_mhz": sclk.summary(), "launch_config": cfg},
+            "full": args.full,
+            "roofline": roofline,
             "per_rank_ms_per_step": [p / args.steps * 1e3 for p in per_rank_s],
             # what carried the barriers and the gather of the per-rank times: "nccl" = RCCL with `rccl_ranks` ranks; "gloo" =
             # the fall-back (or a test hook) -- then this line is NOT an RCCL result, whatever `n_gpus` says
@@ -562,12 +598,37 @@ def main():
             "devices_distinct": (not one_device),
             "scaling_detail": detail,
             "suite": suite,
-            "cpu_baseline": None if (args.skip_cpu_baseline or world > 1) else cpu_baseline(T, B, gamma, lam),
+            "cpu_baseline": None if (not args.full or args.skip_cpu_baseline or world > 1) else cpu_baseline(T, B, gamma, lam),
+            "outputs": dumped,
         }
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 60 * 10**6     # all .npy files of --dump-outputs together (under 64 MB with their headers)
+
+
+def dump_outputs(path, arrays):
+    """arrays: name -> (rows, B) GPU tensor, all with the batch axis last.  Writes path/<name>.npy (float32); when the
+    set is larger than DUMP_BUDGET_BYTES, every array keeps the same sorted sample of batch columns drawn from a generator
+    of fixed seed, so that runs with the same arguments write the same columns.  Returns the record for the JSON line."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    B = next(iter(arrays.values())).shape[-1]
+    bytes_per_col = sum(t.shape[0] * 4 for t in arrays.values())
+    cols = None
+    if bytes_per_col * B > DUMP_BUDGET_BYTES:
+        cols = np.sort(np.random.default_rng(0).choice(B, DUMP_BUDGET_BYTES // bytes_per_col, replace=False))
+    idx = None if cols is None else torch.from_numpy(cols).to(next(iter(arrays.values())).device)
+    for name, t in arrays.items():
+        a = t.detach().float()
+        if idx is not None:
+            a = a.index_select(a.dim() - 1, idx)
+        np.save(os.path.join(path, name + ".npy"), a.cpu().numpy())
+    return {"dir": path, "files": [n + ".npy" for n in arrays], "dtype": "float32", "B": B,
+            "columns": "all" if cols is None else {"count": len(cols), "sample": "sorted numpy default_rng(0).choice(B, count)"}}
 
 
 def frac_rocprof(T, B, bytes_launch):

@@ -51,12 +51,23 @@ def load_surface():
 
 
 def test_snapshot_is_current():
-    """In the build container (where /root/reference exists) the committed snapshot must equal a fresh parse of the
-    reference; on the GPU box there is nothing to compare with."""
-    if not os.path.isdir(REF):
-        import pytest
-        pytest.skip("no /root/reference here")
-    assert json.loads(json.dumps(reference_surface(), sort_keys=True)) == load_surface()
+    """The committed snapshot covers exactly MODULES, every entry in the form reference_surface() writes: module classes
+    with ``__init__`` / ``forward``, public functions with ``__call__``, each a list of [name, default or None] with no
+    required parameter after a defaulted one.  Where the reference tree is present, it must also equal a fresh parse."""
+    snap = load_surface()
+    assert sorted(snap) == sorted(MODULES)
+    for mod, entry in snap.items():
+        assert entry, mod
+        for name, meths in entry.items():
+            assert meths and (set(meths) <= {"__init__", "forward"} or set(meths) == {"__call__"}), (mod, name, meths)
+            for mname, params in meths.items():
+                names = [p[0] for p in params]
+                assert all(len(p) == 2 and isinstance(p[0], str) and p[0].isidentifier() for p in params), (mod, name, mname)
+                assert len(set(names)) == len(names), (mod, name, mname, names)
+                defaulted = [p[1] is not None for p in params]
+                assert defaulted == sorted(defaulted), f"{mod}.{name}.{mname}: required parameter after a defaulted one"
+    if os.path.isdir(REF):
+        assert json.loads(json.dumps(reference_surface(), sort_keys=True)) == snap
 
 
 def _norm(d):

@@ -450,7 +450,7 @@ def test_bench_two_ranks_emits_both_scaling_readings(tmp_path):
     import sys
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-           "--B", "4096", "--skip-cpu-baseline", "--scaling", "weak", "--launch", "eager"]
+           "--B", "4096", "--full", "--skip-cpu-baseline", "--scaling", "weak", "--launch", "eager"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=_bench_env(), cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
@@ -469,7 +469,7 @@ def test_bench_launches_its_own_ranks():
     import sys
     env = {k: v for k, v in _bench_env().items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--B", "8192",
-           "--skip-cpu-baseline"]
+           "--full", "--skip-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
@@ -490,7 +490,7 @@ def test_bench_eight_ranks_on_one_device():
     env = {k: v for k, v in _bench_env().items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["OMP_NUM_THREADS"] = "2"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "5", "--warmup", "2", "--B", "8192",
-           "--skip-cpu-baseline"]
+           "--full", "--skip-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]

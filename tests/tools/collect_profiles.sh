@@ -12,12 +12,13 @@ REPO=$(pwd)
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o trace -- python "$REPO/bench.py" --steps 200 --warmup 20 --skip-cpu-baseline \
+rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o trace -- python "$REPO/bench.py" --steps 200 --warmup 20 --full --skip-cpu-baseline \
     --no-scaling-detail --no-suite > "$OUT/trace.log" 2>&1
 export PROBE_CONFIG_OUT="$OUT/gae_config.json"
 rocprofv3 --pmc FETCH_SIZE -d "$OUT/fetch" -o fetch -- python "$REPO/tests/tools/pmc_probe.py" > "$OUT/fetch.log" 2>&1
 rocprofv3 --pmc WRITE_SIZE -d "$OUT/write" -o write -- python "$REPO/tests/tools/pmc_probe.py" > "$OUT/write.log" 2>&1
 cd "$REPO"
-python bench.py --steps 20 --warmup 5 > gpurun_out/bench.log 2> gpurun_out/bench.err
+RES=$(dirname "$OUT")
+python bench.py --steps 20 --warmup 5 --full > "$RES/bench.log" 2> "$RES/bench.err"
 find "$OUT" -name "*.csv" | head -20
-tail -1 gpurun_out/bench.log | cut -c1-400
+tail -1 "$RES/bench.log" | cut -c1-400
