@@ -125,6 +125,110 @@ struct GaeFn : public ag::Function<GaeFn> {
     }
 };
 
+// ============================================================================================ GAE with done masks
+// Textbook GAE with episode ends (hpc_rll_gae_masked_*): value (T+1,B) stacked, or value (T,B) + next_value (T,B);
+// done / traj_flag (T,B) bool, uint8 or float32 (either may be None).  Dtypes and shapes are checked before the device
+// so that a wrong argument is named even on host tensors.
+int mask_code(const Tensor& m, const char* name) {
+    const at::ScalarType s = m.scalar_type();
+    if (s == at::kBool || s == at::kByte) return HPC_RLL_MASK_U8;
+    if (s == at::kFloat) return HPC_RLL_MASK_F32;
+    TORCH_CHECK(false, name, ": dtype ", s, " is not accepted; expected bool, uint8 or float32");
+    return -1;
+}
+
+// The masks as the kernels take them: one dtype code for both (a byte mask next to a float one becomes 0/1 floats).
+struct Masks { Tensor done, flag; int code = HPC_RLL_MASK_U8; };
+
+Masks check_gae_masked_inputs(const Tensor& value, const Tensor& reward, const OptTensor& done, const OptTensor& flag,
+                              const OptTensor& next_value) {
+    TORCH_CHECK(reward.defined() && value.defined(), "gae_masked: value and reward are required");
+    TORCH_CHECK(reward.dim() == 2, "reward: expected (T,B), got ", reward.sizes());
+    const int64_t T = reward.size(0), B = reward.size(1);
+    const bool nv = has(next_value);
+    TORCH_CHECK(value.dim() == 2 && value.size(0) == (nv ? T : T + 1) && value.size(1) == B, "value: shape ",
+                value.sizes(), ", expected ", nv ? "(T,B)" : "(T+1,B)", " = (", nv ? T : T + 1, ", ", B,
+                ") for reward ", reward.sizes(), nv ? " with next_value" : " (stacked form: row T is the bootstrap value)");
+    Masks m;
+    int codes[2] = {-1, -1};
+    const OptTensor* in[2] = {&done, &flag};
+    const char* names[2] = {"done", "traj_flag"};
+    for (int i = 0; i < 2; ++i) {
+        if (!has(*in[i])) continue;
+        const Tensor& t = **in[i];
+        codes[i] = mask_code(t, names[i]);
+        TORCH_CHECK(t.sizes() == reward.sizes(), names[i], ": shape ", t.sizes(), ", expected ", reward.sizes(),
+                    " (the shape of reward)");
+    }
+    if (nv) {
+        TORCH_CHECK(next_value->scalar_type() == at::kFloat, "next_value: dtype ", next_value->scalar_type(),
+                    ", expected float32");
+        TORCH_CHECK(next_value->sizes() == reward.sizes(), "next_value: shape ", next_value->sizes(), ", expected ",
+                    reward.sizes());
+    }
+    req(reward, "reward");
+    req(value, "value", reward.device());
+    if (nv) req(*next_value, "next_value", reward.device());
+    const at::Device dev = reward.device();
+    for (int i = 0; i < 2; ++i) {
+        if (codes[i] < 0) continue;
+        const Tensor& t = **in[i];
+        req(t, names[i], dev, t.scalar_type());
+        (i == 0 ? m.done : m.flag) = t;
+    }
+    if (codes[0] >= 0 && codes[1] >= 0 && codes[0] != codes[1]) {
+        Tensor& byte = codes[0] == HPC_RLL_MASK_U8 ? m.done : m.flag;
+        byte = byte.ne(0).to(at::kFloat);
+    }
+    m.code = (codes[0] == HPC_RLL_MASK_F32 || codes[1] == HPC_RLL_MASK_F32) ? HPC_RLL_MASK_F32 : HPC_RLL_MASK_U8;
+    return m;
+}
+
+inline const void* vptr(const Tensor& t) { return t.defined() ? t.const_data_ptr() : nullptr; }
+
+struct GaeMaskedFn : public ag::Function<GaeMaskedFn> {
+    static Tensor forward(ag::AutogradContext* ctx, const Tensor& value, const Tensor& reward, const OptTensor& done,
+                          const OptTensor& flag, const OptTensor& next_value, double gamma, double lambda) {
+        const Masks m = check_gae_masked_inputs(value, reward, done, flag, next_value);
+        const int64_t T = reward.size(0), B = reward.size(1);
+        c10::DeviceGuard g(reward.device());
+        Tensor adv = at::empty_like(reward);
+        check(hpc_rll_gae_masked_forward(fptr(value), fptr(next_value), fptr(reward), vptr(m.done), vptr(m.flag), m.code,
+                                         fmut(adv), to_int(T, "T"), to_int(B, "B"), (float)gamma, (float)lambda,
+                                         stream_of(reward.device())),
+              "hpc_rll_gae_masked_forward");
+        ctx->save_for_backward({m.done, m.flag});   // the masks, not the coefficients
+        ctx->saved_data["code"] = (int64_t)m.code;
+        ctx->saved_data["stacked"] = !has(next_value);
+        // needs_input_grad counts the tensor arguments that were passed (a None mask is not one)
+        ctx->saved_data["nv_input"] = (int64_t)(2 + has(done) + has(flag));
+        ctx->saved_data["gamma"] = gamma;
+        ctx->saved_data["lambda"] = lambda;
+        return adv;
+    }
+    static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
+        const bool stacked = ctx->saved_data["stacked"].toBool();
+        const bool need_v = ctx->needs_input_grad(0), need_r = ctx->needs_input_grad(1);
+        const bool need_n = !stacked && ctx->needs_input_grad((size_t)ctx->saved_data["nv_input"].toInt());
+        const ag::tensor_list out_none = {undef(), undef(), undef(), undef(), undef(), undef(), undef()};
+        if (!(need_v || need_r || need_n)) return out_none;
+        const auto saved = ctx->get_saved_variables();
+        Tensor ga = grads[0].contiguous();
+        req(ga, "grad_adv");
+        const int64_t T = ga.size(0), B = ga.size(1);
+        c10::DeviceGuard g(ga.device());
+        Tensor gv = need_v ? new_f32({stacked ? T + 1 : T, B}, ga.device()) : undef();
+        Tensor gr = need_r ? at::empty_like(ga) : undef();
+        Tensor gn = need_n ? at::empty_like(ga) : undef();
+        check(hpc_rll_gae_masked_backward(fptr(ga), vptr(saved[0]), vptr(saved[1]), (int)ctx->saved_data["code"].toInt(),
+                                          fmut(gv), fmut(gn), fmut(gr), stacked ? 1 : 0, to_int(T, "T"), to_int(B, "B"),
+                                          (float)ctx->saved_data["gamma"].toDouble(),
+                                          (float)ctx->saved_data["lambda"].toDouble(), stream_of(ga.device())),
+              "hpc_rll_gae_masked_backward");
+        return {gv, gr, undef(), undef(), gn, undef(), undef()};
+    }
+};
+
 // ==================================================================================================== TD(lambda)
 int td_weight_mode(const OptTensor& weight, int64_t T, int64_t B, const at::Device& dev) {
     if (!has(weight)) return 0;
@@ -867,6 +971,13 @@ PYBIND11_MODULE(hpc_rl_utils, m) {
         return GaeFn::apply(value, reward, gamma, lambda);
     }, py::arg("value"), py::arg("reward"), py::arg("gamma") = 0.99, py::arg("lambda_") = 0.97,
           "adv = GAE(value (T+1,B), reward (T,B)); differentiable wrt value and reward");
+    m.def("gae_masked", [](const Tensor& value, const Tensor& reward, const OptTensor& done, const OptTensor& traj_flag,
+                           const OptTensor& next_value, double gamma, double lambda) {
+        return GaeMaskedFn::apply(value, reward, done, traj_flag, next_value, gamma, lambda);
+    }, py::arg("value"), py::arg("reward"), py::arg("done") = py::none(), py::arg("traj_flag") = py::none(),
+          py::arg("next_value") = py::none(), py::arg("gamma") = 0.99, py::arg("lambda_") = 0.97,
+          "adv = textbook GAE with done / traj_flag masks; value (T+1,B), or value (T,B) with next_value (T,B); "
+          "differentiable wrt value, next_value and reward");
     m.def("gae_coef", [](int64_t T, double gamma, double lambda, const at::Device& dev) {
         TORCH_CHECK(dev.is_cuda(), "gae_coef: device must be a GPU");
         c10::DeviceGuard g(dev);

@@ -86,6 +86,28 @@ int hpc_rll_ktime_end(float* ms, int* kind, int max);
 int hpc_rll_gae_last_config(int dir, int* out);
 
 /* ------------------------------------------------------------------------------------------
+ * Episode-aware GAE with done / truncation masks (no reference counterpart; DI-engine's `gae` with `done` and
+ * `traj_flag`).  Textbook GAE, not the normalised variant above.  f = traj_flag, defaulting to done; for t = T-1 .. 0:
+ *     delta_t = reward_t + gamma*(1 - done_t)*nv_t - value_t,   adv_t = delta_t + gamma*lambda*(1 - f_t)*adv_{t+1}
+ * with nv_t = next_value[t] (next-value form: value, next_value (T,B)) or value[t+1] (stacked form: next_value = NULL,
+ * value (T+1,B)).  done and traj_flag are (T,B) masks of `mask_dtype`, either may be NULL (no episode ends / f = done):
+ *     HPC_RLL_MASK_U8  bool or uint8, one byte per sample, any nonzero byte counts as 1
+ *     HPC_RLL_MASK_F32 float32, (1 - m) used as written (soft masks)
+ * Backward (analytic adjoint; `stacked` = 1 for the stacked form): d_t = g_t + gamma*lambda*(1 - f_{t-1})*d_{t-1},
+ * grad_reward = d; next-value form: grad_value_t = -d_t, grad_next_value_t = gamma*(1 - done_t)*d_t; stacked form
+ * (grad_value (T+1,B), grad_next_value must be NULL): grad_value_t = -d_t [t<T] + gamma*(1 - done_{t-1})*d_{t-1} [t>=1].
+ * Any gradient output may be NULL.  Launch configuration: built-in heuristic only; no atomics, bit-reproducible.
+ * ------------------------------------------------------------------------------------------ */
+#define HPC_RLL_MASK_U8 (0)   /* bool or uint8 masks */
+#define HPC_RLL_MASK_F32 (1)  /* float32 masks */
+int hpc_rll_gae_masked_forward(const float* value, const float* next_value, const float* reward,
+                               const void* done, const void* traj_flag, int mask_dtype,
+                               float* adv, int T, int B, float gamma, float lambda, void* stream);
+int hpc_rll_gae_masked_backward(const float* grad_adv, const void* done, const void* traj_flag, int mask_dtype,
+                                float* grad_value, float* grad_next_value, float* grad_reward, int stacked,
+                                int T, int B, float gamma, float lambda, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Shared helpers of the scalar-loss ops.
  *   hpc_rll_partials_floats(n): floats of scratch ("partials") an op over n columns/samples needs.
  *   hpc_rll_scale_rows: out[i] = g[0]*in[i] (i < n_in), 0 (n_in <= i < n_out) -- the generic
