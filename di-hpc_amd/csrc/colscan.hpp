@@ -1,7 +1,8 @@
 // colscan.hpp -- generic reverse-time column scan for (T,B)-layout return ops on gfx950.
 //
-// All trajectory "return" recurrences on the hot path (TD-lambda, V-trace, UPGO; GAE has its own
-// specialised kernels in gae.hip) are first-order affine maps walked backwards in time,
+// All trajectory "return" recurrences on the hot path (TD-lambda, V-trace, UPGO, the episode-aware GAE forward of
+// gae_masked.hip; the normalised GAE of gae.hip and the episode-aware GAE backward have their own kernels) are
+// first-order affine maps walked backwards in time,
 //       s_t = b_t + a_t * s_{t+1},          t = T-1 .. 0,   s_T = init(column)
 // with per-element (a_t, b_t) computed from the row's inputs.  Affine maps compose associatively, so a
 // chunk [t0,t1) can be scanned from a zero carry (L_t, and the running product P_t of the a's) and
@@ -18,6 +19,8 @@
 // upgo_kernel.h:17-36) -- no time parallelism at all.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "wave.hpp"
 
@@ -41,10 +44,12 @@ namespace hpc_rll {
 //   template<int V> struct Row;                        per-row register payload
 //   template<int V> void init(long col, bool ok, float (&carry)[V]) const;          s_T
 //   template<int V> void load(Row<V>&, int t, long col, bool ok, bool next_in_regs) const;   issue the row's loads
+//                                                  (also called with t = 0 for rows before t = 0, whose result is unused)
 //   template<int V> void link(Row<V>& row, const Row<V>& next_row) const;           fields shared with row t+1
 //   template<int V> void coeffs(const Row<V>&, int t, float (&a)[V], float (&b)[V]) const;
 //   template<int V> void finish(const Row<V>&, int t, long col, bool ok, const float (&s)[V],
 //                               const float (&s_next)[V], float (&acc)[NACC]) const;   outputs + sums
+//                                                  (NACC = 0: no sums, `acc` is a one-element placeholder)
 // SUB (V = 1 only): sub-wave tiles for narrow batches -- a wave's 64 lanes are SUB groups of 64/SUB columns and the
 // groups own SUB DIFFERENT chunks of the time axis ("virtual waves", as gae.hip's half-wave tiles): SUB x more
 // workgroups and SUB x more steps per barrier.  At the reference's TD-lambda test shape (T=1024, B=64) the 64-column
@@ -153,19 +158,21 @@ __global__ __launch_bounds__(NW * 64) void colscan_rev_kernel(const Op op, int T
 
         typename Op::template Row<V> rows[LC];
         float L[LC][V], P[LC][V];
+        // Loads, links and the chunk-local scan.  Every load is unconditional (a load under a branch is waited for
+        // before the branch joins, which serialises the chunk's row loads): rows before t = 0 load row 0 and are not
+        // used.  Only the chunk holding t = 0 has such rows (t0 < 0); every other chunk runs the body without row guards.
+        auto chunk = [&](auto guard) {
+            auto live = [&](int j) { return !decltype(guard)::value || t0 + j >= 0; };
 #pragma unroll
-        for (int j = LC - 1; j >= 0; --j)
-            if (t0 + j >= 0) op.template load<V>(rows[j], t0 + j, col, ok, j < LC - 1);
+            for (int j = LC - 1; j >= 0; --j) op.template load<V>(rows[j], live(j) ? t0 + j : 0, col, ok, j < LC - 1);
 #pragma unroll
-        for (int j = LC - 2; j >= 0; --j)
-            if (t0 + j >= 0) op.template link<V>(rows[j], rows[j + 1]);
-        {
+            for (int j = LC - 2; j >= 0; --j) op.template link<V>(rows[j], rows[j + 1]);
             float a[V], p[V];
 #pragma unroll
             for (int k = 0; k < V; ++k) { a[k] = 0.f; p[k] = 1.f; }
 #pragma unroll
             for (int j = LC - 1; j >= 0; --j) {
-                if (t0 + j >= 0) {
+                if (live(j)) {
                     float ca[V], cb[V];
                     op.template coeffs<V>(rows[j], t0 + j, ca, cb);
 #pragma unroll
@@ -177,7 +184,9 @@ __global__ __launch_bounds__(NW * 64) void colscan_rev_kernel(const Op op, int T
 #pragma unroll
                 for (int k = 0; k < V; ++k) { L[j][k] = a[k]; P[j][k] = p[k]; }
             }
-        }
+        };
+        if (t0 >= 0) chunk(std::false_type{});
+        else chunk(std::true_type{});
 #pragma unroll
         for (int k = 0; k < V; ++k) {
             s_l0[(buf * NWV + w) * TILE + cl * V + k] = L[0][k];
@@ -218,7 +227,7 @@ __global__ __launch_bounds__(NW * 64) void colscan_rev_kernel(const Op op, int T
         }
     }
 
-    if (NACC > 0) {
+    if constexpr (NACC > 0) {
         // deterministic workgroup reduction of the NACC running sums
 #pragma unroll
         for (int k = 0; k < NACC; ++k) {

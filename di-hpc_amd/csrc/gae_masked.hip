@@ -7,18 +7,17 @@
 //     backward: d_t   = g_t + a_{t-1} * d_{t-1};  dL/dr_t = d_t;
 //               next-value form: dL/dV_t = -d_t,  dL/dnv_t = gamma*k^d_t*d_t
 //               stacked form   : dL/dV_t = -d_t [t<T] + gamma*k^d_{t-1}*d_{t-1} [t>=1]   (t = 0 .. T)
-// Same chunked affine scan as gae.hip (a chunk [t0,t1) is scanned from a zero carry and repaired with
-// adv_t = L_t + P_t * adv_{t1}), except that the coefficient now differs per column: the chunk product P is carried
-// PER LANE (P[LC][V] registers instead of one wave-uniform P[LC]) and exchanged through LDS next to the chunk head L.
+// Forward: an Op of the generic reverse column scan (colscan.hpp, s_t = b_t + a_t * s_{t+1}) with b = delta,
+// a = gamma*lambda*k^f and no loss sums (NACC = 0).  The coefficient differs per column, so the chunk product is per lane,
+// as in every colscan Op; the stacked form loads LC+1 value rows per chunk (`link` takes value[t+1] from the next row).
+// Backward: its own kernel, the same chunked scan run forward in time (chunks aligned to t = 0, wave 0 earliest).  It was
+// also run as a colscan Op on the time-reversed view u = T-1-t (bit-identical), and measured 6-11 % slower at C2 and at
+// T=1024, B=4096 (profiles/r08_masked_gae_colscan_ab.txt), so it stays here.
 //
-// Mapping (HBM-bound; stacked form with a byte `done`: 13 B/sample each way):
-//   * lane <-> V consecutive columns, wave <-> LC consecutive time steps held in VGPRs, workgroup = NW waves covering
-//     NW*LC steps of one column tile, one barrier per NW*LC steps; HALF: 32-column tiles whose two half-waves own two
-//     different time chunks (narrow batches, as in gae.hip).
 //   * masks are loaded as they are stored: V bytes per lane for bool / uint8 (one dword for V = 4), V floats for float32.
 //     traj_flag == NULL reuses the `done` registers (no second mask stream).
-//   * every load is unconditional: row indices of the ragged chunk are clamped into [0, T) and out-of-range columns read
-//     the last pack of the row; only the computation (per-step guards) and the stores are conditional.
+//   * out-of-range columns load the last pack of the row and store nothing.  Backward loads are unconditional (row indices
+//     of the ragged chunk are clamped into [0, T)); the forward's rows before t = 0 load row 0 (colscan).
 //   * grid = ceil(B / TILE) workgroups, no inter-workgroup communication, no atomics: results are bit-reproducible, and
 //     a column's result does not depend on the other columns.  Batch shards get the full batch's forward bits (every
 //     configuration uses 8-step chunks); backward bits when the shard runs the same backward chunk length, otherwise
@@ -29,14 +28,16 @@
 
 #include <type_traits>
 
+#include "colscan.hpp"
 #include "hpc_rll_hip.h"
-#include "wave.hpp"
 
 namespace hpc_rll {
 namespace {
 
 // mask modes: which of done / traj_flag are present (MM_DONE: f = done, one stream)
 enum { MM_NONE = 0, MM_DONE = 1, MM_BOTH = 2, MM_FLAG = 3 };
+constexpr bool has_done(int mm) { return mm == MM_DONE || mm == MM_BOTH; }
+constexpr bool has_flag(int mm) { return mm == MM_BOTH || mm == MM_FLAG; }
 
 // One row of a mask as loaded: MT = 0 -> V bytes (bool / uint8; nonzero = 1), MT = 1 -> V floats (soft masks).
 template <int V, int MT> struct MaskRow;
@@ -56,132 +57,49 @@ template <int V> struct MaskRow<V, 1> {
     __device__ __forceinline__ float keep(int k) const { return 1.f - x.v[k]; }
 };
 
-// ------------------------------------------------------------------------------------------------
-// forward: reverse-time scan, chunks aligned to the END of the trajectory, wave NWV-1 owns the latest chunk
-// ------------------------------------------------------------------------------------------------
-template <int V, int LC, int NW, bool HALF, bool NTL, int MT, int MM, bool NVF>
-__global__ __launch_bounds__(NW * 64) void gae_masked_fwd_kernel(const float* __restrict__ value,
-                                                                 const float* __restrict__ next_value,
-                                                                 const float* __restrict__ reward,
-                                                                 const void* __restrict__ done,
-                                                                 const void* __restrict__ flag,
-                                                                 float* __restrict__ adv, int T, int B, float gamma,
-                                                                 float gl) {
-    static_assert(!HALF || V == 1, "half-wave tiles hold one column per lane");
-    constexpr bool HD = MM == MM_DONE || MM == MM_BOTH;    // done present
-    constexpr bool HF = MM == MM_BOTH || MM == MM_FLAG;    // separate traj_flag present
-    constexpr int NWV = HALF ? 2 * NW : NW;
-    constexpr int TILE = HALF ? 32 : 64 * V;
-    // [buf][wave][TILE] chunk-head values, then [buf][wave][TILE] per-lane chunk products
-    __shared__ float lds[4 * NWV * TILE];
-    float* const s_l0 = lds;
-    float* const s_p0 = lds + 2 * NWV * TILE;
+// Forward Op: row t holds V_t, nv_t, r_t and the masks of step t; the stacked form takes nv_t from row t+1's V.
+// NACC = 0: `finish` receives the kernel's one-element placeholder for the sums.
+template <int MT, int MM, bool NVF, bool NTL>
+struct MaskedGaeFwdOp {
+    static constexpr int NACC = 0;
+    static constexpr bool HD = has_done(MM), HF = has_flag(MM);
+    const float* value; const float* next_value; const float* reward; const void* done; const void* flag;
+    float* adv; int T, B; float gamma, gl;   // gl = gamma*lambda
+    template <int V> struct Row { Pack<V> v0, v1, r; MaskRow<V, MT> md, mf; };
 
-    const int lane = threadIdx.x & 63;
-    const int wr = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int cl = HALF ? (lane & 31) : lane;
-    const int w = HALF ? 2 * wr + (lane >> 5) : wr;
-    const long col = (long)blockIdx.x * TILE + (long)cl * V;
-    const bool col_ok = col < (long)B;                   // dispatcher guarantees B % V == 0
-    const long lcol = col_ok ? col : (long)B - V;        // loads of idle lanes stay inside the row
-
-    float carry[V];
+    template <int V> __device__ void init(long, bool, float (&carry)[V]) const {
 #pragma unroll
-    for (int k = 0; k < V; ++k) carry[k] = 0.f;
-
-    constexpr int SPAN = NWV * LC;
-    const int n_iter = (T + SPAN - 1) / SPAN;
-
-    for (int it = 0; it < n_iter; ++it) {
-        const int t1 = T - (it * NWV + (NWV - 1 - w)) * LC;   // exclusive end, may be <= 0
-        const int t0 = t1 - LC;
-        const int buf = it & 1;
-
-        float L[LC][V];
-        float P[LC][V];
-        auto body = [&](auto guard_) {
-            constexpr bool GUARD = decltype(guard_)::value != 0;
-            auto row = [&](int t, int hi) { return GUARD ? (t < 0 ? 0 : (t > hi ? hi : t)) : t; };
-            Pack<V> vr[LC + 1], nr[NVF ? LC : 1], rr[LC];
-            MaskRow<V, MT> md[HD ? LC : 1], mf[HF ? LC : 1];
-#pragma unroll
-            for (int j = LC; j >= 0; --j) {
-                if (!NVF || j < LC) vr[j] = load_pack<V, NTL>(value + (size_t)row(t0 + j, NVF ? T - 1 : T) * B + lcol);
-            }
-#pragma unroll
-            for (int j = LC - 1; j >= 0; --j) {
-                const size_t o = (size_t)row(t0 + j, T - 1) * B + lcol;
-                rr[j] = load_pack<V, NTL>(reward + o);
-                if (NVF) nr[j] = load_pack<V, NTL>(next_value + o);
-                if (HD) md[j].template load<NTL>(done, o);
-                if (HF) mf[j].template load<NTL>(flag, o);
-            }
-            float a[V], p[V];
-#pragma unroll
-            for (int k = 0; k < V; ++k) { a[k] = 0.f; p[k] = 1.f; }
-#pragma unroll
-            for (int j = LC - 1; j >= 0; --j) {
-                if (!GUARD || t0 + j >= 0) {
-#pragma unroll
-                    for (int k = 0; k < V; ++k) {
-                        const float nv = NVF ? nr[j].v[k] : vr[j + 1].v[k];
-                        const float gd = HD ? gamma * md[j].keep(k) : gamma;
-                        const float c = HF ? gl * mf[j].keep(k) : (HD ? gl * md[j].keep(k) : gl);
-                        const float delta = fmaf(gd, nv, rr[j].v[k]) - vr[j].v[k];
-                        a[k] = fmaf(c, a[k], delta);
-                        p[k] *= c;
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < V; ++k) { L[j][k] = a[k]; P[j][k] = p[k]; }
-            }
-        };
-        if (t0 >= 0) body(std::integral_constant<int, 0>{});
-        else body(std::integral_constant<int, 1>{});
-
-        // ---- publish this chunk's head (value at t0 from a zero carry, product over the chunk), per lane
+        for (int k = 0; k < V; ++k) carry[k] = 0.f;
+    }
+    template <int V> __device__ void load(Row<V>& row, int t, long col, bool ok, bool next_in_regs) const {
+        const size_t o = (size_t)t * B + (ok ? col : (long)B - V);
+        row.v0 = load_pack<V, NTL>(value + o);
+        if (NVF) row.v1 = load_pack<V, NTL>(next_value + o);
+        else if (!next_in_regs) row.v1 = load_pack<V, NTL>(value + o + B);
+        row.r = load_pack<V, NTL>(reward + o);
+        if (HD) row.md.template load<NTL>(done, o);
+        if (HF) row.mf.template load<NTL>(flag, o);
+    }
+    template <int V> __device__ void link(Row<V>& row, const Row<V>& nxt) const {
+        if (!NVF) row.v1 = nxt.v0;
+    }
+    template <int V> __device__ void coeffs(const Row<V>& row, int, float (&a)[V], float (&b)[V]) const {
 #pragma unroll
         for (int k = 0; k < V; ++k) {
-            s_l0[(buf * NWV + w) * TILE + cl * V + k] = L[0][k];
-            s_p0[(buf * NWV + w) * TILE + cl * V + k] = P[0][k];
+            const float gd = HD ? gamma * row.md.keep(k) : gamma;
+            a[k] = HF ? gl * row.mf.keep(k) : (HD ? gl * row.md.keep(k) : gl);
+            b[k] = fmaf(gd, row.v1.v[k], row.r.v[k]) - row.v0.v[k];
         }
-        __syncthreads();
-
-        // ---- resolve carries: walk the NWV chunks from the latest to the earliest
-        float A[V], Aw[V];
-#pragma unroll
-        for (int k = 0; k < V; ++k) { A[k] = carry[k]; Aw[k] = 0.f; }
-#pragma unroll
-        for (int u = NWV - 1; u >= 0; --u) {
-            if (u == w) {
-#pragma unroll
-                for (int k = 0; k < V; ++k) Aw[k] = A[k];
-            }
-#pragma unroll
-            for (int k = 0; k < V; ++k) {
-                const int s = (buf * NWV + u) * TILE + cl * V + k;
-                A[k] = fmaf(s_p0[s], A[k], s_l0[s]);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < V; ++k) carry[k] = A[k];
-
-        // ---- repair and store
-        if (col_ok) {
-#pragma unroll
-            for (int j = LC - 1; j >= 0; --j) {
-                const int t = t0 + j;
-                if (t >= 0) {
-                    Pack<V> o;
-#pragma unroll
-                    for (int k = 0; k < V; ++k) o.v[k] = fmaf(P[j][k], Aw[k], L[j][k]);
-                    store_pack<V, true>(adv + (size_t)t * B + col, o);
-                }
-            }
-        }
-        // no second barrier: the next iteration writes the other LDS buffer (see gae_fwd_kernel)
     }
-}
+    template <int V> __device__ void finish(const Row<V>&, int t, long col, bool ok, const float (&s)[V],
+                                            const float (&)[V], float (&)[1]) const {
+        if (!ok) return;
+        Pack<V> o;
+#pragma unroll
+        for (int k = 0; k < V; ++k) o.v[k] = s[k];
+        store_pack<V, true>(adv + (size_t)t * B + col, o);
+    }
+};
 
 // ------------------------------------------------------------------------------------------------
 // backward: forward-time scan d_t = g_t + a_{t-1} d_{t-1}, chunks aligned to t = 0, wave 0 earliest.
@@ -197,8 +115,7 @@ __global__ __launch_bounds__(NW * 64) void gae_masked_bwd_kernel(const float* __
                                                                  float* __restrict__ grad_reward, int T, int B,
                                                                  float gamma, float gl) {
     static_assert(!HALF || V == 1, "half-wave tiles hold one column per lane");
-    constexpr bool HD = MM == MM_DONE || MM == MM_BOTH;
-    constexpr bool HF = MM == MM_BOTH || MM == MM_FLAG;
+    constexpr bool HD = has_done(MM), HF = has_flag(MM);
     constexpr int NWV = HALF ? 2 * NW : NW;
     constexpr int TILE = HALF ? 32 : 64 * V;
     __shared__ float lds[4 * NWV * TILE];
@@ -393,6 +310,14 @@ inline int max_vec(int B, int mt, std::initializer_list<const void*> f32, std::i
     return ok ? 2 : 1;
 }
 
+// One scan launch of `op` in configuration (V, LC, NW, HALF); HALF: 32-column tiles, two half-waves per wave (SUB = 2).
+template <int V, int LC, int NW, bool HALF, class Op>
+inline void launch(const Op& op, int T, int B, hipStream_t st) {
+    constexpr int TILE = HALF ? 32 : 64 * V;
+    hipLaunchKernelGGL((colscan_rev_kernel<Op, V, LC, NW, HALF ? 2 : 1>), dim3((unsigned)((B + TILE - 1) / TILE)),
+                       dim3(NW * 64), 0, st, op, T, B, (float*)nullptr, ScanFold{});
+}
+
 inline int check_launch() {
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? HPC_RLL_OK : (int)e;
@@ -417,14 +342,11 @@ extern "C" int hpc_rll_gae_masked_forward(const float* value, const float* next_
     const float gl = gamma * lambda;
     hipStream_t st = (hipStream_t)stream;
     with_cfg<true>(idx, [&](auto V_, auto LC_, auto NW_, auto H_, auto N_) {
-        constexpr int V = decltype(V_)::value, LC = decltype(LC_)::value, NW = decltype(NW_)::value;
-        constexpr bool HALF = decltype(H_)::value != 0, NTL = decltype(N_)::value != 0;
-        constexpr int TILE = HALF ? 32 : 64 * V;
         with_mode(mask_dtype, mask_mode(done, traj_flag), next_value != nullptr, [&](auto MT_, auto MM_, auto NV_) {
-            hipLaunchKernelGGL((gae_masked_fwd_kernel<V, LC, NW, HALF, NTL, decltype(MT_)::value, decltype(MM_)::value,
-                                                      decltype(NV_)::value != 0>),
-                               dim3((unsigned)((B + TILE - 1) / TILE)), dim3(NW * 64), 0, st, value, next_value, reward,
-                               done, traj_flag, adv, T, B, gamma, gl);
+            const MaskedGaeFwdOp<decltype(MT_)::value, decltype(MM_)::value, decltype(NV_)::value != 0,
+                                 decltype(N_)::value != 0>
+                op{value, next_value, reward, done, traj_flag, adv, T, B, gamma, gl};
+            launch<decltype(V_)::value, decltype(LC_)::value, decltype(NW_)::value, decltype(H_)::value != 0>(op, T, B, st);
         });
     });
     return check_launch();
