@@ -1,7 +1,8 @@
 // colscan.hpp -- generic reverse-time column scan for (T,B)-layout return ops on gfx950.
 //
 // All trajectory "return" recurrences on the hot path (TD-lambda, V-trace, UPGO, the episode-aware GAE forward of
-// gae_masked.hip; the normalised GAE of gae.hip and the episode-aware GAE backward have their own kernels) are
+// gae_masked.hip, the episode-aware TD-lambda / V-trace of scan_masked.hip; the normalised GAE of gae.hip and the
+// episode-aware GAE backward have their own kernels) are
 // first-order affine maps walked backwards in time,
 //       s_t = b_t + a_t * s_{t+1},          t = T-1 .. 0,   s_T = init(column)
 // with per-element (a_t, b_t) computed from the row's inputs.  Affine maps compose associatively, so a
@@ -301,9 +302,8 @@ inline void launch_colscan(const Op& op, const ScanCfg& c, int T, int B, float* 
     }
     HPC_RLL_SCAN_CASE(1, 1) HPC_RLL_SCAN_CASE(1, 2) HPC_RLL_SCAN_CASE(1, 4) HPC_RLL_SCAN_CASE(1, 8)
     HPC_RLL_SCAN_CASE(1, 16)
-    if constexpr (ALLOW_V2) {
+    if constexpr (ALLOW_V2) {   // no (2, 16): scan_cfg gives V = 2 only from 512 workgroups, where 8 waves reach the target
         HPC_RLL_SCAN_CASE(2, 1) HPC_RLL_SCAN_CASE(2, 2) HPC_RLL_SCAN_CASE(2, 4) HPC_RLL_SCAN_CASE(2, 8)
-        HPC_RLL_SCAN_CASE(2, 16)
     }
 #undef HPC_RLL_SCAN_CASE
 }
@@ -314,5 +314,18 @@ inline int scan_num_blocks(int T, int B, bool can_v2) { return (int)scan_grid(sc
 int finalize_sums(const float* partials, int nblocks, int nacc, const float* scales /*host, nacc*/, float* out,
                   hipStream_t st);
 int scale_rows(const float* g, const float* in, float* out, long n_in, long n_out, hipStream_t st);
+
+// scan launch + finalisation of its NACC sums into `out` (x scale[k]): one launch when a ticket is available (make_fold),
+// otherwise the scan leaves partials and finalize_sums adds them in a second launch
+template <class Op, bool ALLOW_V2, bool ALLOW_LC16 = false>
+inline int scan_and_finalize(const Op& op, const ScanCfg& c, int T, int B, float* partials, int nacc, const float* scale,
+                             float* out, hipStream_t st) {
+    const ScanFold fold = make_fold(st, nacc, scale, out, (long)scan_grid(c, B));
+    launch_colscan<Op, ALLOW_V2, ALLOW_LC16>(op, c, T, B, partials, st, fold);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    if (fold.out) return 0;
+    return finalize_sums(partials, (int)scan_grid(c, B), nacc, scale, out, st);
+}
 
 }  // namespace hpc_rll

@@ -14,8 +14,9 @@
 // also run as a colscan Op on the time-reversed view u = T-1-t (bit-identical), and measured 6-11 % slower at C2 and at
 // T=1024, B=4096 (profiles/r08_masked_gae_colscan_ab.txt), so it stays here.
 //
-//   * masks are loaded as they are stored: V bytes per lane for bool / uint8 (one dword for V = 4), V floats for float32.
-//     traj_flag == NULL reuses the `done` registers (no second mask stream).
+//   * masks are loaded as they are stored (masks.hpp, shared with the masked TD(lambda) / V-trace of scan_masked.hip):
+//     V bytes per lane for bool / uint8 (one dword for V = 4), V floats for float32.  traj_flag == NULL reuses the `done`
+//     registers (no second mask stream).
 //   * out-of-range columns load the last pack of the row and store nothing.  Backward loads are unconditional (row indices
 //     of the ragged chunk are clamped into [0, T)); the forward's rows before t = 0 load row 0 (colscan).
 //   * grid = ceil(B / TILE) workgroups, no inter-workgroup communication, no atomics: results are bit-reproducible, and
@@ -30,32 +31,10 @@
 
 #include "colscan.hpp"
 #include "hpc_rll_hip.h"
+#include "masks.hpp"
 
 namespace hpc_rll {
 namespace {
-
-// mask modes: which of done / traj_flag are present (MM_DONE: f = done, one stream)
-enum { MM_NONE = 0, MM_DONE = 1, MM_BOTH = 2, MM_FLAG = 3 };
-constexpr bool has_done(int mm) { return mm == MM_DONE || mm == MM_BOTH; }
-constexpr bool has_flag(int mm) { return mm == MM_BOTH || mm == MM_FLAG; }
-
-// One row of a mask as loaded: MT = 0 -> V bytes (bool / uint8; nonzero = 1), MT = 1 -> V floats (soft masks).
-template <int V, int MT> struct MaskRow;
-template <int V> struct MaskRow<V, 0> {
-    using Raw = typename std::conditional<V == 1, uint8_t, typename std::conditional<V == 2, uint16_t, uint32_t>::type>::type;
-    Raw x;
-    template <bool NT> __device__ __forceinline__ void load(const void* base, size_t idx) {
-        x = ld<NT>(reinterpret_cast<const Raw*>(static_cast<const uint8_t*>(base) + idx));
-    }
-    __device__ __forceinline__ float keep(int k) const { return ((x >> (8 * k)) & 0xffu) ? 0.f : 1.f; }
-};
-template <int V> struct MaskRow<V, 1> {
-    Pack<V> x;
-    template <bool NT> __device__ __forceinline__ void load(const void* base, size_t idx) {
-        x = load_pack<V, NT>(static_cast<const float*>(base) + idx);
-    }
-    __device__ __forceinline__ float keep(int k) const { return 1.f - x.v[k]; }
-};
 
 // Forward Op: row t holds V_t, nv_t, r_t and the masks of step t; the stacked form takes nv_t from row t+1's V.
 // NACC = 0: `finish` receives the kernel's one-element placeholder for the sums.
@@ -260,10 +239,6 @@ inline int choose_cfg(int T, int B, int vmax) {
     return nw == 8 ? 1 : 0;
 }
 
-inline bool aligned(const void* p, size_t a) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
-template <int N> using I = std::integral_constant<int, N>;
-
 // Calls f(I<V>, I<LC>, I<NW>, I<HALF>, I<NTL>) for entry `idx` of the configuration list.
 template <bool FWD, class F>
 inline void with_cfg(int idx, F&& f) {
@@ -278,36 +253,6 @@ inline void with_cfg(int idx, F&& f) {
             else f(I<2>{}, I<16>{}, I<4>{}, I<0>{}, I<1>{});
             break;
     }
-}
-
-// Calls f(I<MT>, I<MM>, I<NVF>) for the runtime mask dtype / mask mode / input form.
-template <class F>
-inline void with_mode(int mt, int mm, bool nvf, F&& f) {
-    auto form = [&](auto MT_, auto MM_) {
-        if (nvf) f(MT_, MM_, I<1>{});
-        else f(MT_, MM_, I<0>{});
-    };
-    if (mm == MM_NONE) { form(I<0>{}, I<MM_NONE>{}); return; }
-    auto mode = [&](auto MT_) {
-        if (mm == MM_DONE) form(MT_, I<MM_DONE>{});
-        else if (mm == MM_BOTH) form(MT_, I<MM_BOTH>{});
-        else form(MT_, I<MM_FLAG>{});
-    };
-    if (mt == 1) mode(I<1>{});
-    else mode(I<0>{});
-}
-
-inline int mask_mode(const void* done, const void* flag) {
-    return done ? (flag ? MM_BOTH : MM_DONE) : (flag ? MM_FLAG : MM_NONE);
-}
-
-// Widest pack (2 or 1 columns per lane) the shape and every pointer allow; masks in their own element size.
-inline int max_vec(int B, int mt, std::initializer_list<const void*> f32, std::initializer_list<const void*> masks) {
-    if (B % 2) return 1;
-    bool ok = true;
-    for (const void* p : f32) ok = ok && aligned(p, 8);
-    for (const void* p : masks) ok = ok && aligned(p, mt == 1 ? 8 : 2);
-    return ok ? 2 : 1;
 }
 
 // One scan launch of `op` in configuration (V, LC, NW, HALF); HALF: 32-column tiles, two half-waves per wave (SUB = 2).

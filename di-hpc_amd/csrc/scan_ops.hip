@@ -38,10 +38,6 @@ int categorical_backward(const float* logits, const int64_t* action, const float
 
 namespace {
 
-inline int last_error() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? HPC_RLL_OK : (int)e;
-}
 inline bool al8(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
 struct TicketPool {
@@ -84,17 +80,6 @@ inline unsigned* scan_ticket(hipStream_t st) {
     if (idx < 0) return nullptr;
     return dv.base + idx;
 }
-// scan launch + finalisation of its NACC sums into `out` (x scale[k]): one launch when a ticket is available
-template <class Op, bool ALLOW_V2, bool ALLOW_LC16 = false>
-inline int scan_and_finalize(const Op& op, const ScanCfg& c, int T, int B, float* partials, int nacc, const float* scale,
-                             float* out, hipStream_t st) {
-    const ScanFold fold = make_fold(st, nacc, scale, out, (long)scan_grid(c, B));
-    launch_colscan<Op, ALLOW_V2, ALLOW_LC16>(op, c, T, B, partials, st, fold);
-    const int rc = last_error();
-    if (rc || fold.out) return rc;
-    return finalize_sums(partials, (int)scan_grid(c, B), nacc, scale, out, st);
-}
-
 template <int V> __device__ __forceinline__ Pack<V> ldz(const float* p, bool ok) {
     if (ok) return load_pack<V>(p);
     Pack<V> z;

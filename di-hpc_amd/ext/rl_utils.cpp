@@ -140,9 +140,10 @@ int mask_code(const Tensor& m, const char* name) {
 // The masks as the kernels take them: one dtype code for both (a byte mask next to a float one becomes 0/1 floats).
 struct Masks { Tensor done, flag; int code = HPC_RLL_MASK_U8; };
 
-Masks check_gae_masked_inputs(const Tensor& value, const Tensor& reward, const OptTensor& done, const OptTensor& flag,
-                              const OptTensor& next_value) {
-    TORCH_CHECK(reward.defined() && value.defined(), "gae_masked: value and reward are required");
+// Shared by gae_masked, td_lambda_masked and vtrace_masked (`op` names the caller in the first message).
+Masks check_masked_inputs(const char* op, const Tensor& value, const Tensor& reward, const OptTensor& done,
+                          const OptTensor& flag, const OptTensor& next_value) {
+    TORCH_CHECK(reward.defined() && value.defined(), op, ": value and reward are required");
     TORCH_CHECK(reward.dim() == 2, "reward: expected (T,B), got ", reward.sizes());
     const int64_t T = reward.size(0), B = reward.size(1);
     const bool nv = has(next_value);
@@ -189,7 +190,7 @@ inline const void* vptr(const Tensor& t) { return t.defined() ? t.const_data_ptr
 struct GaeMaskedFn : public ag::Function<GaeMaskedFn> {
     static Tensor forward(ag::AutogradContext* ctx, const Tensor& value, const Tensor& reward, const OptTensor& done,
                           const OptTensor& flag, const OptTensor& next_value, double gamma, double lambda) {
-        const Masks m = check_gae_masked_inputs(value, reward, done, flag, next_value);
+        const Masks m = check_masked_inputs("gae_masked", value, reward, done, flag, next_value);
         const int64_t T = reward.size(0), B = reward.size(1);
         c10::DeviceGuard g(reward.device());
         Tensor adv = at::empty_like(reward);
@@ -374,6 +375,130 @@ struct VtraceFn : public ag::Function<VtraceFn> {
         Tensor grad_target = need_t ? at::empty_like(target) : undef();
         Tensor grad_value = need_v ? new_f32({T + 1, B}, dev) : undef();
         vtrace_backward_launch(g_pg, g_v, g_e, target, action, ws, grad_target, grad_value);
+        out[0] = grad_target;
+        out[3] = grad_value;
+        return out;
+    }
+};
+
+// ============================================================================ TD(lambda) and V-trace with done masks
+// Episode-aware returns (hpc_rll_td_lambda_masked_forward / hpc_rll_vtrace_masked_forward): the masks, the two value forms
+// and the checks of gae_masked; only the forward scans differ from td_lambda / vtrace, whose backward entry points consume
+// the saved per-sample coefficients.  Shapes and dtypes are checked before the device, so that a wrong argument is named
+// even on host tensors.
+void check_shape(const Tensor& t, const char* name, at::IntArrayRef shape, at::ScalarType dtype = at::kFloat) {
+    TORCH_CHECK(t.defined(), name, ": expected a tensor, got None");
+    TORCH_CHECK(t.scalar_type() == dtype, name, ": dtype ", t.scalar_type(), ", expected ", dtype);
+    TORCH_CHECK(t.sizes() == shape, name, ": shape ", t.sizes(), ", expected ", shape);
+}
+
+// weight None | (B,) | (T,B) -> weight_mode 0 / 1 / 2 (dtype and shape only; the device is checked by the caller)
+int masked_td_weight_mode(const OptTensor& weight, int64_t T, int64_t B) {
+    if (!has(weight)) return 0;
+    const Tensor& w = *weight;
+    TORCH_CHECK(w.scalar_type() == at::kFloat, "weight: dtype ", w.scalar_type(), ", expected float32");
+    if (w.dim() == 2 && w.size(0) == T && w.size(1) == B) return 2;
+    if (w.dim() == 1 && w.size(0) == B) return 1;
+    TORCH_CHECK(false, "weight: shape ", w.sizes(), ", expected (", T, ",", B, ") or (", B, ",)");
+}
+
+struct TdLambdaMaskedFn : public ag::Function<TdLambdaMaskedFn> {
+    static Tensor forward(ag::AutogradContext* ctx, const Tensor& value, const Tensor& reward, const OptTensor& done,
+                          const OptTensor& flag, const OptTensor& next_value, const OptTensor& weight, double gamma,
+                          double lambda, std::optional<double> scale) {
+        TORCH_CHECK(reward.defined() && value.defined(), "td_lambda_masked: value and reward are required");
+        TORCH_CHECK(reward.dim() == 2, "reward: expected (T,B), got ", reward.sizes());
+        const int64_t T = reward.size(0), B = reward.size(1);
+        const int mode = masked_td_weight_mode(weight, T, B);
+        const Masks m = check_masked_inputs("td_lambda_masked", value, reward, done, flag, next_value);
+        const at::Device dev = reward.device();
+        if (mode) req(*weight, "weight", dev);
+        c10::DeviceGuard g(dev);
+        Tensor loss = new_f32({1}, dev);
+        Tensor grad_buf = at::empty_like(reward);
+        Tensor partials = new_f32({hpc_rll_partials_floats(B)}, dev);
+        check(hpc_rll_td_lambda_masked_forward(fptr(value), fptr(next_value), fptr(reward), fptr(weight), mode,
+                                               vptr(m.done), vptr(m.flag), m.code, fmut(loss), fmut(grad_buf),
+                                               fmut(partials), to_int(T, "T"), to_int(B, "B"), (float)gamma,
+                                               (float)lambda, loss_scale(scale, T * B), stream_of(dev)),
+              "hpc_rll_td_lambda_masked_forward");
+        ctx->save_for_backward({grad_buf});
+        ctx->saved_data["stacked"] = !has(next_value);
+        return loss;
+    }
+    static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
+        const Tensor grad_buf = ctx->get_saved_variables()[0];
+        const bool stacked = ctx->saved_data["stacked"].toBool();
+        const int64_t T = grad_buf.size(0), B = grad_buf.size(1);
+        const at::Device dev = grad_buf.device();
+        c10::DeviceGuard g(dev);
+        Tensor gl = grad1(grads[0], dev, "grad_loss");
+        Tensor gv = new_f32({stacked ? T + 1 : T, B}, dev);
+        if (stacked)
+            check(hpc_rll_td_lambda_backward(fptr(gl), fptr(grad_buf), fmut(gv), (int)T, (int)B, stream_of(dev)),
+                  "hpc_rll_td_lambda_backward");
+        else
+            check(hpc_rll_scale_rows(fptr(gl), fptr(grad_buf), fmut(gv), T * B, T * B, stream_of(dev)),
+                  "hpc_rll_scale_rows");
+        ag::tensor_list out(9);
+        out[0] = gv;
+        return out;
+    }
+};
+
+struct VtraceMaskedFn : public ag::Function<VtraceMaskedFn> {
+    static ag::tensor_list forward(ag::AutogradContext* ctx, const Tensor& target, const Tensor& behaviour,
+                                   const Tensor& action, const Tensor& value, const Tensor& reward,
+                                   const OptTensor& done, const OptTensor& flag, const OptTensor& next_value,
+                                   const OptTensor& weight, double gamma, double lambda, double rho_clip,
+                                   double c_clip, double rho_pg_clip, std::optional<double> scale) {
+        TORCH_CHECK(target.defined(), "target_output: expected a tensor, got None");
+        TORCH_CHECK(target.dim() == 3, "target_output: expected (T,B,N), got ", target.sizes());
+        const int64_t T = target.size(0), B = target.size(1), N = target.size(2);
+        TORCH_CHECK(target.scalar_type() == at::kFloat, "target_output: dtype ", target.scalar_type(), ", expected ",
+                    at::kFloat);
+        check_shape(behaviour, "behaviour_output", {T, B, N});
+        check_shape(action, "action", {T, B}, at::kLong);
+        check_shape(reward, "reward", {T, B});
+        if (has(weight)) check_shape(*weight, "weight", {T, B});
+        const Masks m = check_masked_inputs("vtrace_masked", value, reward, done, flag, next_value);
+        const at::Device dev = reward.device();
+        req(target, "target_output", dev);
+        req(behaviour, "behaviour_output", dev);
+        req(action, "action", dev, at::kLong);
+        if (has(weight)) req(*weight, "weight", dev);
+        c10::DeviceGuard g(dev);
+        Tensor losses = new_f32({3}, dev);
+        Tensor ws = vtrace_workspace(T, B, dev);
+        check(hpc_rll_vtrace_masked_forward(fptr(target), fptr(behaviour), iptr(action), fptr(value), fptr(next_value),
+                                            fptr(reward), fptr(weight), vptr(m.done), vptr(m.flag), m.code,
+                                            fmut(losses), fmut(ws), to_int(T, "T"), to_int(B, "B"), to_int(N, "N"),
+                                            (float)gamma, (float)lambda, (float)rho_clip, (float)c_clip,
+                                            (float)rho_pg_clip, loss_scale(scale, T * B), stream_of(dev)),
+              "hpc_rll_vtrace_masked_forward");
+        ctx->save_for_backward({target, action, ws});
+        ctx->saved_data["stacked"] = !has(next_value);
+        return {alias_of(losses, 0, 1), alias_of(losses, 1, 1), alias_of(losses, 2, 1)};
+    }
+    static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
+        ag::tensor_list out(15);
+        const bool need_t = ctx->needs_input_grad(0), need_v = ctx->needs_input_grad(3);
+        if (!(need_t || need_v)) return out;
+        const bool stacked = ctx->saved_data["stacked"].toBool();
+        const auto saved = ctx->get_saved_variables();
+        const Tensor &target = saved[0], &action = saved[1], &ws = saved[2];
+        const at::Device dev = target.device();
+        c10::DeviceGuard g(dev);
+        const int64_t T = target.size(0), B = target.size(1);
+        Tensor g_pg = grad1(grads[0], dev, "grad_policy_loss"), g_v = grad1(grads[1], dev, "grad_value_loss"),
+               g_e = grad1(grads[2], dev, "grad_entropy_loss");
+        Tensor grad_target = need_t ? at::empty_like(target) : undef();
+        Tensor grad_value = need_v ? new_f32({stacked ? T + 1 : T, B}, dev) : undef();
+        // next-value form: the unit value gradient (ws rows 2T*B ...) has T rows and no bootstrap row to zero
+        vtrace_backward_launch(g_pg, g_v, g_e, target, action, ws, grad_target, stacked ? grad_value : undef());
+        if (need_v && !stacked)
+            check(hpc_rll_scale_rows(fptr(g_v), fptr(ws) + 2 * T * B, fmut(grad_value), T * B, T * B, stream_of(dev)),
+                  "hpc_rll_scale_rows");
         out[0] = grad_target;
         out[3] = grad_value;
         return out;
@@ -983,6 +1108,26 @@ PYBIND11_MODULE(hpc_rl_utils, m) {
         c10::DeviceGuard g(dev);
         return gae_coef(T, gamma, lambda, dev);
     });
+    m.def("td_lambda_masked", [](const Tensor& value, const Tensor& reward, const OptTensor& done,
+                                 const OptTensor& traj_flag, const OptTensor& next_value, const OptTensor& weight,
+                                 double gamma, double lambda, std::optional<double> scale) {
+        return TdLambdaMaskedFn::apply(value, reward, done, traj_flag, next_value, weight, gamma, lambda, scale);
+    }, py::arg("value"), py::arg("reward"), py::arg("done") = py::none(), py::arg("traj_flag") = py::none(),
+          py::arg("next_value") = py::none(), py::arg("weight") = py::none(), py::arg("gamma") = 0.9,
+          py::arg("lambda_") = 0.8, py::arg("scale") = py::none(),
+          "episode-aware TD(lambda) loss (1,) with done / traj_flag masks; differentiable wrt value");
+    m.def("vtrace_masked", [](const Tensor& target, const Tensor& behaviour, const Tensor& action, const Tensor& value,
+                              const Tensor& reward, const OptTensor& done, const OptTensor& traj_flag,
+                              const OptTensor& next_value, const OptTensor& weight, double gamma, double lambda,
+                              double rho_clip, double c_clip, double rho_pg_clip, std::optional<double> scale) {
+        return VtraceMaskedFn::apply(target, behaviour, action, value, reward, done, traj_flag, next_value, weight, gamma,
+                                     lambda, rho_clip, c_clip, rho_pg_clip, scale);
+    }, py::arg("target_output"), py::arg("behaviour_output"), py::arg("action"), py::arg("value"), py::arg("reward"),
+          py::arg("done") = py::none(), py::arg("traj_flag") = py::none(), py::arg("next_value") = py::none(),
+          py::arg("weight") = py::none(), py::arg("gamma") = 0.99, py::arg("lambda_") = 0.95,
+          py::arg("rho_clip_ratio") = 1.0, py::arg("c_clip_ratio") = 1.0, py::arg("rho_pg_clip_ratio") = 1.0,
+          py::arg("scale") = py::none(),
+          "episode-aware V-trace losses (policy, value, entropy) with done / traj_flag masks");
     m.def("td_lambda", [](const Tensor& value, const Tensor& reward, const OptTensor& weight, double gamma, double lambda,
                           std::optional<double> scale) {
         return TdLambdaFn::apply(value, reward, weight, gamma, lambda, scale);

@@ -8,6 +8,9 @@ buffer every call); inputs are validated; ``weight=None`` works for TD-lambda (t
 buffer as (T,B): SURVEY.md A.2); optional batch-axis data parallelism (``sharded=True``, see hpc_rll.dist).
 The autograd nodes are compiled torch::autograd::Functions in ``hpc_rl_utils`` (``td_lambda``, ``q_nstep_td``,
 ``dist_nstep_td``, ``iqn_nstep_td``, ``qrdqn_nstep_td``): one pybind call per forward.
+
+``masked_td_lambda`` / ``MaskedTDLambda`` (no reference counterpart) are episode-aware TD(lambda) with ``done`` and
+``traj_flag`` masks, the conventions of ``hpc_rll.rl_utils.gae.masked_gae``; see ``masked_td_lambda``.
 """
 from typing import Optional
 
@@ -46,6 +49,47 @@ class TDLambda(_ShardedLoss):
         """value (T+1,B), reward (T,B), weight None | (B,) | (T,B) -> loss (1,)."""
         _assert_cuda(value, reward, weight)
         return self._reduce(hpc_rl_utils.td_lambda(value, reward, weight, gamma, lambda_, self._scale(reward.numel())))
+
+
+def masked_td_lambda(value, reward, done=None, weight=None, gamma: float = 0.9, lambda_: float = 0.8, next_value=None,
+                     traj_flag=None) -> torch.Tensor:
+    r"""Episode-aware TD(lambda) loss with done and truncation masks (trfl's ``generalized_lambda_returns`` with per-step
+    ``pcontinues``).
+
+    With ``k^d_t = 1 - done_t``, ``k^f_t = 1 - f_t`` (``f = traj_flag``, default: ``done``) and ``G_T = nv_{T-1}``, for
+    ``t = T-1 .. 0``::
+
+        nv_t = next_value[t]                  (next-value form: value (T,B), next_value (T,B))
+             = value[t+1]                     (stacked form: value (T+1,B), row T the bootstrap value)
+        G_t  = reward_t + (gamma*k^d_t - gamma*lambda_*k^f_t) * nv_t + gamma*lambda_*k^f_t * G_{t+1}
+        loss = 0.5 * mean(weight * (G_t - value_t)^2)
+
+    ``k^d`` weights the bootstrap value and ``k^f`` the continuation.  ``done`` / ``traj_flag`` are (T,B) ``bool``,
+    ``uint8`` (nonzero counts as 1) or ``float32`` (``1 - m`` used as written: soft masks); ``done=None`` means no episode
+    ends.  Callers set ``traj_flag_t = 1`` wherever ``done_t = 1``.  Time-limit truncation: the next-value form with
+    ``done_t = 0``, ``traj_flag_t = 1`` and the final observation's value in ``next_value[t]``.  ``weight`` is None,
+    (B,) or (T,B).  The gradient flows to ``value`` (rows ``t < T``; the stacked bootstrap row gets zero) only: ``G`` is a
+    constant, as in :class:`TDLambda`.  With ``f = done`` the stacked form's ``G_t - value_t`` is ``masked_gae``'s
+    advantage for the same masks.
+
+    How it differs from :class:`TDLambda`: that op assumes no episode ends inside the trajectory; without masks (or with
+    all-zero masks) this one gives its loss and gradient bit for bit.  All tensors live on one GPU and are contiguous.
+    """
+    return hpc_rl_utils.td_lambda_masked(value, reward, done, traj_flag, next_value, weight, gamma, lambda_)
+
+
+class MaskedTDLambda(_ShardedLoss):
+    """Module form of :func:`masked_td_lambda`, with the data-parallel option of :class:`TDLambda` (``sharded=True``:
+    1/(global count) scale and one all-reduce of the loss)."""
+
+    def __init__(self, T, B, sharded: bool = False, group=None):
+        super().__init__()
+        self.T, self.B, self.sharded, self.group = T, B, sharded, group
+
+    def forward(self, value, reward, done=None, weight=None, gamma: float = 0.9, lambda_: float = 0.8, next_value=None,
+                traj_flag=None) -> torch.Tensor:
+        return self._reduce(hpc_rl_utils.td_lambda_masked(value, reward, done, traj_flag, next_value, weight, gamma,
+                                                          lambda_, self._scale(reward.numel())))
 
 
 class QNStepTD(_ShardedLoss):

@@ -190,6 +190,37 @@ int hpc_rll_vtrace_backward(const float* g_pg, const float* g_value, const float
                             const int64_t* action, const float* ws, float* grad_target_output, float* grad_value,
                             int T, int B, int N, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Episode-aware TD(lambda) and V-trace with done / truncation masks (no reference counterpart: hpc_rll/origin/td.py
+ * leaves terminal states to the caller).  Masks as for hpc_rll_gae_masked_*: k^d_t = 1 - done_t, k^f_t = 1 - f_t with
+ * f = traj_flag defaulting to done, (T,B) of `mask_dtype`, either may be NULL; nv_t = next_value[t] (next-value form:
+ * value, next_value (T,B)) or value[t+1] (stacked form: next_value = NULL, value (T+1,B)).  Time-limit truncation:
+ * done_t = 0, traj_flag_t = 1 and the final observation's value in next_value[t].  k^d weights the bootstrap value,
+ * k^f the continuation.  disc = gamma*lambda and gamma - disc are rounded to fp32 as in the unmasked ops.
+ *
+ * TD(lambda):  G_T = nv_{T-1},  G_t = r_t + (gamma*k^d_t - disc*k^f_t)*nv_t + disc*k^f_t*G_{t+1};
+ *   loss (1,) = 0.5*scale*sum w (G_t - V_t)^2 with weight_mode / weight as hpc_rll_td_lambda_forward; grad_buf (T,B) =
+ *   d loss / d value[:T] (G is a constant).  Backward: hpc_rll_td_lambda_backward (stacked form, grad_value (T+1,B),
+ *   last row 0) or hpc_rll_scale_rows(grad_loss, grad_buf, grad_value, T*B, T*B) (next-value form).
+ * V-trace:  IS, rho, c, rho_pg and the entropy as hpc_rll_vtrace_forward;  s_T = 0,
+ *   s_t = rho_t*(r_t + gamma*k^d_t*nv_t - V_t) + disc*k^f_t*c_t*s_{t+1}   (vs_t = V_t + s_t),
+ *   adv_t = rho_pg_t*(r_t + gamma*(k^d_t*nv_t + k^f_t*s_{t+1}) - V_t);  losses and ws as hpc_rll_vtrace_forward (same
+ *   workspace size).  Backward: hpc_rll_vtrace_backward (stacked form), or hpc_rll_vtrace_backward with grad_value = NULL
+ *   plus hpc_rll_scale_rows(g_value, ws + 2*T*B, grad_value, T*B, T*B) (next-value form).
+ * Without masks, or with all-zero masks, both equal their unmasked op bit for bit (the same launch configuration for
+ * the same (T,B)); with f = done and soft masks they are the per-step-discount forms with discount gamma*(1 - m).
+ * Argument errors: HPC_RLL_EINVAL (null pointers, bad mask_dtype / weight_mode, negative sizes), HPC_RLL_EALIGN.
+ * ------------------------------------------------------------------------------------------ */
+int hpc_rll_td_lambda_masked_forward(const float* value, const float* next_value, const float* reward,
+                                     const float* weight, int weight_mode, const void* done, const void* traj_flag,
+                                     int mask_dtype, float* loss, float* grad_buf, float* partials, int T, int B,
+                                     float gamma, float lambda, float scale, void* stream);
+int hpc_rll_vtrace_masked_forward(const float* target_output, const float* behaviour_output, const int64_t* action,
+                                  const float* value, const float* next_value, const float* reward, const float* weight,
+                                  const void* done, const void* traj_flag, int mask_dtype, float* losses, float* ws,
+                                  int T, int B, int N, float gamma, float lambda, float rho_clip, float c_clip,
+                                  float rho_pg_clip, float scale, void* stream);
+
 /* UPGO -- replaces UpgoForward/Backward (rl_utils/entry.h:148-156, src/rl_utils/upgo.cu:8-70).
  * target_output (T,B,N), rho (T,B), action (T,B), reward (T,B), value (T+1,B); loss (1,). */
 int64_t hpc_rll_upgo_workspace_floats(int T, int B);
