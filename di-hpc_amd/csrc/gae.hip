@@ -674,7 +674,7 @@ __global__ __launch_bounds__(NW * 64) void gae_bwd_pf_kernel(const float* __rest
 // ------------------------------------------------------------------------------------------------
 // host side: configuration choice + dispatch
 // ------------------------------------------------------------------------------------------------
-struct Cfg { int v, lc, nw, flags; bool half; bool pf; };
+struct Cfg { int v, lc, nw, flags; bool half; bool pf; bool pf_refused; int plain_flags; };
 
 // Kernel timing (hpc_rll_ktime_begin / _end): while armed, every GAE launch goes through hipExtLaunchKernelGGL with a
 // start/stop event pair that brackets the KERNEL ITSELF (the dispatch packet's begin / end timestamps -- what
@@ -729,6 +729,7 @@ inline int max_vec(int B, std::initializer_list<const void*> ptrs) {
 inline Cfg choose_cfg(bool fwd, int T, int B, int vmax, int v, int lc, int nw, int flags) {
     auto wgs_for = [&](int vv) { return (B + 64 * vv - 1) / (64 * vv); };
     const bool all_auto = v == 0 && lc == 0 && nw == 0;
+    const bool all_explicit = v != 0 && lc != 0 && nw != 0;
     const bool streaming = (12.0 * (double)T * (double)B) >= 300e6;
     int av, alc, anw, afl;
     bool apf = false;   // the software-pipelined kernels (round 3)
@@ -808,8 +809,14 @@ inline Cfg choose_cfg(bool fwd, int T, int B, int vmax, int v, int lc, int nw, i
     if (pf && !(nw == 2 || nw == 4 || nw == 8)) pf = false;
     if (pf && fwd && !((lc == 4 || lc == 8 || lc == 16) && !(v == 4 && lc == 16) && !(v == 1 && lc == 4))) pf = false;
     if (pf && !fwd && !((lc == 2 || lc == 4 || lc == 8) && !(v == 1 && lc != 8))) pf = false;
+    const int plain_flags = flags & 3;   // what the plain kernel runs with when a NULL gradient rules the pipelined backward out
     if (pf) flags |= 2;
-    Cfg out{v, lc, nw, flags & 3, half, pf};
+    // an EXPLICIT request for the pipelined kernel (flags bit 3) is an error, not a silent run of the plain kernel, when it
+    // leaves any of vec / lc / nw to the heuristic or names a triple the kernel is not instantiated for (a legal half-wave
+    // request takes precedence, as before)
+    const bool pf_asked = explicit_flags >= 0 && (explicit_flags & 8) != 0;
+    const bool pf_refused = pf_asked && (!all_explicit || (!half && !pf));
+    Cfg out{v, lc, nw, flags & 3, half, pf, pf_refused, plain_flags};
     return out;
 }
 
@@ -942,6 +949,7 @@ extern "C" int hpc_rll_gae_forward_ex(const float* value, const float* reward, f
     if (!aligned(value, 4) || !aligned(reward, 4) || !aligned(adv, 4) || !aligned(coef, 4)) return HPC_RLL_EALIGN;
     if (flags >= 0 && (flags & ~15)) return HPC_RLL_EUNSUPPORTED;   // bits 4, 5: retired in round 5
     const Cfg cfg = choose_cfg(true, T, B, max_vec(B, {value, reward, adv}), vec, lc, nw, flags);
+    if (cfg.pf_refused) return HPC_RLL_EUNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     if (cfg.pf) {
         std::atomic<int>* lc_ = g_kt.last_cfg[0];
@@ -972,9 +980,14 @@ extern "C" int hpc_rll_gae_backward_ex(const float* grad_adv, float* grad_value,
     if (!aligned(grad_adv, 4) || !aligned(grad_value, 4) || !aligned(grad_reward, 4) || !aligned(coef, 4))
         return HPC_RLL_EALIGN;
     if (flags >= 0 && (flags & ~15)) return HPC_RLL_EUNSUPPORTED;   // bits 4, 5: retired in round 5
-    const Cfg cfg = choose_cfg(false, T, B, max_vec(B, {grad_adv, grad_value, grad_reward}), vec, lc, nw, flags);
+    Cfg cfg = choose_cfg(false, T, B, max_vec(B, {grad_adv, grad_value, grad_reward}), vec, lc, nw, flags);
+    if (cfg.pf_refused) return HPC_RLL_EUNSUPPORTED;
+    if (cfg.pf && (!grad_value || !grad_reward)) {   // the pipelined kernel writes both: the plain one runs, with the flags
+        cfg.pf = false;                               // it was asked for, and is reported
+        cfg.flags = cfg.plain_flags;
+    }
     hipStream_t st = (hipStream_t)stream;
-    if (cfg.pf && grad_value && grad_reward) {
+    if (cfg.pf) {
         std::atomic<int>* lc_ = g_kt.last_cfg[1];
         lc_[0] = cfg.v; lc_[1] = cfg.lc; lc_[2] = cfg.nw; lc_[3] = cfg.flags; lc_[4] = 0; lc_[5] = 1;
         if (!dispatch_bwd_pf(cfg, B, st, grad_adv, grad_value, grad_reward, coef, T, B, gamma)) return HPC_RLL_EUNSUPPORTED;

@@ -69,10 +69,15 @@ int hpc_rll_gae_forward_ex(const float* value, const float* reward, float* adv, 
                            int T, int B, float gamma, int vec, int lc, int nw, int flags, void* stream);
 int hpc_rll_gae_backward_ex(const float* grad_adv, float* grad_value, float* grad_reward, const float* coef,
                             int T, int B, float gamma, int vec, int lc, int nw, int flags, void* stream);
-/* Flags bit 2 (value 4): half-wave tiles (32 columns, two time chunks per wave; narrow batches).  Bit 3 (value 8, with explicit
- * vec/lc/nw): the software-pipelined kernel (the next chunk's row loads are issued before the current chunk's barrier /
- * stores); bit-identical results.  Bits 4 and 5 (the one-trajectory-per-wavefront mapping and XCD-contiguous column tiles of
- * rounds 3-4) left the library in round 5 (tests/tools/micro/gae_wpt.hip keeps the former): HPC_RLL_EUNSUPPORTED.
+/* Flags bit 2 (value 4): half-wave tiles (32 columns, two time chunks per wave; narrow batches).  Bit 3 (value 8): the
+ * software-pipelined kernel (the next chunk's row loads are issued before the current chunk's barrier / stores);
+ * bit-identical results.  It needs explicit vec, lc and nw from its instantiated set -- forward (vec,lc) in (1,8) (1,16)
+ * (2,4) (2,8) (2,16) (4,4) (4,8), backward (1,8) (2,2) (2,4) (2,8) (4,2) (4,4) (4,8), nw in {2,4,8} -- and stores
+ * nontemporally whatever bit 1 says; any other request with bit 3 is HPC_RLL_EUNSUPPORTED and launches nothing.  A
+ * backward with a NULL gradient runs the plain kernel of the same triple with bits 0-1 as given, and
+ * hpc_rll_gae_last_config says so.  Bits 4 and 5 (the one-trajectory-per-wavefront mapping and XCD-contiguous column
+ * tiles of rounds 3-4) left the library in round 5 (tests/tools/micro/gae_wpt.hip keeps the former):
+ * HPC_RLL_EUNSUPPORTED.
  *
  * Diagnostics (no reference counterpart; the reference times whole python calls, tests/test_gae.py:31-52).
  * hpc_rll_ktime_begin(capacity) arms per-launch KERNEL timing for the next `capacity` GAE launches of this process

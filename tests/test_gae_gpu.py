@@ -132,6 +132,22 @@ def _ex_call(dev, v, r, ga, gamma, lam, vec, lc, nw, flags=-1):
     return st1, st2, adv.cpu().numpy(), gv.cpu().numpy(), gr.cpu().numpy()
 
 
+def _last_triples():
+    """(vec, lc, nw) of the latest forward and backward launch (hpc_rll_gae_last_config)."""
+    import cabi
+    out = []
+    for direction in (0, 1):
+        c6 = (ctypes.c_int * 6)()
+        assert cabi.lib.hpc_rll_gae_last_config(direction, c6) == 0
+        out.append(tuple(c6[:3]))
+    return out
+
+
+def _vmax_for(B):
+    """Columns per lane B allows (torch allocations are at least 16-byte aligned, so B alone decides)."""
+    return 4 if B % 4 == 0 else 2 if B % 2 == 0 else 1
+
+
 @pytest.mark.parametrize("T,B", [(100, 260), (1024, 64), (37, 1028)])
 def test_every_launch_configuration(dev, cref, T, B):
     """All (vec, lc, nw) kernel instantiations give the oracle's answer (ragged T, several tiles)."""
@@ -152,6 +168,11 @@ def test_every_launch_configuration(dev, cref, T, B):
                     assert rel_err(o_adv, adv) < TOL, (vec, lc, nw, flags)
                     assert rel_err(o_gv, gv) < 2 * TOL, (vec, lc, nw, flags)
                     assert rel_err(o_gr, gr) < 2 * TOL, (vec, lc, nw, flags)
+                    ran_f, ran_b = _last_triples()
+                    if vec > _vmax_for(B):      # clamped to what B allows: correct, but not the triple asked for
+                        assert ran_f == ran_b == (_vmax_for(B), lc, nw), (vec, lc, nw, flags, ran_f, ran_b)
+                        continue
+                    assert ran_f == ran_b == (vec, lc, nw), (vec, lc, nw, flags, ran_f, ran_b)
                     n += 1
     assert n >= 100
 
