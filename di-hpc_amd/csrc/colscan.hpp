@@ -272,33 +272,58 @@ inline unsigned scan_grid(const ScanCfg& c, int B) {
     return (unsigned)((B + tile - 1) / tile);
 }
 
+// Dispatch diagnostic (hpc_rll_scan_last_config; the record lives in scan_ops.hip, as make_fold's tickets do).  An Op names
+// itself with `static constexpr int DIAG_OP` (the op index of the header) and, where it has them, its mask form with
+// DIAG_MT / DIAG_MM / DIAG_NVF and its load kind with DIAG_NTL.  scan_note_launch is called next to every launch with the
+// template arguments OF THAT LAUNCH, scan_note_final where the loss sums are finalised (1 = folded into the launch,
+// 2 = finalize_sums): what is reported is what was launched, not a second evaluation of scan_cfg.
+void scan_note_launch(int op, int v, int lc, int nw, int sub, int ntl, int mask_dtype, int mask_mode, int nvf, long grid);
+void scan_note_final(int op, int how);
+template <class Op, class = void> struct ScanDiagMask { static constexpr int mt = 0, mm = 0, nvf = 0; };
+template <class Op> struct ScanDiagMask<Op, std::void_t<decltype(Op::DIAG_MM)>> {
+    static constexpr int mt = Op::DIAG_MT, mm = Op::DIAG_MM, nvf = Op::DIAG_NVF;
+};
+template <class Op, class = void> struct ScanDiagLoad { static constexpr int ntl = 0; };
+template <class Op> struct ScanDiagLoad<Op, std::void_t<decltype(Op::DIAG_NTL)>> { static constexpr int ntl = Op::DIAG_NTL; };
+template <class Op, int V, int LC, int NW, int SUB>
+inline void scan_note(long grid) {
+    scan_note_launch(Op::DIAG_OP, V, LC, NW, SUB, ScanDiagLoad<Op>::ntl, ScanDiagMask<Op>::mt, ScanDiagMask<Op>::mm,
+                     ScanDiagMask<Op>::nvf, grid);
+}
+
 template <class Op, bool ALLOW_V2 = true, bool ALLOW_LC16 = false>
 inline void launch_colscan(const Op& op, const ScanCfg& c, int T, int B, float* partials, hipStream_t st,
                            const ScanFold& fold = ScanFold{nullptr, nullptr, {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}}) {
     const unsigned grid = scan_grid(c, B);
+    // one launch and its diagnostic record, both from the same template arguments
+#define HPC_RLL_SCAN_LAUNCH(V_, LC_, NW_, SUB_)                                                                       \
+    do {                                                                                                              \
+        hipLaunchKernelGGL((colscan_rev_kernel<Op, V_, LC_, NW_, SUB_>), dim3(grid), dim3(NW_ * 64), 0, st, op, T, B, \
+                           partials, fold);                                                                           \
+        scan_note<Op, V_, LC_, NW_, SUB_>((long)grid);                                                                \
+    } while (0)
     if constexpr (ALLOW_LC16) {
         if (c.lc == 16 && c.v == 1 && c.nw == 16 && c.sub == 1) {
-            hipLaunchKernelGGL((colscan_rev_kernel<Op, 1, 16, 16>), dim3(grid), dim3(1024), 0, st, op, T, B, partials, fold);
+            HPC_RLL_SCAN_LAUNCH(1, 16, 16, 1);
             return;
         }
     }
     if (c.sub == 2 && c.v == 1 && c.nw == 16) {
-        hipLaunchKernelGGL((colscan_rev_kernel<Op, 1, 8, 16, 2>), dim3(grid), dim3(1024), 0, st, op, T, B, partials, fold);
+        HPC_RLL_SCAN_LAUNCH(1, 8, 16, 2);
         return;
     }
     if (c.sub == 4 && c.v == 1 && c.nw == 16) {
-        hipLaunchKernelGGL((colscan_rev_kernel<Op, 1, 8, 16, 4>), dim3(grid), dim3(1024), 0, st, op, T, B, partials, fold);
+        HPC_RLL_SCAN_LAUNCH(1, 8, 16, 4);
         return;
     }
     if (c.sub == 8 && c.v == 1 && c.nw == 16) {   // 8-column tiles: 128 virtual waves = 1024 steps per barrier
-        hipLaunchKernelGGL((colscan_rev_kernel<Op, 1, 8, 16, 8>), dim3(grid), dim3(1024), 0, st, op, T, B, partials, fold);
+        HPC_RLL_SCAN_LAUNCH(1, 8, 16, 8);
         return;
     }
-#define HPC_RLL_SCAN_CASE(V_, NW_)                                                                          \
-    if (c.v == V_ && c.nw == NW_) {                                                                         \
-        hipLaunchKernelGGL((colscan_rev_kernel<Op, V_, 8, NW_>), dim3(grid), dim3(NW_ * 64), 0, st, op, T, B, \
-                           partials, fold);                                                                 \
-        return;                                                                                             \
+#define HPC_RLL_SCAN_CASE(V_, NW_)            \
+    if (c.v == V_ && c.nw == NW_) {           \
+        HPC_RLL_SCAN_LAUNCH(V_, 8, NW_, 1);   \
+        return;                               \
     }
     HPC_RLL_SCAN_CASE(1, 1) HPC_RLL_SCAN_CASE(1, 2) HPC_RLL_SCAN_CASE(1, 4) HPC_RLL_SCAN_CASE(1, 8)
     HPC_RLL_SCAN_CASE(1, 16)
@@ -306,6 +331,7 @@ inline void launch_colscan(const Op& op, const ScanCfg& c, int T, int B, float* 
         HPC_RLL_SCAN_CASE(2, 1) HPC_RLL_SCAN_CASE(2, 2) HPC_RLL_SCAN_CASE(2, 4) HPC_RLL_SCAN_CASE(2, 8)
     }
 #undef HPC_RLL_SCAN_CASE
+#undef HPC_RLL_SCAN_LAUNCH
 }
 
 inline int scan_num_blocks(int T, int B, bool can_v2) { return (int)scan_grid(scan_cfg(T, B, can_v2), B); }
@@ -324,6 +350,7 @@ inline int scan_and_finalize(const Op& op, const ScanCfg& c, int T, int B, float
     launch_colscan<Op, ALLOW_V2, ALLOW_LC16>(op, c, T, B, partials, st, fold);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
+    scan_note_final(Op::DIAG_OP, fold.out ? 1 : 2);
     if (fold.out) return 0;
     return finalize_sums(partials, (int)scan_grid(c, B), nacc, scale, out, st);
 }

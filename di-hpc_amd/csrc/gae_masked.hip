@@ -40,7 +40,8 @@ namespace {
 // NACC = 0: `finish` receives the kernel's one-element placeholder for the sums.
 template <int MT, int MM, bool NVF, bool NTL>
 struct MaskedGaeFwdOp {
-    static constexpr int NACC = 0;
+    static constexpr int NACC = 0, DIAG_OP = HPC_RLL_SCAN_OP_GAE_MASKED_FWD, DIAG_MT = MT, DIAG_MM = MM, DIAG_NVF = NVF,
+                         DIAG_NTL = NTL;
     static constexpr bool HD = has_done(MM), HF = has_flag(MM);
     const float* value; const float* next_value; const float* reward; const void* done; const void* flag;
     float* adv; int T, B; float gamma, gl;   // gl = gamma*lambda
@@ -259,8 +260,10 @@ inline void with_cfg(int idx, F&& f) {
 template <int V, int LC, int NW, bool HALF, class Op>
 inline void launch(const Op& op, int T, int B, hipStream_t st) {
     constexpr int TILE = HALF ? 32 : 64 * V;
-    hipLaunchKernelGGL((colscan_rev_kernel<Op, V, LC, NW, HALF ? 2 : 1>), dim3((unsigned)((B + TILE - 1) / TILE)),
-                       dim3(NW * 64), 0, st, op, T, B, (float*)nullptr, ScanFold{});
+    const unsigned grid = (unsigned)((B + TILE - 1) / TILE);
+    hipLaunchKernelGGL((colscan_rev_kernel<Op, V, LC, NW, HALF ? 2 : 1>), dim3(grid), dim3(NW * 64), 0, st, op, T, B,
+                       (float*)nullptr, ScanFold{});
+    scan_note<Op, V, LC, NW, HALF ? 2 : 1>((long)grid);   // hpc_rll_scan_last_config: the instantiation just launched
 }
 
 inline int check_launch() {
@@ -323,11 +326,13 @@ extern "C" int hpc_rll_gae_masked_backward(const float* grad_adv, const void* do
         constexpr int V = decltype(V_)::value, LC = decltype(LC_)::value, NW = decltype(NW_)::value;
         constexpr bool HALF = decltype(H_)::value != 0, NTL = decltype(N_)::value != 0;
         constexpr int TILE = HALF ? 32 : 64 * V;
+        const unsigned grid = (unsigned)((B + TILE - 1) / TILE);
         with_mode(mask_dtype, mask_mode(done, traj_flag), !stacked, [&](auto MT_, auto MM_, auto NV_) {
-            hipLaunchKernelGGL((gae_masked_bwd_kernel<V, LC, NW, HALF, NTL, decltype(MT_)::value, decltype(MM_)::value,
-                                                      decltype(NV_)::value != 0>),
-                               dim3((unsigned)((B + TILE - 1) / TILE)), dim3(NW * 64), 0, st, grad_adv, done, traj_flag,
-                               grad_value, grad_next_value, grad_reward, T, B, gamma, gl);
+            constexpr int MT = decltype(MT_)::value, MM = decltype(MM_)::value;
+            constexpr bool NVF = decltype(NV_)::value != 0;
+            hipLaunchKernelGGL((gae_masked_bwd_kernel<V, LC, NW, HALF, NTL, MT, MM, NVF>), dim3(grid), dim3(NW * 64), 0, st,
+                               grad_adv, done, traj_flag, grad_value, grad_next_value, grad_reward, T, B, gamma, gl);
+            scan_note_launch(HPC_RLL_SCAN_OP_GAE_MASKED_BWD, V, LC, NW, HALF ? 2 : 1, NTL, MT, MM, NVF, (long)grid);
         });
     });
     return check_launch();

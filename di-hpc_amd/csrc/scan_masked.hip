@@ -44,7 +44,7 @@ inline __device__ size_t row_off(int t, long col, bool ok, int B, int V) {
 // ================================================================================================
 template <int MT, int MM, bool NVF>
 struct MaskedTdLambdaOp {
-    static constexpr int NACC = 1;
+    static constexpr int NACC = 1, DIAG_OP = HPC_RLL_SCAN_OP_TD_LAMBDA_MASKED, DIAG_MT = MT, DIAG_MM = MM, DIAG_NVF = NVF;
     static constexpr bool HD = has_done(MM), HF = has_flag(MM), ANY = HD || HF;
     const float* value; const float* next_value; const float* reward; const float* weight; int weight_mode;
     const void* done; const void* flag; float* grad_buf; int T, B; float gamma, disc, rest, scale;
@@ -110,7 +110,7 @@ struct MaskedTdLambdaOp {
 // ================================================================================================
 template <int MT, int MM, bool NVF>
 struct MaskedVtraceOp {
-    static constexpr int NACC = 3;
+    static constexpr int NACC = 3, DIAG_OP = HPC_RLL_SCAN_OP_VTRACE_MASKED, DIAG_MT = MT, DIAG_MM = MM, DIAG_NVF = NVF;
     static constexpr bool HD = has_done(MM), HF = has_flag(MM), ANY = HD || HF;
     const float* value; const float* next_value; const float* reward; const float* weight; const float* logp_t;
     const float* logp_b; const float* ent; const void* done; const void* flag; float* coef_pg; float* coef_ent;

@@ -93,7 +93,7 @@ template <int V> __device__ __forceinline__ Pack<V> ldz(const float* p, bool ok)
 //              loss = 0.5 * scale * sum w (ret - V_t)^2 ;  dloss/dV_t = w (V_t - ret_t) * scale   (t < T)
 // ================================================================================================
 struct TdLambdaOp {
-    static constexpr int NACC = 1;
+    static constexpr int NACC = 1, DIAG_OP = HPC_RLL_SCAN_OP_TD_LAMBDA;
     const float* value; const float* reward; const float* weight; int weight_mode;  // 0 none, 1 (B,), 2 (T,B)
     float* grad_buf; int T, B; float disc, rest, scale;                            // disc = gamma*lambda
     template <int V> struct Row { Pack<V> v0, v1, r, w; };
@@ -141,7 +141,7 @@ struct TdLambdaOp {
 // saved for backward: coef_pg = -w adv scale, coef_ent = w scale, gv_unit = 2 w (V_t - vs_t) scale
 // ================================================================================================
 struct VtraceOp {
-    static constexpr int NACC = 3;
+    static constexpr int NACC = 3, DIAG_OP = HPC_RLL_SCAN_OP_VTRACE;
     const float* value; const float* reward; const float* weight; const float* logp_t; const float* logp_b;
     const float* ent; float* coef_pg; float* coef_ent; float* gv_unit; int T, B;
     float gamma, disc, rho_clip, c_clip, pg_clip, scale;
@@ -203,7 +203,7 @@ struct VtraceOp {
 //   loss = -scale sum rho (ret - V_t) logp ;  saved coef = -rho (ret - V_t) scale
 // ================================================================================================
 struct UpgoOp {
-    static constexpr int NACC = 1;
+    static constexpr int NACC = 1, DIAG_OP = HPC_RLL_SCAN_OP_UPGO;
     const float* value; const float* reward; const float* rho; const float* logp; float* coef; int T, B; float scale;
     template <int V> struct Row { Pack<V> v0, v1, r, rho, lp; float lam[V]; };
 
@@ -270,9 +270,33 @@ ScanFold make_fold(hipStream_t st, int nacc, const float* scale, float* out, lon
     return fold;
 }
 
+// The scan family's dispatch record (colscan.hpp: scan_note_launch / scan_note_final write it, hpc_rll_scan_last_config
+// reads it).  Plain ints of the host process, like the GAE record of gae.hip: not synchronised.
+namespace {
+int g_scan_last[HPC_RLL_SCAN_OPS][HPC_RLL_SCAN_CONFIG_INTS];   // [op][0] = launches so far; zero at load
+}
+void scan_note_launch(int op, int v, int lc, int nw, int sub, int ntl, int mask_dtype, int mask_mode, int nvf, long grid) {
+    if (op < 0 || op >= HPC_RLL_SCAN_OPS) return;
+    int* r = g_scan_last[op];
+    const int vals[HPC_RLL_SCAN_CONFIG_INTS] = {r[0] + 1, v, lc, nw, sub, ntl, mask_dtype, mask_mode, nvf, (int)grid, 0};
+    for (int i = 0; i < HPC_RLL_SCAN_CONFIG_INTS; ++i) r[i] = vals[i];
+}
+void scan_note_final(int op, int how) {
+    if (op < 0 || op >= HPC_RLL_SCAN_OPS) return;
+    g_scan_last[op][HPC_RLL_SCAN_CONFIG_INTS - 1] = how;
+}
+
 }  // namespace hpc_rll
 
 using namespace hpc_rll;
+
+extern "C" int hpc_rll_scan_last_config(int op, int* out) {
+    if (op < 0 || op >= HPC_RLL_SCAN_OPS || !out) return HPC_RLL_EINVAL;
+    const int* r = g_scan_last[op];
+    out[0] = r[0];
+    for (int i = 1; i < HPC_RLL_SCAN_CONFIG_INTS; ++i) out[i] = r[0] ? r[i] : -1;   // no launch yet: count 0, the rest -1
+    return HPC_RLL_OK;
+}
 
 // ------------------------------------------------------------------------------------------------ TD(lambda)
 extern "C" int hpc_rll_td_lambda_forward(const float* value, const float* reward, const float* weight,

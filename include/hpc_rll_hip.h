@@ -123,6 +123,33 @@ int hpc_rll_gae_masked_backward(const float* grad_adv, const void* done, const v
 int64_t hpc_rll_partials_floats(int64_t n);
 int hpc_rll_scale_rows(const float* g, const float* in, float* out, int64_t n_in, int64_t n_out, void* stream);
 
+/* Diagnostic of the column-scan family (no reference counterpart; read-only, modelled on hpc_rll_gae_last_config):
+ * which kernel the most recent launch of this process ran for `op`, recorded on the host where the template is chosen,
+ * so it names the instantiation that was launched rather than re-evaluating the selection rule.
+ * out[HPC_RLL_SCAN_CONFIG_INTS] = {
+ *    [0] launches of this op so far (0 = no launch yet: every other entry is then -1),
+ *    [1] columns per lane, [2] steps per wave chunk, [3] waves per workgroup,
+ *    [4] sub-wave groups per wave (1, 2, 4 or 8; the half-wave tiles of the episode-aware GAE are 2),
+ *    [5] nontemporal loads (0 / 1),
+ *    [6] mask element type of the instantiation (HPC_RLL_MASK_U8 / HPC_RLL_MASK_F32; U8 when there is no mask),
+ *    [7] mask mode: 0 no masks, 1 done only (traj_flag = done), 2 done and traj_flag, 3 traj_flag only,
+ *    [8] 1 = next-value form, 0 = stacked form,
+ *    [9] workgroups of the launch,
+ *    [10] how the loss sums were finalised: 0 the op has none, 1 folded into the launch (grids up to 512 workgroups),
+ *         2 by the separate finalize launch }.
+ * Calls that return before launching (empty shapes, argument errors) leave the record as it was.  Plain ints of the
+ * host process, not synchronised.  HPC_RLL_EINVAL for an op outside the list or out == NULL. */
+#define HPC_RLL_SCAN_OP_TD_LAMBDA (0)         /* hpc_rll_td_lambda_forward */
+#define HPC_RLL_SCAN_OP_VTRACE (1)            /* hpc_rll_vtrace_forward */
+#define HPC_RLL_SCAN_OP_UPGO (2)              /* hpc_rll_upgo_forward */
+#define HPC_RLL_SCAN_OP_TD_LAMBDA_MASKED (3)  /* hpc_rll_td_lambda_masked_forward */
+#define HPC_RLL_SCAN_OP_VTRACE_MASKED (4)     /* hpc_rll_vtrace_masked_forward */
+#define HPC_RLL_SCAN_OP_GAE_MASKED_FWD (5)    /* hpc_rll_gae_masked_forward */
+#define HPC_RLL_SCAN_OP_GAE_MASKED_BWD (6)    /* hpc_rll_gae_masked_backward */
+#define HPC_RLL_SCAN_OPS (7)
+#define HPC_RLL_SCAN_CONFIG_INTS (11)
+int hpc_rll_scan_last_config(int op, int* out);
+
 /* Categorical head over `rows` rows of N logits (rows = T*B or B), action int64 per row.
  * Replaces categoricalTarget/categoricalBehaviour (vtrace_kernel.h:11-151), crossEntropyKernel
  * (upgo_kernel.h:40-81), categoricalProbEntropy/categoricalProb (ppo_kernel.h:12-150) and the

@@ -81,6 +81,41 @@ def test_argument_errors_are_status_codes_not_crashes():
     assert L.hpc_rll_vtrace_workspace_floats(10, 20) >= 6 * 200
 
 
+def test_scan_last_config_argument_errors_and_no_launch_yet():
+    """hpc_rll_scan_last_config: a bad op or a NULL output is a status code and writes nothing; before the first launch of
+    an op (a fresh process: nothing here can launch) the record is {0 launches, -1 everywhere else}; a call that returns
+    before launching (empty shape, argument error) leaves it so."""
+    import subprocess
+    import sys
+    hdr = open(HEADER).read()
+    n_ops = int(re.search(r"#define HPC_RLL_SCAN_OPS \((\d+)\)", hdr).group(1))
+    n_int = int(re.search(r"#define HPC_RLL_SCAN_CONFIG_INTS \((\d+)\)", hdr).group(1))
+    assert (n_ops, n_int) == (7, 11)
+    assert sorted(int(x) for x in re.findall(r"#define HPC_RLL_SCAN_OP_\w+ \((\d+)\)", hdr)) == list(range(n_ops))
+    code = f"""
+import ctypes, sys
+sys.path.insert(0, {os.path.join(ROOT, "tests")!r})
+import cabi
+L = cabi.lib
+out = (ctypes.c_int * {n_int})(*([77] * {n_int}))
+for op in (-1, {n_ops}, 1 << 20):
+    assert L.hpc_rll_scan_last_config(op, out) == -1, op
+assert L.hpc_rll_scan_last_config(0, None) == -1
+assert list(out) == [77] * {n_int}, "a refused call wrote to its output"
+assert L.hpc_rll_gae_masked_forward(None, None, None, None, None, 0, None, 0, 4, 0.99, 0.97, None) == 0      # T = 0
+assert L.hpc_rll_gae_masked_backward(None, None, None, 0, None, None, None, 1, 4, 0, 0.99, 0.97, None) == 0  # B = 0
+assert L.hpc_rll_td_lambda_masked_forward(None, None, None, None, 3, None, None, 0, None, None, None, 4, 4, 0.9, 0.8, 1.0,
+                                          None) == -1
+assert L.hpc_rll_td_lambda_forward(None, None, None, 0, None, None, None, 4, 4, 0.9, 0.8, 1.0, None) == -1
+for op in range({n_ops}):
+    assert L.hpc_rll_scan_last_config(op, out) == 0, op
+    assert list(out) == [0] + [-1] * {n_int - 1}, (op, list(out))
+print("scan diag ok")
+"""
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "scan diag ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
+
+
 def test_tuning_knobs_documented_and_guarded():
     """hpc_rll_tune_set is host-only code with ONE table (csrc/tune.hip, round 5): at most 20 live keys (VERDICT r04 item 7 --
     there were 40), each documented in the header, accepting its shipped default and rejecting an out-of-range value with a

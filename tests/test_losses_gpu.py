@@ -54,7 +54,8 @@ def test_td_lambda_golden(golden):
         assert grad_err(g[f"c{i}_grad_value"], v.grad.cpu().numpy()) < GTOL
 
 
-# (1024,64), (2000,17), (513,300), (300,1000): sub-wave tiles of colscan.hpp (4 / 4 / 2 / 2 time chunks per wave)
+# (1024,64), (2000,17), (513,300), (300,1000): sub-wave tiles of colscan.hpp (8 / 8 / 4 / 2 time chunks per wave, by scan_cfg:
+# one workgroup of 64 columns and >= 128 eight-step chunks gives 8-column tiles; tests/test_scan_dispatch_gpu.py pins each one)
 @pytest.mark.parametrize("T,B,wmode", [(1024, 64, 2), (256, 16384, 2), (37, 4100, 1), (5, 70000, 0), (1, 1, 2), (100, 3, 1),
                                        (2000, 17, 1), (513, 300, 0), (300, 1000, 2),
                                        (1100, 96, 2), (2048, 8, 1), (1024, 100, 0)])   # 8 time chunks per wave (8-column tiles)
