@@ -1,0 +1,334 @@
+// gaussian.hip -- PPO for diagonal-Gaussian policy heads (continuous actions) on gfx950: one forward and one backward launch.
+//
+// No reference counterpart: the reference's only PPO op takes a categorical head (ppo_kernel.h); DI-engine's
+// ppo_error_continuous is the semantics.  With z_j = (a_j - mu_j) / sigma_j,
+//   logp = sum_j [-z_j^2/2 - log sigma_j - log(2 pi)/2],   H = sum_j [1/2 + log(2 pi)/2 + log sigma_j]   (new policy)
+// and from ratio = exp(logp_new - logp_old) onward the arithmetic is PpoOp::apply (ppo_op.hpp), shared with the categorical op.
+//
+// Mapping (categorical.hip is the model): a row of A values is owned by a GROUP of G lanes (G = 1..64, a power of two), lane gl
+// holds E pieces of VEC consecutive floats, piece e at column (e*G + gl)*VEC, of each of the five (B,A) inputs; R rows per group
+// and iteration give R independent load + reduction chains.  A Gaussian row needs no maximum, so one pass forms the two sums.
+//   * logp_new - logp_old is accumulated as a sum of PER-DIMENSION differences
+//         (z_old - z_new)(z_old + z_new)/2 + (log sigma_old - log sigma_new):
+//     log(2 pi) cancels and no two sums of size ~A are subtracted (torch's fp32 formula loses 7e-5 of max|grad_mu| at A = 376 to
+//     that cancellation).  PpoOp::apply is called with that difference as logp_new and 0 as logp_old;
+//   * sums over the group are the DPP butterflies of wave.hpp (no LDS, no barrier), the total is in the group's LAST lane, which
+//     applies the per-sample arithmetic and keeps the five running sums; workgroup sums -> partials -> the last workgroup folds
+//     them (colscan.hpp), exactly as ppo_fwd_fused_kernel does;
+//   * every load is unconditional: padding lanes re-read column 0, idle groups re-read the last row;
+//   * forward saves 3 floats per sample (coef_logp, coef_ent, gv_unit); backward RECOMPUTES z from mu_new, sigma_new, action:
+//         grad_mu_j    = k1 z_j / sigma_j,   grad_sigma_j = (k1 (z_j^2 - 1) + k2) / sigma_j,
+//         k1 = g_policy coef_logp,  k2 = g_ent coef_ent,   grad_value = g_value gv_unit (the group's last lane, same launch).
+// No float atomics: results are bit-identical from run to run.
+//
+// Algorithmic HBM bytes per sample: forward 20 A + 16 (+4 weight, +4 value_old) read, 12 written;
+//                                   backward 12 A + 12 read, 8 A + 4 written.
+#include <hip/hip_runtime.h>
+
+#include "hpc_rll_hip.h"
+#include "wave.hpp"
+#include "colscan.hpp"
+#include "ppo_op.hpp"
+
+namespace hpc_rll {
+namespace {
+
+constexpr int kGaussMaxA = 1024;                        // 64 lanes x 16 floats per lane and input
+constexpr float kLn2 = 0.69314718055994530942f;
+constexpr float kEntConst = 1.41893853320467274178f;    // 1/2 + log(2 pi)/2: entropy of a unit normal
+
+// sum over an aligned group of G lanes, valid in the group's LAST lane (G <= 16: in every lane)
+template <int G> __device__ __forceinline__ float gsum_last(float x) {
+    if (G >= 2) x = dpp_add<0xB1, 0xF>(x);     // quad_perm [1,0,3,2]
+    if (G >= 4) x = dpp_add<0x4E, 0xF>(x);     // quad_perm [2,3,0,1]
+    if (G >= 8) x = dpp_add<0x141, 0xF>(x);    // row_half_mirror
+    if (G >= 16) x = dpp_add<0x140, 0xF>(x);   // row_mirror
+    if (G >= 32) x = dpp_add<0x142, 0xA>(x);   // row_bcast:15 -> rows 1 and 3
+    if (G >= 64) x = dpp_add<0x143, 0xC>(x);   // row_bcast:31 -> row 3
+    return x;
+}
+
+// log sigma as log2: sigma > 0 is the caller's contract, the bare v_log_f32 is within 1 ulp
+__device__ __forceinline__ float log2_(float s) { return __builtin_amdgcn_logf(s); }
+
+// one lane's slice of one row of one (B,A) input; load() only issues the (nontemporal: read once per kernel) loads
+template <int G, int VEC, int E>
+struct GaussSlice {
+    float x[E * VEC];
+    __device__ __forceinline__ void load(const float* __restrict__ row, int A, int gl) {
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const int c = (e * G + gl) * VEC;
+            const int cc = (c < A) ? c : 0;
+            if (VEC == 4) {
+                const vfloat4 t = __builtin_nontemporal_load(reinterpret_cast<const vfloat4*>(row + cc));
+                x[e * 4 + 0] = t.x; x[e * 4 + 1] = t.y; x[e * 4 + 2] = t.z; x[e * 4 + 3] = t.w;
+            } else {
+                x[e] = __builtin_nontemporal_load(row + cc);
+            }
+        }
+    }
+};
+
+// rows per group and iteration: 5 (forward) or 3 (backward) inputs x R rows x E*VEC floats per lane stay within ~80 VGPRs
+template <int VEC, int E> struct GaussRows { static constexpr int value = (E * VEC <= 4) ? 4 : ((E * VEC <= 8) ? 2 : 1); };
+
+template <int G, int VEC, int E>
+__global__ __launch_bounds__(256) void ppo_gauss_fwd_kernel(const float* __restrict__ mu_new,
+                                                            const float* __restrict__ sigma_new,
+                                                            const float* __restrict__ mu_old,
+                                                            const float* __restrict__ sigma_old,
+                                                            const float* __restrict__ action, const PpoOp op, long rows,
+                                                            int A, float* __restrict__ partials, const ScanFold fold) {
+    constexpr int GPB = 256 / G;
+    constexpr int R = GaussRows<VEC, E>::value;
+    __shared__ float red[PpoOp::NACC * 4];
+    const int gl = threadIdx.x % G;
+    const int gi = threadIdx.x / G;
+    const bool full = A == G * VEC * E;   // uniform: no padding lanes
+    const float hconst = (float)A * kEntConst;
+    const long stride = (long)gridDim.x * GPB * R;
+    float acc[PpoOp::NACC];
+#pragma unroll
+    for (int k = 0; k < PpoOp::NACC; ++k) acc[k] = 0.f;
+    for (long bb = (long)blockIdx.x * GPB * R; bb < rows; bb += stride) {
+        GaussSlice<G, VEC, E> mn[R], sn[R], mo[R], so[R], ac[R];
+        PpoOp::In in[R];
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            long row = bb + (long)k * GPB + gi;
+            if (row >= rows) row = rows - 1;             // (re-reads the last row; the sample op below is guarded)
+            const long off = row * (long)A;
+            mn[k].load(mu_new + off, A, gl);
+            sn[k].load(sigma_new + off, A, gl);
+            mo[k].load(mu_old + off, A, gl);
+            so[k].load(sigma_old + off, A, gl);
+            ac[k].load(action + off, A, gl);
+            in[k] = op.load(row);                        // (every lane: the same address per group, one request)
+        }
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            float d = 0.f, h = 0.f;   // this lane's part of logp_new - logp_old and of sum log2 sigma_new
+#pragma unroll
+            for (int e = 0; e < E; ++e)
+#pragma unroll
+                for (int q = 0; q < VEC; ++q) {
+                    const int i = e * VEC + q;
+                    const bool ok = full || (e * G + gl) * VEC + q < A;
+                    const float a = ac[k].x[i];
+                    const float zn = (a - mn[k].x[i]) * __builtin_amdgcn_rcpf(sn[k].x[i]);
+                    const float zo = (a - mo[k].x[i]) * __builtin_amdgcn_rcpf(so[k].x[i]);
+                    const float ln = log2_(sn[k].x[i]), lo = log2_(so[k].x[i]);
+                    const float t = fmaf(0.5f * (zo - zn), zo + zn, (lo - ln) * kLn2);
+                    d += ok ? t : 0.f;
+                    h += ok ? ln : 0.f;
+                }
+            d = gsum_last<G>(d);
+            h = gsum_last<G>(h);
+            const long row = bb + (long)k * GPB + gi;
+            if (gl == G - 1 && row < rows) op.apply(row, in[k], d, fmaf(h, kLn2, hconst), 0.f, acc);
+        }
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < PpoOp::NACC; ++k) {
+        const float s = wave_sum(acc[k]);
+        if (lane == 0) red[k * 4 + w] = s;
+    }
+    __syncthreads();
+    float sum = 0.f;
+    if (threadIdx.x < PpoOp::NACC)
+        sum = (red[threadIdx.x * 4] + red[threadIdx.x * 4 + 1]) + (red[threadIdx.x * 4 + 2] + red[threadIdx.x * 4 + 3]);
+    publish_sums<PpoOp::NACC, 256>(sum, partials, fold);
+}
+
+// c1 / c2 / c3 = the forward's coef_logp / coef_ent / gv_unit; g_* device scalars (NULL = 1); any of the three outputs may be NULL
+template <int G, int VEC, int E>
+__global__ __launch_bounds__(256) void ppo_gauss_bwd_kernel(const float* __restrict__ mu_new,
+                                                            const float* __restrict__ sigma_new,
+                                                            const float* __restrict__ action, const float* __restrict__ c1,
+                                                            const float* __restrict__ c2, const float* __restrict__ c3,
+                                                            const float* __restrict__ g_p, const float* __restrict__ g_e,
+                                                            const float* __restrict__ g_v, float* __restrict__ grad_mu,
+                                                            float* __restrict__ grad_sigma, float* __restrict__ grad_value,
+                                                            long rows, int A) {
+    constexpr int GPB = 256 / G;
+    constexpr int R = GaussRows<VEC, E>::value;
+    const int gl = threadIdx.x % G;
+    const int gi = threadIdx.x / G;
+    const float u1 = g_p ? g_p[0] : 1.f;
+    const float u2 = g_e ? g_e[0] : 1.f;
+    const float u3 = (grad_value && g_v) ? g_v[0] : 1.f;
+    const long stride = (long)gridDim.x * GPB * R;
+    for (long bb = (long)blockIdx.x * GPB * R; bb < rows; bb += stride) {
+        GaussSlice<G, VEC, E> mn[R], sn[R], ac[R];
+        float k1[R], k2[R], k3[R];
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            long row = bb + (long)k * GPB + gi;
+            if (row >= rows) row = rows - 1;             // (re-reads the last row; the stores below are guarded)
+            const long off = row * (long)A;
+            mn[k].load(mu_new + off, A, gl);
+            sn[k].load(sigma_new + off, A, gl);
+            ac[k].load(action + off, A, gl);
+            k1[k] = u1 * c1[row];
+            k2[k] = u2 * c2[row];
+            k3[k] = grad_value ? u3 * c3[row] : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            const long row = bb + (long)k * GPB + gi;
+            if (row >= rows) continue;
+            const long off = row * (long)A;
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                const int c0 = (e * G + gl) * VEC;
+                float om[VEC], os[VEC];
+#pragma unroll
+                for (int q = 0; q < VEC; ++q) {
+                    const int i = e * VEC + q;
+                    const float inv = __builtin_amdgcn_rcpf(sn[k].x[i]);
+                    const float z = (ac[k].x[i] - mn[k].x[i]) * inv;
+                    om[q] = k1[k] * z * inv;
+                    os[q] = fmaf(k1[k], fmaf(z, z, -1.f), k2[k]) * inv;
+                }
+                if (c0 < A) {
+                    if (VEC == 4) {
+                        vfloat4 t;
+                        if (grad_mu) {
+                            t.x = om[0]; t.y = om[1]; t.z = om[2]; t.w = om[3];
+                            __builtin_nontemporal_store(t, reinterpret_cast<vfloat4*>(grad_mu + off + c0));
+                        }
+                        if (grad_sigma) {
+                            t.x = os[0]; t.y = os[1]; t.z = os[2]; t.w = os[3];
+                            __builtin_nontemporal_store(t, reinterpret_cast<vfloat4*>(grad_sigma + off + c0));
+                        }
+                    } else {
+                        if (grad_mu) __builtin_nontemporal_store(om[0], grad_mu + off + c0);
+                        if (grad_sigma) __builtin_nontemporal_store(os[0], grad_sigma + off + c0);
+                    }
+                }
+            }
+            if (grad_value && gl == G - 1) grad_value[row] = k3[k];
+        }
+    }
+}
+
+struct GaussCfg { int g, vec, e; };
+
+// The group is one DPP row (16 lanes) or less while 4 pieces per lane suffice (A <= 256 with 16-byte loads, A <= 64 without);
+// longer rows take the whole wave with up to 4 (16-byte) or 16 (4-byte) pieces per lane: A <= 1024 either way.
+inline GaussCfg gauss_cfg(int A, bool can_vec4) {
+    GaussCfg c;
+    c.vec = (can_vec4 && (A % 4) == 0) ? 4 : 1;
+    const int pieces = (A + c.vec - 1) / c.vec;
+    const int gmax = pieces <= 16 * 4 ? 16 : 64;
+    c.g = 1;
+    while (c.g < gmax && c.g < pieces) c.g <<= 1;
+    const int e = (pieces + c.g - 1) / c.g;
+    c.e = 1;
+    while (c.e < e) c.e <<= 1;
+    return c;
+}
+
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+inline int last_error() {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? HPC_RLL_OK : (int)e;
+}
+
+// every (G, VEC, E) gauss_cfg can return for 1 <= A <= kGaussMaxA
+#define HPC_RLL_GAUSS_DISPATCH(CASE)                                                                                  \
+    CASE(1, 4, 1) CASE(2, 4, 1) CASE(4, 4, 1) CASE(8, 4, 1) CASE(16, 4, 1) CASE(16, 4, 2) CASE(16, 4, 4)             \
+    CASE(64, 4, 2) CASE(64, 4, 4)                                                                                     \
+    CASE(1, 1, 1) CASE(2, 1, 1) CASE(4, 1, 1) CASE(8, 1, 1) CASE(16, 1, 1) CASE(16, 1, 2) CASE(16, 1, 4)             \
+    CASE(64, 1, 2) CASE(64, 1, 4) CASE(64, 1, 8) CASE(64, 1, 16)
+
+int gauss_forward(const float* mu_new, const float* sigma_new, const float* mu_old, const float* sigma_old,
+                  const float* action, const PpoOp& op, long rows, int A, float* partials, const float* scales, float* out5,
+                  hipStream_t st) {
+    const GaussCfg cfg = gauss_cfg(A, al16(mu_new) && al16(sigma_new) && al16(mu_old) && al16(sigma_old) && al16(action));
+#define HPC_RLL_GAUSS_FWD_CASE(G_, V_, E_)                                                                            \
+    if (cfg.g == G_ && cfg.vec == V_ && cfg.e == E_) {                                                                \
+        const long per = (256 / G_) * GaussRows<V_, E_>::value;                                                       \
+        long grid = (rows + per - 1) / per;                                                                           \
+        if (grid > kFoldMaxGrid) grid = kFoldMaxGrid;   /* the workgroups loop; the sums are folded inside the launch */ \
+        const ScanFold fold = make_fold(st, PpoOp::NACC, scales, out5, grid);                                         \
+        hipLaunchKernelGGL((ppo_gauss_fwd_kernel<G_, V_, E_>), dim3((unsigned)grid), dim3(256), 0, st, mu_new,         \
+                           sigma_new, mu_old, sigma_old, action, op, rows, A, partials, fold);                        \
+        const int rc = last_error();                                                                                  \
+        if (rc || fold.out) return rc;                                                                                \
+        return finalize_sums(partials, (int)grid, PpoOp::NACC, scales, out5, st);                                     \
+    }
+    HPC_RLL_GAUSS_DISPATCH(HPC_RLL_GAUSS_FWD_CASE)
+#undef HPC_RLL_GAUSS_FWD_CASE
+    return HPC_RLL_EUNSUPPORTED;
+}
+
+int gauss_backward(const float* mu_new, const float* sigma_new, const float* action, const float* c1, const float* c2,
+                   const float* c3, const float* g_p, const float* g_e, const float* g_v, float* grad_mu, float* grad_sigma,
+                   float* grad_value, long rows, int A, hipStream_t st) {
+    const GaussCfg cfg = gauss_cfg(A, al16(mu_new) && al16(sigma_new) && al16(action) && al16(grad_mu) && al16(grad_sigma));
+#define HPC_RLL_GAUSS_BWD_CASE(G_, V_, E_)                                                                            \
+    if (cfg.g == G_ && cfg.vec == V_ && cfg.e == E_) {                                                                \
+        const long per = (256 / G_) * GaussRows<V_, E_>::value;                                                       \
+        long grid = (rows + per - 1) / per;                                                                           \
+        if (grid > 256L * 1024) grid = 256L * 1024;     /* short-lived workgroups, as the categorical row kernels */  \
+        hipLaunchKernelGGL((ppo_gauss_bwd_kernel<G_, V_, E_>), dim3((unsigned)grid), dim3(256), 0, st, mu_new,         \
+                           sigma_new, action, c1, c2, c3, g_p, g_e, g_v, grad_mu, grad_sigma, grad_value, rows, A);   \
+        return last_error();                                                                                          \
+    }
+    HPC_RLL_GAUSS_DISPATCH(HPC_RLL_GAUSS_BWD_CASE)
+#undef HPC_RLL_GAUSS_BWD_CASE
+    return HPC_RLL_EUNSUPPORTED;
+}
+
+}  // namespace
+}  // namespace hpc_rll
+
+using namespace hpc_rll;
+
+// ws layout (floats): [coef_logp B | coef_ent B | gv_unit B | partials: 5 sums x at most kFoldMaxGrid workgroups]
+extern "C" int64_t hpc_rll_ppo_continuous_workspace_floats(int B) {
+    if (B < 0) return HPC_RLL_EINVAL;
+    return 3 * (int64_t)B + 8 * (kFoldMaxGrid + 1);
+}
+
+extern "C" int hpc_rll_ppo_continuous_forward(const float* mu_new, const float* sigma_new, const float* mu_old,
+                                              const float* sigma_old, const float* action, const float* value_new,
+                                              const float* value_old, const float* adv, const float* ret,
+                                              const float* weight, float* out5, float* ws, int B, int A, float clip_ratio,
+                                              int use_value_clip, float dual_clip, float scale, void* stream) {
+    if (B < 0 || A <= 0 || !out5) return HPC_RLL_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (B > 0 && (!mu_new || !sigma_new || !mu_old || !sigma_old || !action || !value_new || !value_old || !adv || !ret || !ws))
+        return HPC_RLL_EINVAL;
+    if (A > kGaussMaxA) return HPC_RLL_EUNSUPPORTED;
+    if (B == 0) return (int)hipMemsetAsync(out5, 0, 5 * sizeof(float), st);
+    float *coef_logp = ws, *coef_ent = ws + B, *gv_unit = ws + 2 * (size_t)B, *partials = ws + 3 * (size_t)B;
+    const PpoOp op{nullptr, nullptr, nullptr, value_new, value_old, adv, ret, weight, coef_logp, coef_ent, gv_unit,
+                   clip_ratio, dual_clip, scale, use_value_clip};
+    // approx_kl and clipfrac are plain (unweighted) means over the LOCAL batch: scale by 1/B
+    const float sc[5] = {scale, 0.5f * scale, scale, 1.f / (float)B, 1.f / (float)B};
+    return gauss_forward(mu_new, sigma_new, mu_old, sigma_old, action, op, B, A, partials, sc, out5, st);
+}
+
+extern "C" int hpc_rll_ppo_continuous_backward(const float* g_policy, const float* g_value, const float* g_ent,
+                                               const float* mu_new, const float* sigma_new, const float* action,
+                                               const float* ws, float* grad_mu, float* grad_sigma, float* grad_value, int B,
+                                               int A, void* stream) {
+    if (B < 0 || A <= 0) return HPC_RLL_EINVAL;
+    if (B > 0 && !ws) return HPC_RLL_EINVAL;
+    if (B > 0 && (grad_mu || grad_sigma) && (!mu_new || !sigma_new || !action)) return HPC_RLL_EINVAL;
+    if (A > kGaussMaxA) return HPC_RLL_EUNSUPPORTED;
+    if (B == 0) return HPC_RLL_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (!grad_mu && !grad_sigma) {   // only the value head asks for a gradient: no row work
+        if (!grad_value) return HPC_RLL_OK;
+        if (!g_value) return HPC_RLL_EINVAL;
+        return scale_rows(g_value, ws + 2 * (size_t)B, grad_value, B, B, st);
+    }
+    return gauss_backward(mu_new, sigma_new, action, ws, ws + B, ws + 2 * (size_t)B, g_policy, g_ent, g_value, grad_mu,
+                          grad_sigma, grad_value, B, A, st);
+}

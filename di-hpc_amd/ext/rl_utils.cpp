@@ -3,7 +3,7 @@
 // Two layers in one module:
 //   * the reference's L2 functions `XxxForward(inputs, outputs, scalars...)` / `XxxBackward(inputs, outputs)`
 //     (declared in include/hpc/rll/cuda/rl_utils/entry.h:10-165) -- validated, launched on torch's current stream;
-//   * fused autograd ops (`gae`, `td_lambda`, `vtrace`, `upgo`, `ppo`, `q_nstep_td`, `dist_nstep_td`, `iqn_nstep_td`,
+//   * fused autograd ops (`gae`, `td_lambda`, `vtrace`, `upgo`, `ppo`, `ppo_continuous`, `q_nstep_td`, `dist_nstep_td`, `iqn_nstep_td`,
 //     `qrdqn_nstep_td`) -- torch::autograd::Function nodes that allocate outputs, launch and register backward in ONE
 //     pybind call; these are what hpc_rll.rl_utils.* modules use.
 // Host-only C++: every kernel lives behind the C ABI of libhpc_rll_hip.so (include/hpc_rll_hip.h).
@@ -636,6 +636,73 @@ struct PpoFn : public ag::Function<PpoFn> {
     }
 };
 
+// ============================================================================================ PPO, Gaussian head
+PpoContinuousDims ppo_continuous_check(const Tensor& mu_new, const Tensor& sigma_new, const Tensor& mu_old,
+                                       const Tensor& sigma_old, const Tensor& action, const Tensor& vn, const Tensor& vo,
+                                       const Tensor& adv, const Tensor& ret, const OptTensor& weight) {
+    req(mu_new, "mu_new");
+    TORCH_CHECK(mu_new.dim() == 2, "mu_new: expected (B,A), got ", mu_new.sizes());
+    const int64_t B = mu_new.size(0), A = mu_new.size(1);
+    const at::Device dev = mu_new.device();
+    req(sigma_new, "sigma_new", dev, {B, A});
+    req(mu_old, "mu_old", dev, {B, A});
+    req(sigma_old, "sigma_old", dev, {B, A});
+    req(action, "action", dev, {B, A});
+    req(vn, "value_new", dev, {B});
+    req(vo, "value_old", dev, {B});
+    req(adv, "adv", dev, {B});
+    req(ret, "return_", dev, {B});
+    req_opt(weight, "weight", dev, {B});
+    TORCH_CHECK(A >= 1, "mu_new: the action dimension must be at least 1, got ", mu_new.sizes());
+    return {B, A, dev};
+}
+
+struct PpoContinuousFn : public ag::Function<PpoContinuousFn> {
+    static ag::tensor_list forward(ag::AutogradContext* ctx, const Tensor& mu_new, const Tensor& sigma_new,
+                                   const Tensor& mu_old, const Tensor& sigma_old, const Tensor& action, const Tensor& vn,
+                                   const Tensor& vo, const Tensor& adv, const Tensor& ret, const OptTensor& weight,
+                                   double clip_ratio, bool use_value_clip, double dual_clip, std::optional<double> scale) {
+        const PpoContinuousDims d = ppo_continuous_check(mu_new, sigma_new, mu_old, sigma_old, action, vn, vo, adv, ret, weight);
+        c10::DeviceGuard g(d.dev);
+        const int B = to_int(d.B, "B"), A = to_int(d.A, "A");
+        Tensor out5 = new_f32({5}, d.dev);
+        Tensor ws = new_f32({hpc_rll_ppo_continuous_workspace_floats(B)}, d.dev);
+        const int rc = hpc_rll_ppo_continuous_forward(
+            fptr(mu_new), fptr(sigma_new), fptr(mu_old), fptr(sigma_old), fptr(action), fptr(vn), fptr(vo), fptr(adv), fptr(ret),
+            fptr(weight), fmut(out5), fmut(ws), B, A, (float)clip_ratio, use_value_clip ? 1 : 0, (float)dual_clip,
+            loss_scale(scale, d.B), stream_of(d.dev));
+        TORCH_CHECK(rc != HPC_RLL_EUNSUPPORTED, "ppo_continuous: an action dimension of ", A,
+                    " is not supported by the gfx950 kernels (1 <= A <= 1024)");
+        check(rc, "hpc_rll_ppo_continuous_forward");
+        ctx->save_for_backward({mu_new, sigma_new, action, ws});
+        Tensor info = alias_of(out5, 3, 2);
+        ctx->mark_non_differentiable({info});
+        return {alias_of(out5, 0, 1), alias_of(out5, 1, 1), alias_of(out5, 2, 1), info};
+    }
+    static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
+        ag::tensor_list out(14);
+        const bool need_m = ctx->needs_input_grad(0), need_s = ctx->needs_input_grad(1), need_v = ctx->needs_input_grad(5);
+        if (!(need_m || need_s || need_v)) return out;
+        const auto saved = ctx->get_saved_variables();
+        const Tensor &mu_new = saved[0], &sigma_new = saved[1], &action = saved[2], &ws = saved[3];
+        const at::Device dev = mu_new.device();
+        c10::DeviceGuard g(dev);
+        Tensor g_p = grad1(grads[0], dev, "grad_policy_loss"), g_v = grad1(grads[1], dev, "grad_value_loss"),
+               g_e = grad1(grads[2], dev, "grad_entropy_loss");
+        Tensor grad_mu = need_m ? at::empty_like(mu_new) : undef();
+        Tensor grad_sigma = need_s ? at::empty_like(sigma_new) : undef();
+        Tensor grad_value = need_v ? new_f32({mu_new.size(0)}, dev) : undef();
+        check(hpc_rll_ppo_continuous_backward(fptr(g_p), fptr(g_v), fptr(g_e), fptr(mu_new), fptr(sigma_new), fptr(action),
+                                              fptr(ws), fmut(grad_mu), fmut(grad_sigma), fmut(grad_value),
+                                              (int)mu_new.size(0), (int)mu_new.size(1), stream_of(dev)),
+              "hpc_rll_ppo_continuous_backward");
+        out[0] = grad_mu;
+        out[1] = grad_sigma;
+        out[5] = grad_value;
+        return out;
+    }
+};
+
 // ==================================================================================================== q n-step TD
 struct QDims { int64_t B, N, nstep; at::Device dev; };
 int64_t check_nstep_reward(const Tensor& reward, int64_t B, const at::Device& dev) {
@@ -1154,6 +1221,18 @@ PYBIND11_MODULE(hpc_rl_utils, m) {
     }, py::arg("logits_new"), py::arg("logits_old"), py::arg("action"), py::arg("value_new"), py::arg("value_old"),
           py::arg("adv"), py::arg("return_"), py::arg("weight") = py::none(), py::arg("clip_ratio") = 0.2,
           py::arg("use_value_clip") = true, py::arg("dual_clip") = 0.0, py::arg("scale") = py::none());
+    m.def("ppo_continuous", [](const Tensor& mu_new, const Tensor& sigma_new, const Tensor& mu_old, const Tensor& sigma_old,
+                               const Tensor& action, const Tensor& vn, const Tensor& vo, const Tensor& adv, const Tensor& ret,
+                               const OptTensor& weight, double clip_ratio, bool use_value_clip, double dual_clip,
+                               std::optional<double> scale) {
+        return PpoContinuousFn::apply(mu_new, sigma_new, mu_old, sigma_old, action, vn, vo, adv, ret, weight, clip_ratio,
+                                      use_value_clip, dual_clip, scale);
+    }, py::arg("mu_new"), py::arg("sigma_new"), py::arg("mu_old"), py::arg("sigma_old"), py::arg("action"),
+          py::arg("value_new"), py::arg("value_old"), py::arg("adv"), py::arg("return_"), py::arg("weight") = py::none(),
+          py::arg("clip_ratio") = 0.2, py::arg("use_value_clip") = true, py::arg("dual_clip") = 0.0,
+          py::arg("scale") = py::none(),
+          "PPO losses (policy, value, entropy, info) for a diagonal-Gaussian policy: mu / sigma / action (B,A) fp32, "
+          "sigma > 0; differentiable wrt mu_new, sigma_new and value_new");
     m.def("q_nstep_td", [](const Tensor& q, const Tensor& nq, const Tensor& action, const Tensor& naction,
                            const Tensor& reward, const Tensor& done, const OptTensor& weight, double gamma, bool rescale,
                            std::optional<double> scale) {

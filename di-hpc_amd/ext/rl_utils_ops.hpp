@@ -37,4 +37,10 @@ void ppo_forward_launch(const PpoDims& d, const Tensor& ln, const Tensor& lo, co
 void ppo_backward_launch(const Tensor& g_p, const Tensor& g_v, const Tensor& g_e, const Tensor& ln, const Tensor& action,
                          const Tensor& ws, const Tensor& grad_logits, const Tensor& grad_value);
 
+// PPO with a diagonal-Gaussian head (no reference counterpart, hence no list form)
+struct PpoContinuousDims { int64_t B, A; at::Device dev; };
+PpoContinuousDims ppo_continuous_check(const Tensor& mu_new, const Tensor& sigma_new, const Tensor& mu_old,
+                                       const Tensor& sigma_old, const Tensor& action, const Tensor& vn, const Tensor& vo,
+                                       const Tensor& adv, const Tensor& ret, const OptTensor& weight);
+
 }  // namespace hpc_rll_ext

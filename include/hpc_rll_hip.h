@@ -274,7 +274,27 @@ int hpc_rll_ppo_backward(const float* g_policy, const float* g_value, const floa
                          const int64_t* action, const float* ws, float* grad_logits_new, float* grad_value_new,
                          int B, int N, void* stream);
 
-/* q n-step TD (rescale=0) / with value rescaling (rescale=1) -- replaces QNStepTd{,Rescale}Forward/Backward
+/* PPO for diagonal-Gaussian policies (continuous actions; no reference counterpart, semantics of DI-engine's
+ * ppo_error_continuous).  mu_new, sigma_new, mu_old, sigma_old, action (B,A) fp32; value_new/old, adv, ret, weight (B,)
+ * (weight NULL = ones).  sigma is the standard deviation and must be > 0 (not checked: device values).  With
+ * z = (a - mu)/sigma: logp = sum_j [-z_j^2/2 - log sigma_j - log(2 pi)/2], H = sum_j [1/2 + log(2 pi)/2 + log sigma_new_j],
+ * ratio = exp(logp_new - logp_old); from there on, and out5 / dual_clip / scale, exactly hpc_rll_ppo_forward.
+ * ws: hpc_rll_ppo_continuous_workspace_floats(B) floats (3 per sample + the partial sums; nothing of size B*A is saved).
+ * backward: g_* device scalars (NULL = 1); grad_mu, grad_sigma (B,A) and grad_value (B,) may each be NULL (not wanted):
+ *   grad_mu = k1 z/sigma, grad_sigma = (k1 (z^2 - 1) + k2)/sigma, k1 = g_policy*ws[b], k2 = g_ent*ws[B+b],
+ *   grad_value = g_value*ws[2B+b].  One launch each way; 1 <= A <= 1024, beyond that HPC_RLL_EUNSUPPORTED.
+ * B == 0: out5 = 0, nothing launched.  Null pointers / negative sizes: HPC_RLL_EINVAL before any HIP call. */
+int64_t hpc_rll_ppo_continuous_workspace_floats(int B);
+int hpc_rll_ppo_continuous_forward(const float* mu_new, const float* sigma_new, const float* mu_old,
+                                   const float* sigma_old, const float* action, const float* value_new,
+                                   const float* value_old, const float* adv, const float* ret, const float* weight,
+                                   float* out5, float* ws, int B, int A, float clip_ratio, int use_value_clip,
+                                   float dual_clip, float scale, void* stream);
+int hpc_rll_ppo_continuous_backward(const float* g_policy, const float* g_value, const float* g_ent, const float* mu_new,
+                                    const float* sigma_new, const float* action, const float* ws, float* grad_mu,
+                                    float* grad_sigma, float* grad_value, int B, int A, void* stream);
+
+/* q n-step TD (rescale=0)/ with value rescaling (rescale=1) -- replaces QNStepTd{,Rescale}Forward/Backward
  * (rl_utils/entry.h:89-109).  q,next_n_q (B,N); action,next_n_action (B,) int64; reward (nstep,B); done,
  * weight (B,) float (weight NULL = ones).  loss (1,), td_err (B,), grad_buf (B,). */
 int hpc_rll_q_nstep_td_forward(const float* q, const float* next_n_q, const int64_t* action,
