@@ -23,6 +23,7 @@
 
 #include <type_traits>
 
+#include "hpc_rll_hip.h"
 #include "wave.hpp"
 
 namespace hpc_rll {
@@ -277,6 +278,11 @@ inline unsigned scan_grid(const ScanCfg& c, int B) {
 // DIAG_MT / DIAG_MM / DIAG_NVF and its load kind with DIAG_NTL.  scan_note_launch is called next to every launch with the
 // template arguments OF THAT LAUNCH, scan_note_final where the loss sums are finalised (1 = folded into the launch,
 // 2 = finalize_sums): what is reported is what was launched, not a second evaluation of scan_cfg.
+// The episode-aware UPGO (scan_masked.hip) keeps its record in a slot PAST the header's op list: HPC_RLL_SCAN_OPS and the
+// range hpc_rll_scan_last_config accepts are part of ABI 6 and stay as they are; hpc_rll_upgo_masked_last_config is the
+// only reader of this slot.
+constexpr int kScanOpUpgoMasked = HPC_RLL_SCAN_OPS;
+constexpr int kScanRecords = HPC_RLL_SCAN_OPS + 1;
 void scan_note_launch(int op, int v, int lc, int nw, int sub, int ntl, int mask_dtype, int mask_mode, int nvf, long grid);
 void scan_note_final(int op, int how);
 template <class Op, class = void> struct ScanDiagMask { static constexpr int mt = 0, mm = 0, nvf = 0; };

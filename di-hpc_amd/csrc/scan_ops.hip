@@ -271,18 +271,25 @@ ScanFold make_fold(hipStream_t st, int nacc, const float* scale, float* out, lon
 }
 
 // The scan family's dispatch record (colscan.hpp: scan_note_launch / scan_note_final write it, hpc_rll_scan_last_config
-// reads it).  Plain ints of the host process, like the GAE record of gae.hip: not synchronised.
+// reads it).  Plain ints of the host process, like the GAE record of gae.hip: not synchronised.  The last slot
+// (kScanOpUpgoMasked) is internal: only hpc_rll_upgo_masked_last_config reads it.
 namespace {
-int g_scan_last[HPC_RLL_SCAN_OPS][HPC_RLL_SCAN_CONFIG_INTS];   // [op][0] = launches so far; zero at load
+int g_scan_last[kScanRecords][HPC_RLL_SCAN_CONFIG_INTS];   // [op][0] = launches so far; zero at load
+int read_scan_record(int slot, int* out) {
+    const int* r = g_scan_last[slot];
+    out[0] = r[0];
+    for (int i = 1; i < HPC_RLL_SCAN_CONFIG_INTS; ++i) out[i] = r[0] ? r[i] : -1;   // no launch yet: count 0, the rest -1
+    return HPC_RLL_OK;
+}
 }
 void scan_note_launch(int op, int v, int lc, int nw, int sub, int ntl, int mask_dtype, int mask_mode, int nvf, long grid) {
-    if (op < 0 || op >= HPC_RLL_SCAN_OPS) return;
+    if (op < 0 || op >= kScanRecords) return;
     int* r = g_scan_last[op];
     const int vals[HPC_RLL_SCAN_CONFIG_INTS] = {r[0] + 1, v, lc, nw, sub, ntl, mask_dtype, mask_mode, nvf, (int)grid, 0};
     for (int i = 0; i < HPC_RLL_SCAN_CONFIG_INTS; ++i) r[i] = vals[i];
 }
 void scan_note_final(int op, int how) {
-    if (op < 0 || op >= HPC_RLL_SCAN_OPS) return;
+    if (op < 0 || op >= kScanRecords) return;
     g_scan_last[op][HPC_RLL_SCAN_CONFIG_INTS - 1] = how;
 }
 
@@ -292,10 +299,12 @@ using namespace hpc_rll;
 
 extern "C" int hpc_rll_scan_last_config(int op, int* out) {
     if (op < 0 || op >= HPC_RLL_SCAN_OPS || !out) return HPC_RLL_EINVAL;
-    const int* r = g_scan_last[op];
-    out[0] = r[0];
-    for (int i = 1; i < HPC_RLL_SCAN_CONFIG_INTS; ++i) out[i] = r[0] ? r[i] : -1;   // no launch yet: count 0, the rest -1
-    return HPC_RLL_OK;
+    return read_scan_record(op, out);
+}
+
+extern "C" int hpc_rll_upgo_masked_last_config(int* out) {
+    if (!out) return HPC_RLL_EINVAL;
+    return read_scan_record(kScanOpUpgoMasked, out);
 }
 
 // ------------------------------------------------------------------------------------------------ TD(lambda)

@@ -3,7 +3,7 @@
 // Two layers in one module:
 //   * the reference's L2 functions `XxxForward(inputs, outputs, scalars...)` / `XxxBackward(inputs, outputs)`
 //     (declared in include/hpc/rll/cuda/rl_utils/entry.h:10-165) -- validated, launched on torch's current stream;
-//   * fused autograd ops (`gae`, `td_lambda`, `vtrace`, `upgo`, `ppo`, `ppo_continuous`, `q_nstep_td`, `dist_nstep_td`, `iqn_nstep_td`,
+//   * fused autograd ops (`gae`, `td_lambda`, `vtrace`, `upgo`, `upgo_masked`, `ppo`, `ppo_continuous`, `q_nstep_td`, `dist_nstep_td`, `iqn_nstep_td`,
 //     `qrdqn_nstep_td`) -- torch::autograd::Function nodes that allocate outputs, launch and register backward in ONE
 //     pybind call; these are what hpc_rll.rl_utils.* modules use.
 // Host-only C++: every kernel lives behind the C ABI of libhpc_rll_hip.so (include/hpc_rll_hip.h).
@@ -565,6 +565,50 @@ ag::tensor_list UpgoFn::backward(ag::AutogradContext* ctx, ag::tensor_list grads
     out[0] = grad_target;
     return out;
 }
+
+// UPGO with done masks (hpc_rll_upgo_masked_forward): the masks, the two value forms and the checks of the masked ops
+// above; the workspace and the backward are UpgoFn's.  Shapes and dtypes are checked before the device.
+struct UpgoMaskedFn : public ag::Function<UpgoMaskedFn> {
+    static Tensor forward(ag::AutogradContext* ctx, const Tensor& target, const Tensor& rho, const Tensor& action,
+                          const Tensor& reward, const Tensor& value, const OptTensor& done, const OptTensor& flag,
+                          const OptTensor& next_value, double gamma, std::optional<double> scale) {
+        TORCH_CHECK(target.defined(), "target_output: expected a tensor, got None");
+        TORCH_CHECK(target.dim() == 3, "target_output: expected (T,B,N), got ", target.sizes());
+        const int64_t T = target.size(0), B = target.size(1), N = target.size(2);
+        TORCH_CHECK(target.scalar_type() == at::kFloat, "target_output: dtype ", target.scalar_type(), ", expected ",
+                    at::kFloat);
+        check_shape(rho, "rhos", {T, B});
+        check_shape(action, "action", {T, B}, at::kLong);
+        check_shape(reward, "rewards", {T, B});
+        const Masks m = check_masked_inputs("upgo_masked", value, reward, done, flag, next_value);
+        const at::Device dev = reward.device();
+        req(target, "target_output", dev);
+        req(rho, "rhos", dev);
+        req(action, "action", dev, at::kLong);
+        c10::DeviceGuard g(dev);
+        Tensor loss = new_f32({1}, dev);
+        Tensor ws = upgo_workspace(T, B, dev);
+        check(hpc_rll_upgo_masked_forward(fptr(target), fptr(rho), iptr(action), fptr(reward), fptr(value),
+                                          fptr(next_value), vptr(m.done), vptr(m.flag), m.code, fmut(loss), fmut(ws),
+                                          to_int(T, "T"), to_int(B, "B"), to_int(N, "N"), (float)gamma,
+                                          loss_scale(scale, T * B), stream_of(dev)),
+              "hpc_rll_upgo_masked_forward");
+        ctx->save_for_backward({target, action, ws});
+        return loss;
+    }
+    static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
+        ag::tensor_list out(10);
+        if (!ctx->needs_input_grad(0)) return out;
+        const auto saved = ctx->get_saved_variables();
+        const Tensor& target = saved[0];
+        c10::DeviceGuard g(target.device());
+        Tensor gl = grad1(grads[0], target.device(), "grad_loss");
+        Tensor grad_target = at::empty_like(target);
+        upgo_backward_launch(gl, target, saved[1], saved[2], grad_target);
+        out[0] = grad_target;
+        return out;
+    }
+};
 
 // =========================================================================================================== PPO
 PpoDims ppo_check(const Tensor& ln, const Tensor& lo, const Tensor& action, const Tensor& vn, const Tensor& vo,
@@ -1214,6 +1258,14 @@ PYBIND11_MODULE(hpc_rl_utils, m) {
         return UpgoFn::apply(target, rho, action, reward, value, scale);
     }, py::arg("target_output"), py::arg("rhos"), py::arg("action"), py::arg("rewards"), py::arg("bootstrap_values"),
           py::arg("scale") = py::none());
+    m.def("upgo_masked", [](const Tensor& target, const Tensor& rho, const Tensor& action, const Tensor& reward,
+                            const Tensor& value, const OptTensor& done, const OptTensor& traj_flag,
+                            const OptTensor& next_value, double gamma, std::optional<double> scale) {
+        return UpgoMaskedFn::apply(target, rho, action, reward, value, done, traj_flag, next_value, gamma, scale);
+    }, py::arg("target_output"), py::arg("rhos"), py::arg("action"), py::arg("rewards"), py::arg("bootstrap_values"),
+          py::arg("done") = py::none(), py::arg("traj_flag") = py::none(), py::arg("next_value") = py::none(),
+          py::arg("gamma") = 1.0, py::arg("scale") = py::none(),
+          "episode-aware UPGO loss (1,) with done / traj_flag masks; differentiable wrt target_output");
     m.def("ppo", [](const Tensor& ln, const Tensor& lo, const Tensor& action, const Tensor& vn, const Tensor& vo,
                     const Tensor& adv, const Tensor& ret, const OptTensor& weight, double clip_ratio, bool use_value_clip,
                     double dual_clip, std::optional<double> scale) {

@@ -261,6 +261,29 @@ int hpc_rll_upgo_forward(const float* target_output, const float* rho, const int
 int hpc_rll_upgo_backward(const float* g, const float* target_output, const int64_t* action, const float* ws,
                           float* grad_target_output, int T, int B, int N, void* stream);
 
+/* Episode-aware UPGO with done / truncation masks (no reference counterpart: hpc_rll_upgo_forward carries the return and
+ * the comparison r_{t+1} + V_{t+2} >= V_{t+1} across an episode end and has no discount).  Masks, mask_dtype and the two
+ * value forms as hpc_rll_td_lambda_masked_forward: k^d_t = 1 - done_t, k^f_t = 1 - f_t (f = traj_flag, defaulting to
+ * done), nv_t = value[t+1] (stacked: next_value = NULL, value (T+1,B)) or next_value[t] (value, next_value (T,B)).
+ *   q_t   = fmaf(gamma, k^d_t*nv_t, r_t)                       the one-step target of step t
+ *   lam_t = 1 for t = T-1, else [q_{t+1} >= value[t+1]]        (row t+1 of `value` in both forms; step t+1's own done)
+ *   a_t   = gamma*k^f_t*lam_t,   G_T = nv_{T-1},   G_t = fmaf(gamma*k^d_t - a_t, nv_t, r_t) + a_t*G_{t+1}
+ *   loss (1,) = -scale * sum rho (G_t - V_t) log pi(action), G a constant.
+ * A done step returns r_t; a time-limit truncation (next-value form, done_t = 0, traj_flag_t = 1, the final observation's
+ * value in next_value[t]) returns r_t + gamma*nv_t.  With gamma = 1, the stacked form and no masks (or all-zero masks) the
+ * loss and the saved coefficients equal hpc_rll_upgo_forward's bit for bit (the same launch configuration).
+ * ws: hpc_rll_upgo_workspace_floats(T,B) floats with the layout of hpc_rll_upgo_forward; backward: hpc_rll_upgo_backward.
+ * Argument errors, before any HIP call: HPC_RLL_EINVAL (negative sizes, N <= 0, NULL loss, bad mask_dtype, other NULL
+ * operands), HPC_RLL_EALIGN; T == 0 or B == 0 zeroes loss.
+ * hpc_rll_upgo_masked_last_config: the HPC_RLL_SCAN_CONFIG_INTS ints of hpc_rll_scan_last_config for this op ({0, -1 ...}
+ * before its first launch; HPC_RLL_EINVAL and nothing written for out == NULL).  The record is private to this entry
+ * point: the op list of hpc_rll_scan_last_config is part of ABI 6 and is unchanged. */
+int hpc_rll_upgo_masked_forward(const float* target_output, const float* rho, const int64_t* action, const float* reward,
+                                const float* value, const float* next_value, const void* done, const void* traj_flag,
+                                int mask_dtype, float* loss, float* ws, int T, int B, int N, float gamma, float scale,
+                                void* stream);
+int hpc_rll_upgo_masked_last_config(int* out);
+
 /* PPO -- replaces PPOForward/Backward (rl_utils/entry.h:158-165, src/rl_utils/ppo.cu:8-111).
  * logits (B,N), action (B,), value_new/old, adv, ret, weight (B,) (weight NULL = ones).
  * out5 = policy_loss, value_loss, entropy_loss, approx_kl, clipfrac.  dual_clip < 1 disables dual clip
