@@ -23,6 +23,14 @@
 //
 // Algorithmic HBM bytes per sample: forward 20 A + 16 (+4 weight, +4 value_old) read, 12 written;
 //                                   backward 12 A + 12 read, 8 A + 4 written.
+//
+// V-trace for the same heads (hpc_rll_vtrace_continuous_*; DI-engine's vtrace_error_continuous_action is the semantics):
+// gauss_heads_fwd_kernel is the head alone, for a PAIR of policies over one action.  Per row it writes logp of the target
+// policy, its entropy and logp_b = logp_t - d, with d the same sum of per-dimension differences as above (identical policies
+// give d = 0 and logp_b == logp_t bit for bit).  For V-trace it writes d itself in place of logp_b: logp_t is of size ~1.4 A, so
+// logp_b rounded to fp32 would give d back only to half an ulp of logp_t (6e-5 at A = 1024), and the scan forms IS = exp(d).
+// The three (T,B) arrays feed MaskedVtraceOp<.., LR> (scan_masked.hip); the backward is ppo_gauss_bwd_kernel with V-trace's saved
+// coef_pg / coef_ent as c1 / c2 and no value output.  Bytes per row: 20 A read, 12 written; backward 12 A + 8 read, 8 A written.
 #include <hip/hip_runtime.h>
 
 #include "hpc_rll_hip.h"
@@ -36,6 +44,7 @@ namespace {
 constexpr int kGaussMaxA = 1024;                        // 64 lanes x 16 floats per lane and input
 constexpr float kLn2 = 0.69314718055994530942f;
 constexpr float kEntConst = 1.41893853320467274178f;    // 1/2 + log(2 pi)/2: entropy of a unit normal
+constexpr float kHalfLn2Pi = 0.91893853320467274178f;   // log(2 pi)/2
 
 // sum over an aligned group of G lanes, valid in the group's LAST lane (G <= 16: in every lane)
 template <int G> __device__ __forceinline__ float gsum_last(float x) {
@@ -214,6 +223,77 @@ __global__ __launch_bounds__(256) void ppo_gauss_bwd_kernel(const float* __restr
     }
 }
 
+// The heads of two policies (t = target, b = behaviour) over one action, no loss: per row
+//   logp_t = -q/2 - sum log sigma_t - A log(2 pi)/2 (q = sum z_t^2),  ent = A (1/2 + log(2 pi)/2) + sum log sigma_t,
+//   logp_b = logp_t - d,  d = sum [(z_b - z_t)(z_b + z_t)/2 + (log sigma_b - log sigma_t)]  (the forward's difference above,
+//   with z_b - z_t formed from sigma_t - sigma_b and mu_t - mu_b: an fp32 emulation leaves 3e-7 rms in d at A = 376 against
+//   4e-6 from the difference of the two rounded z, which the V-trace policy loss inherits as a relative error);
+//   with log_ratio the third output is d itself (what the V-trace scan takes: d loses nothing to the size of logp_t).
+// Three sums per row, stored by the group's last lane; no LDS, no barrier, nothing accumulated across rows.
+template <int G, int VEC, int E>
+__global__ __launch_bounds__(256) void gauss_heads_fwd_kernel(const float* __restrict__ mu_t,
+                                                              const float* __restrict__ sigma_t,
+                                                              const float* __restrict__ mu_b,
+                                                              const float* __restrict__ sigma_b,
+                                                              const float* __restrict__ action, float* __restrict__ logp_t,
+                                                              float* __restrict__ ent, float* __restrict__ logp_b,
+                                                              const bool log_ratio, long rows, int A) {
+    constexpr int GPB = 256 / G;
+    constexpr int R = GaussRows<VEC, E>::value;
+    const int gl = threadIdx.x % G;
+    const int gi = threadIdx.x / G;
+    const bool full = A == G * VEC * E;   // uniform: no padding lanes
+    const float hconst = (float)A * kEntConst, lconst = (float)A * kHalfLn2Pi;
+    const long stride = (long)gridDim.x * GPB * R;
+    for (long bb = (long)blockIdx.x * GPB * R; bb < rows; bb += stride) {
+        GaussSlice<G, VEC, E> mt[R], st[R], mb[R], sb[R], ac[R];
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            long row = bb + (long)k * GPB + gi;
+            if (row >= rows) row = rows - 1;             // (re-reads the last row; the stores below are guarded)
+            const long off = row * (long)A;
+            mt[k].load(mu_t + off, A, gl);
+            st[k].load(sigma_t + off, A, gl);
+            mb[k].load(mu_b + off, A, gl);
+            sb[k].load(sigma_b + off, A, gl);
+            ac[k].load(action + off, A, gl);
+        }
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            float q = 0.f, h = 0.f, d = 0.f;   // this lane's part of sum z_t^2, sum log2 sigma_t and logp_t - logp_b
+#pragma unroll
+            for (int e = 0; e < E; ++e)
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) {
+                    const int i = e * VEC + j;
+                    const bool ok = full || (e * G + gl) * VEC + j < A;
+                    const float a = ac[k].x[i];
+                    const float rt = __builtin_amdgcn_rcpf(st[k].x[i]);
+                    const float zt = (a - mt[k].x[i]) * rt;
+                    const float zb = (a - mb[k].x[i]) * __builtin_amdgcn_rcpf(sb[k].x[i]);
+                    const float lt = log2_(st[k].x[i]), lb = log2_(sb[k].x[i]);
+                    // z_b - z_t = (z_b (sigma_t - sigma_b) + (mu_t - mu_b)) / sigma_t: from the small differences of the
+                    // parameters, not from two rounded z of size ~1 (whose difference is good to 1e-7 |z| only)
+                    const float dz = fmaf(zb, st[k].x[i] - sb[k].x[i], mt[k].x[i] - mb[k].x[i]) * rt;
+                    const float t = fmaf(0.5f * dz, zb + zt, (lb - lt) * kLn2);
+                    q += ok ? zt * zt : 0.f;
+                    h += ok ? lt : 0.f;
+                    d += ok ? t : 0.f;
+                }
+            q = gsum_last<G>(q);
+            h = gsum_last<G>(h);
+            d = gsum_last<G>(d);
+            const long row = bb + (long)k * GPB + gi;
+            if (gl == G - 1 && row < rows) {
+                const float lp = fmaf(-0.5f, q, -fmaf(h, kLn2, lconst));
+                logp_t[row] = lp;
+                ent[row] = fmaf(h, kLn2, hconst);
+                logp_b[row] = log_ratio ? d : lp - d;
+            }
+        }
+    }
+}
+
 struct GaussCfg { int g, vec, e; };
 
 // The group is one DPP row (16 lanes) or less while 4 pieces per lane suffice (A <= 256 with 16-byte loads, A <= 64 without);
@@ -285,6 +365,33 @@ int gauss_backward(const float* mu_new, const float* sigma_new, const float* act
 }
 
 }  // namespace
+
+// Internal C++ entry point used by scan_masked.hip (same library), as categorical_forward is: the head alone.
+int gaussian_heads_forward(const float* mu_t, const float* sigma_t, const float* mu_b, const float* sigma_b,
+                           const float* action, float* logp_t, float* ent, float* logp_b, bool log_ratio, long rows, int A,
+                           hipStream_t st) {
+    if (rows < 0 || A <= 0) return HPC_RLL_EINVAL;
+    if (rows > 0 && (!mu_t || !sigma_t || !mu_b || !sigma_b || !action || !logp_t || !ent || !logp_b)) return HPC_RLL_EINVAL;
+    for (const void* p : {(const void*)mu_t, (const void*)sigma_t, (const void*)mu_b, (const void*)sigma_b,
+                          (const void*)action, (const void*)logp_t, (const void*)ent, (const void*)logp_b})
+        if (reinterpret_cast<uintptr_t>(p) & 3) return HPC_RLL_EALIGN;
+    if (A > kGaussMaxA) return HPC_RLL_EUNSUPPORTED;
+    if (rows == 0) return HPC_RLL_OK;
+    const GaussCfg cfg = gauss_cfg(A, al16(mu_t) && al16(sigma_t) && al16(mu_b) && al16(sigma_b) && al16(action));
+#define HPC_RLL_GAUSS_HEADS_CASE(G_, V_, E_)                                                                          \
+    if (cfg.g == G_ && cfg.vec == V_ && cfg.e == E_) {                                                                \
+        const long per = (256 / G_) * GaussRows<V_, E_>::value;                                                       \
+        long grid = (rows + per - 1) / per;                                                                           \
+        if (grid > 256L * 1024) grid = 256L * 1024;     /* short-lived workgroups, as gauss_backward; they loop */    \
+        hipLaunchKernelGGL((gauss_heads_fwd_kernel<G_, V_, E_>), dim3((unsigned)grid), dim3(256), 0, st, mu_t,         \
+                           sigma_t, mu_b, sigma_b, action, logp_t, ent, logp_b, log_ratio, rows, A);                  \
+        return last_error();                                                                                          \
+    }
+    HPC_RLL_GAUSS_DISPATCH(HPC_RLL_GAUSS_HEADS_CASE)
+#undef HPC_RLL_GAUSS_HEADS_CASE
+    return HPC_RLL_EUNSUPPORTED;
+}
+
 }  // namespace hpc_rll
 
 using namespace hpc_rll;
@@ -331,4 +438,37 @@ extern "C" int hpc_rll_ppo_continuous_backward(const float* g_policy, const floa
     }
     return gauss_backward(mu_new, sigma_new, action, ws, ws + B, ws + 2 * (size_t)B, g_policy, g_ent, g_value, grad_mu,
                           grad_sigma, grad_value, B, A, st);
+}
+
+extern "C" int hpc_rll_gaussian_forward(const float* mu, const float* sigma, const float* mu_b, const float* sigma_b,
+                                        const float* action, float* logp, float* entropy, float* logp_b, int64_t rows,
+                                        int A, void* stream) {
+    return gaussian_heads_forward(mu, sigma, mu_b, sigma_b, action, logp, entropy, logp_b, /*log_ratio=*/false, (long)rows,
+                                  A, (hipStream_t)stream);
+}
+
+// The forward (hpc_rll_vtrace_continuous_forward) is in scan_masked.hip, next to MaskedVtraceOp.  ws as hpc_rll_vtrace_forward:
+// coef_pg at 0, coef_ent at T*B, gv_unit at 2*T*B.  grad_value is the STACKED form's (T+1,B), bootstrap row zeroed.
+extern "C" int hpc_rll_vtrace_continuous_backward(const float* g_pg, const float* g_value, const float* g_ent,
+                                                  const float* mu_target, const float* sigma_target, const float* action,
+                                                  const float* ws, float* grad_mu, float* grad_sigma, float* grad_value,
+                                                  int T, int B, int A, void* stream) {
+    if (T < 0 || B < 0 || A <= 0) return HPC_RLL_EINVAL;
+    const size_t TB = (size_t)T * B;
+    const bool heads = TB && (grad_mu || grad_sigma);
+    if (grad_value && (!g_value || (TB && !ws))) return HPC_RLL_EINVAL;
+    if (heads && (!mu_target || !sigma_target || !action || !ws)) return HPC_RLL_EINVAL;
+    for (const void* p : {(const void*)g_pg, (const void*)g_value, (const void*)g_ent, (const void*)mu_target,
+                          (const void*)sigma_target, (const void*)action, (const void*)ws, (const void*)grad_mu,
+                          (const void*)grad_sigma, (const void*)grad_value})
+        if (reinterpret_cast<uintptr_t>(p) & 3) return HPC_RLL_EALIGN;
+    if (A > kGaussMaxA) return HPC_RLL_EUNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    if (grad_value) {
+        const int rc = scale_rows(g_value, ws + 2 * TB, grad_value, (long)TB, (long)TB + B, st);
+        if (rc) return rc;
+    }
+    if (!heads) return HPC_RLL_OK;
+    return gauss_backward(mu_target, sigma_target, action, ws, ws + TB, nullptr, g_pg, g_ent, nullptr, grad_mu, grad_sigma,
+                          nullptr, (long)TB, A, st);
 }

@@ -25,7 +25,8 @@
 // A masked call therefore runs the chunking of its unmasked sibling and, without episode ends, gives its bits.
 // Instantiations (a closed list): 14 mask forms (with_mode: MM_NONE with u8 + 3 mask modes x 2 dtypes, times stacked /
 // next-value) x 13 scan configurations for TD(lambda) (launch_colscan with V2 and LC16) + 14 x 8 for V-trace (V = 1) +
-// 14 x 8 for UPGO (V = 1): 406 kernels, none using scratch (tests/tools/kernel_regs.py scan_masked).
+// 14 x 8 for UPGO (V = 1) + 14 x 8 for V-trace over a log ratio (LR, the Gaussian head): 518 kernels, none using scratch
+// (tests/tools/kernel_regs.py scan_masked).
 #include <hip/hip_runtime.h>
 
 #include "colscan.hpp"
@@ -36,6 +37,9 @@ namespace hpc_rll {
 
 int categorical_forward(const float* logits, const int64_t* action, float* logp, float* ent, long rows, int N,
                         hipStream_t st);
+int gaussian_heads_forward(const float* mu_t, const float* sigma_t, const float* mu_b, const float* sigma_b,
+                           const float* action, float* logp_t, float* ent, float* logp_b, bool log_ratio, long rows, int A,
+                           hipStream_t st);
 
 namespace {
 
@@ -113,7 +117,8 @@ struct MaskedTdLambdaOp {
 // V-trace with masks: IS, rho, c, rho_pg, entropy, the three losses and the saved coefficients as VtraceOp
 //   (coef_pg = -w adv scale, coef_ent = w scale, gv_unit = 2 w (V_t - vs_t) scale = -2 w s_t scale)
 // ================================================================================================
-template <int MT, int MM, bool NVF>
+// LR: the logp_b slot holds the log ratio logp_t - logp_b itself (the Gaussian head: hpc_rll_vtrace_continuous_forward), not logp_b
+template <int MT, int MM, bool NVF, bool LR = false>
 struct MaskedVtraceOp {
     static constexpr int NACC = 3, DIAG_OP = HPC_RLL_SCAN_OP_VTRACE_MASKED, DIAG_MT = MT, DIAG_MM = MM, DIAG_NVF = NVF;
     static constexpr bool HD = has_done(MM), HF = has_flag(MM), ANY = HD || HF;
@@ -144,7 +149,7 @@ struct MaskedVtraceOp {
         if (HF) row.mf.template load<false>(flag, o);
 #pragma unroll
         for (int k = 0; k < V; ++k) {
-            row.is.v[k] = expf(row.lp.v[k] - lb.v[k]);
+            row.is.v[k] = expf(LR ? lb.v[k] : row.lp.v[k] - lb.v[k]);
             if (!weight) row.w.v[k] = 1.f;
         }
     }
@@ -264,6 +269,29 @@ struct MaskedUpgoOp {
 
 inline bool valid_mask_dtype(int mt) { return mt == HPC_RLL_MASK_U8 || mt == HPC_RLL_MASK_F32; }
 
+// The V-trace scan over a workspace whose logp_t | ent | logp_b slots a head (categorical or Gaussian) has filled:
+// ws layout of hpc_rll_vtrace_forward (scan_ops.hip), coef_pg | coef_ent | gv_unit | logp_t | ent | logp_b | partials.
+// LR: the logp_b slot holds logp_t - logp_b.
+template <bool LR>
+int vtrace_masked_scan(const float* value, const float* next_value, const float* reward, const float* weight,
+                       const void* done, const void* traj_flag, int mask_dtype, float* losses, float* ws, int T, int B,
+                       float gamma, float lambda, float rho_clip, float c_clip, float rho_pg_clip, float scale,
+                       hipStream_t st) {
+    const size_t TB = (size_t)T * B;
+    float *coef_pg = ws, *coef_ent = ws + TB, *gv_unit = ws + 2 * TB, *logp_t = ws + 3 * TB, *ent = ws + 4 * TB,
+          *logp_b = ws + 5 * TB, *partials = ws + 6 * TB;
+    const ScanCfg c = scan_cfg(T, B, false);   // V = 1, as hpc_rll_vtrace_forward
+    const float sc[3] = {scale, scale, scale};
+    int rc = HPC_RLL_OK;
+    with_mode(mask_dtype, mask_mode(done, traj_flag), next_value != nullptr, [&](auto MT_, auto MM_, auto NV_) {
+        using Op = MaskedVtraceOp<decltype(MT_)::value, decltype(MM_)::value, decltype(NV_)::value != 0, LR>;
+        const Op op{value, next_value, reward, weight, logp_t, logp_b, ent, done, traj_flag, coef_pg, coef_ent, gv_unit,
+                    T, B, gamma, gamma * lambda, rho_clip, c_clip, rho_pg_clip, scale};
+        rc = scan_and_finalize<Op, false>(op, c, T, B, partials, 3, sc, losses, st);
+    });
+    return rc;
+}
+
 }  // namespace
 }  // namespace hpc_rll
 
@@ -314,21 +342,46 @@ extern "C" int hpc_rll_vtrace_masked_forward(const float* target_output, const f
         return HPC_RLL_EALIGN;
     if (mask_dtype == HPC_RLL_MASK_F32 && (!aligned(done, 4) || !aligned(traj_flag, 4))) return HPC_RLL_EALIGN;
     const size_t TB = (size_t)T * B;   // ws layout of hpc_rll_vtrace_forward (scan_ops.hip)
-    float *coef_pg = ws, *coef_ent = ws + TB, *gv_unit = ws + 2 * TB, *logp_t = ws + 3 * TB, *ent = ws + 4 * TB,
-          *logp_b = ws + 5 * TB, *partials = ws + 6 * TB;
+    float *logp_t = ws + 3 * TB, *ent = ws + 4 * TB, *logp_b = ws + 5 * TB;
     int rc = categorical_forward(target_output, action, logp_t, ent, (long)TB, N, st);
     if (rc) return rc;
     rc = categorical_forward(behaviour_output, action, logp_b, nullptr, (long)TB, N, st);
     if (rc) return rc;
-    const ScanCfg c = scan_cfg(T, B, false);   // V = 1, as hpc_rll_vtrace_forward
-    const float sc[3] = {scale, scale, scale};
-    with_mode(mask_dtype, mask_mode(done, traj_flag), next_value != nullptr, [&](auto MT_, auto MM_, auto NV_) {
-        using Op = MaskedVtraceOp<decltype(MT_)::value, decltype(MM_)::value, decltype(NV_)::value != 0>;
-        const Op op{value, next_value, reward, weight, logp_t, logp_b, ent, done, traj_flag, coef_pg, coef_ent, gv_unit,
-                    T, B, gamma, gamma * lambda, rho_clip, c_clip, rho_pg_clip, scale};
-        rc = scan_and_finalize<Op, false>(op, c, T, B, partials, 3, sc, losses, st);
-    });
-    return rc;
+    return vtrace_masked_scan<false>(value, next_value, reward, weight, done, traj_flag, mask_dtype, losses, ws, T, B, gamma,
+                                     lambda, rho_clip, c_clip, rho_pg_clip, scale, st);
+}
+
+// V-trace for diagonal-Gaussian policies (gaussian.hip: gauss_heads_fwd_kernel): one head launch writes logp_t, ent and the
+// log ratio d = logp_t - logp_b into the workspace, and from there on this is hpc_rll_vtrace_masked_forward
+// (vtrace_masked_scan): the same Op, with IS = exp(d) instead of exp(logp_t - logp_b), the same configuration for the same
+// (T, B), and its dispatch record.  d goes to the scan as it is because logp_t is of size ~1.4 A: a logp_b = logp_t - d rounded to
+// fp32 gives d back only to half an ulp of logp_t (6e-5 at A = 1024), which the policy loss inherits whatever T*B is.
+extern "C" int hpc_rll_vtrace_continuous_forward(const float* mu_target, const float* sigma_target,
+                                                 const float* mu_behaviour, const float* sigma_behaviour,
+                                                 const float* action, const float* value, const float* next_value,
+                                                 const float* reward, const float* weight, const void* done,
+                                                 const void* traj_flag, int mask_dtype, float* losses, float* ws, int T,
+                                                 int B, int A, float gamma, float lambda, float rho_clip, float c_clip,
+                                                 float rho_pg_clip, float scale, void* stream) {
+    if (T < 0 || B < 0 || A <= 0 || !losses || !valid_mask_dtype(mask_dtype)) return HPC_RLL_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const bool empty = T == 0 || B == 0;
+    if (!empty && (!mu_target || !sigma_target || !mu_behaviour || !sigma_behaviour || !action || !value || !reward || !ws))
+        return HPC_RLL_EINVAL;
+    if (!aligned(mu_target, 4) || !aligned(sigma_target, 4) || !aligned(mu_behaviour, 4) || !aligned(sigma_behaviour, 4) ||
+        !aligned(action, 4) || !aligned(value, 4) || !aligned(next_value, 4) || !aligned(reward, 4) || !aligned(weight, 4) ||
+        !aligned(losses, 4) || !aligned(ws, 4))
+        return HPC_RLL_EALIGN;
+    if (mask_dtype == HPC_RLL_MASK_F32 && (!aligned(done, 4) || !aligned(traj_flag, 4))) return HPC_RLL_EALIGN;
+    if (A > 1024) return HPC_RLL_EUNSUPPORTED;   // the head's limit (gaussian.hip), after the null checks
+    if (empty) return (int)hipMemsetAsync(losses, 0, 3 * sizeof(float), st);
+    const size_t TB = (size_t)T * B;   // ws layout of hpc_rll_vtrace_forward (scan_ops.hip)
+    float *logp_t = ws + 3 * TB, *ent = ws + 4 * TB, *logp_b = ws + 5 * TB;
+    int rc = gaussian_heads_forward(mu_target, sigma_target, mu_behaviour, sigma_behaviour, action, logp_t, ent, logp_b,
+                                    /*log_ratio=*/true, (long)TB, A, st);
+    if (rc) return rc;
+    return vtrace_masked_scan<true>(value, next_value, reward, weight, done, traj_flag, mask_dtype, losses, ws, T, B, gamma,
+                                    lambda, rho_clip, c_clip, rho_pg_clip, scale, st);
 }
 
 // ------------------------------------------------------------------------------------------------ UPGO

@@ -3,7 +3,7 @@
 // Two layers in one module:
 //   * the reference's L2 functions `XxxForward(inputs, outputs, scalars...)` / `XxxBackward(inputs, outputs)`
 //     (declared in include/hpc/rll/cuda/rl_utils/entry.h:10-165) -- validated, launched on torch's current stream;
-//   * fused autograd ops (`gae`, `td_lambda`, `vtrace`, `upgo`, `upgo_masked`, `ppo`, `ppo_continuous`, `q_nstep_td`, `dist_nstep_td`, `iqn_nstep_td`,
+//   * fused autograd ops (`gae`, `td_lambda`, `vtrace`, `upgo`, `upgo_masked`, `ppo`, `ppo_continuous`, `vtrace_continuous`, `q_nstep_td`, `dist_nstep_td`, `iqn_nstep_td`,
 //     `qrdqn_nstep_td`) -- torch::autograd::Function nodes that allocate outputs, launch and register backward in ONE
 //     pybind call; these are what hpc_rll.rl_utils.* modules use.
 // Host-only C++: every kernel lives behind the C ABI of libhpc_rll_hip.so (include/hpc_rll_hip.h).
@@ -747,6 +747,80 @@ struct PpoContinuousFn : public ag::Function<PpoContinuousFn> {
     }
 };
 
+// V-trace with a diagonal-Gaussian head (hpc_rll_vtrace_continuous_*): the masks, value forms and checks of vtrace_masked;
+// mu / sigma of the target and the behaviour policy and the action are (T,B,A) fp32.  Gradients flow to mu_target,
+// sigma_target and value; backward allocates only the gradients autograd asks for.
+struct VtraceContinuousFn : public ag::Function<VtraceContinuousFn> {
+    static ag::tensor_list forward(ag::AutogradContext* ctx, const Tensor& mu_t, const Tensor& sigma_t, const Tensor& mu_b,
+                                   const Tensor& sigma_b, const Tensor& action, const Tensor& value, const Tensor& reward,
+                                   const OptTensor& done, const OptTensor& flag, const OptTensor& next_value,
+                                   const OptTensor& weight, double gamma, double lambda, double rho_clip, double c_clip,
+                                   double rho_pg_clip, std::optional<double> scale) {
+        TORCH_CHECK(mu_t.defined(), "mu_target: expected a tensor, got None");
+        TORCH_CHECK(mu_t.dim() == 3, "mu_target: expected (T,B,A), got ", mu_t.sizes());
+        const int64_t T = mu_t.size(0), B = mu_t.size(1), A = mu_t.size(2);
+        check_shape(mu_t, "mu_target", {T, B, A});
+        check_shape(sigma_t, "sigma_target", {T, B, A});
+        check_shape(mu_b, "mu_behaviour", {T, B, A});
+        check_shape(sigma_b, "sigma_behaviour", {T, B, A});
+        check_shape(action, "action", {T, B, A});
+        check_shape(reward, "reward", {T, B});
+        if (has(weight)) check_shape(*weight, "weight", {T, B});
+        TORCH_CHECK(A >= 1 && A <= 1024, "vtrace_continuous: an action dimension of ", A,
+                    " is not supported by the gfx950 kernels (1 <= A <= 1024)");
+        const Masks m = check_masked_inputs("vtrace_continuous", value, reward, done, flag, next_value);
+        const at::Device dev = reward.device();
+        req(mu_t, "mu_target", dev);
+        req(sigma_t, "sigma_target", dev);
+        req(mu_b, "mu_behaviour", dev);
+        req(sigma_b, "sigma_behaviour", dev);
+        req(action, "action", dev);
+        if (has(weight)) req(*weight, "weight", dev);
+        c10::DeviceGuard g(dev);
+        Tensor losses = new_f32({3}, dev);
+        Tensor ws = vtrace_workspace(T, B, dev);
+        check(hpc_rll_vtrace_continuous_forward(fptr(mu_t), fptr(sigma_t), fptr(mu_b), fptr(sigma_b), fptr(action),
+                                                fptr(value), fptr(next_value), fptr(reward), fptr(weight), vptr(m.done),
+                                                vptr(m.flag), m.code, fmut(losses), fmut(ws), to_int(T, "T"),
+                                                to_int(B, "B"), to_int(A, "A"), (float)gamma, (float)lambda,
+                                                (float)rho_clip, (float)c_clip, (float)rho_pg_clip,
+                                                loss_scale(scale, T * B), stream_of(dev)),
+              "hpc_rll_vtrace_continuous_forward");
+        ctx->save_for_backward({mu_t, sigma_t, action, ws});
+        ctx->saved_data["stacked"] = !has(next_value);
+        return {alias_of(losses, 0, 1), alias_of(losses, 1, 1), alias_of(losses, 2, 1)};
+    }
+    static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
+        ag::tensor_list out(17);
+        const bool need_m = ctx->needs_input_grad(0), need_s = ctx->needs_input_grad(1), need_v = ctx->needs_input_grad(5);
+        if (!(need_m || need_s || need_v)) return out;
+        const bool stacked = ctx->saved_data["stacked"].toBool();
+        const auto saved = ctx->get_saved_variables();
+        const Tensor &mu_t = saved[0], &sigma_t = saved[1], &action = saved[2], &ws = saved[3];
+        const at::Device dev = mu_t.device();
+        c10::DeviceGuard g(dev);
+        const int64_t T = mu_t.size(0), B = mu_t.size(1), A = mu_t.size(2);
+        Tensor g_pg = grad1(grads[0], dev, "grad_policy_loss"), g_v = grad1(grads[1], dev, "grad_value_loss"),
+               g_e = grad1(grads[2], dev, "grad_entropy_loss");
+        Tensor grad_mu = need_m ? at::empty_like(mu_t) : undef();
+        Tensor grad_sigma = need_s ? at::empty_like(sigma_t) : undef();
+        Tensor grad_value = need_v ? new_f32({stacked ? T + 1 : T, B}, dev) : undef();
+        // next-value form: the unit value gradient (ws rows 2T*B ...) has T rows and no bootstrap row to zero
+        check(hpc_rll_vtrace_continuous_backward(fptr(g_pg), fptr(g_v), fptr(g_e), fptr(mu_t), fptr(sigma_t), fptr(action),
+                                                 fptr(ws), fmut(grad_mu), fmut(grad_sigma),
+                                                 fmut(stacked ? grad_value : undef()), (int)T, (int)B, (int)A,
+                                                 stream_of(dev)),
+              "hpc_rll_vtrace_continuous_backward");
+        if (need_v && !stacked)
+            check(hpc_rll_scale_rows(fptr(g_v), fptr(ws) + 2 * T * B, fmut(grad_value), T * B, T * B, stream_of(dev)),
+                  "hpc_rll_scale_rows");
+        out[0] = grad_mu;
+        out[1] = grad_sigma;
+        out[5] = grad_value;
+        return out;
+    }
+};
+
 // ==================================================================================================== q n-step TD
 struct QDims { int64_t B, N, nstep; at::Device dev; };
 int64_t check_nstep_reward(const Tensor& reward, int64_t B, const at::Device& dev) {
@@ -1285,6 +1359,20 @@ PYBIND11_MODULE(hpc_rl_utils, m) {
           py::arg("scale") = py::none(),
           "PPO losses (policy, value, entropy, info) for a diagonal-Gaussian policy: mu / sigma / action (B,A) fp32, "
           "sigma > 0; differentiable wrt mu_new, sigma_new and value_new");
+    m.def("vtrace_continuous", [](const Tensor& mu_t, const Tensor& sigma_t, const Tensor& mu_b, const Tensor& sigma_b,
+                                  const Tensor& action, const Tensor& value, const Tensor& reward, const OptTensor& done,
+                                  const OptTensor& traj_flag, const OptTensor& next_value, const OptTensor& weight,
+                                  double gamma, double lambda, double rho_clip, double c_clip, double rho_pg_clip,
+                                  std::optional<double> scale) {
+        return VtraceContinuousFn::apply(mu_t, sigma_t, mu_b, sigma_b, action, value, reward, done, traj_flag, next_value,
+                                         weight, gamma, lambda, rho_clip, c_clip, rho_pg_clip, scale);
+    }, py::arg("mu_target"), py::arg("sigma_target"), py::arg("mu_behaviour"), py::arg("sigma_behaviour"), py::arg("action"),
+          py::arg("value"), py::arg("reward"), py::arg("done") = py::none(), py::arg("traj_flag") = py::none(),
+          py::arg("next_value") = py::none(), py::arg("weight") = py::none(), py::arg("gamma") = 0.99,
+          py::arg("lambda_") = 0.95, py::arg("rho_clip_ratio") = 1.0, py::arg("c_clip_ratio") = 1.0,
+          py::arg("rho_pg_clip_ratio") = 1.0, py::arg("scale") = py::none(),
+          "episode-aware V-trace losses (policy, value, entropy) for diagonal-Gaussian policies: mu / sigma / action (T,B,A) "
+          "fp32, sigma > 0; differentiable wrt mu_target, sigma_target and value");
     m.def("q_nstep_td", [](const Tensor& q, const Tensor& nq, const Tensor& action, const Tensor& naction,
                            const Tensor& reward, const Tensor& done, const OptTensor& weight, double gamma, bool rescale,
                            std::optional<double> scale) {

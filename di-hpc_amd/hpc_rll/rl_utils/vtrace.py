@@ -6,7 +6,10 @@ Backward recomputes the softmax from ``target_output`` instead of saving three (
 ``hpc_rl_utils.vtrace`` (compiled torch::autograd::Function).
 
 ``masked_vtrace`` / ``MaskedVTrace`` (no reference counterpart) are episode-aware V-trace with ``done`` and ``traj_flag``
-masks, the conventions of ``hpc_rll.rl_utils.gae.masked_gae``; see ``masked_vtrace``."""
+masks, the conventions of ``hpc_rll.rl_utils.gae.masked_gae``; see ``masked_vtrace``.
+
+``vtrace_continuous`` / ``VTraceContinuous`` (no reference counterpart) are ``masked_vtrace`` for diagonal-Gaussian policies
+(continuous actions, DI-engine's ``vtrace_error_continuous_action``); see ``vtrace_continuous``."""
 from collections import namedtuple
 
 import torch
@@ -88,6 +91,56 @@ class MaskedVTrace(torch.nn.Module):
         pg, v, e = hpc_rl_utils.vtrace_masked(target_output, behaviour_output, action, value, reward, done, traj_flag,
                                               next_value, weight, gamma, lambda_, rho_clip_ratio, c_clip_ratio,
                                               rho_pg_clip_ratio, scale)
+        if self.sharded:
+            pg, v, e = _dp.all_reduce_sum((pg, v, e), self.group)     # the three scalars in ONE all-reduce
+        return hpc_vtrace_loss(pg, v, e)
+
+
+def vtrace_continuous(mu_target, sigma_target, mu_behaviour, sigma_behaviour, action, value, reward, done=None,
+                      weight=None, gamma: float = 0.99, lambda_: float = 0.95, rho_clip_ratio: float = 1.0,
+                      c_clip_ratio: float = 1.0, rho_pg_clip_ratio: float = 1.0, next_value=None, traj_flag=None):
+    r"""Episode-aware V-trace losses for diagonal-Gaussian policies (continuous actions; the semantics of DI-engine's
+    ``vtrace_error_continuous_action``, with the masks of :func:`masked_vtrace`).
+
+    ``mu_*``, ``sigma_*`` and ``action`` are (T,B,A) float32, ``1 <= A <= 1024``; ``sigma`` is the standard deviation and
+    ``sigma > 0`` is the caller's contract (device values are not checked).  With ``z = (action - mu) / sigma`` per
+    dimension, summed over the A dimensions::
+
+        logp    = sum(-z^2/2 - log(sigma)) - A*log(2*pi)/2            (target and behaviour policy alike)
+        entropy = A*(1/2 + log(2*pi)/2) + sum(log(sigma_target))
+        IS      = exp(logp_target - logp_behaviour)
+
+    which are ``Independent(Normal(mu, sigma), 1).log_prob(action)`` and ``.entropy()``.  The log ratio is accumulated as a
+    sum of per-dimension differences, so it does not lose precision as A grows, and identical policies give ``IS = 1``
+    exactly.  From ``IS`` on -- ``rho``, ``c``, ``rho_pg``, the recursion for ``vs`` and ``adv`` with ``done`` /
+    ``traj_flag`` / ``next_value``, ``weight`` (None or (T,B)) and the three mean losses -- everything is
+    :func:`masked_vtrace`, bit for bit for equal log-probabilities: policy_loss = -mean(logp_target * adv * weight),
+    value_loss = mean(weight * (value - vs)^2), entropy_loss = mean(weight * entropy).
+
+    Gradients flow to ``mu_target``, ``sigma_target`` and ``value`` (rows ``t < T``; the stacked bootstrap row gets zero);
+    nothing flows to the behaviour policy, ``action``, ``reward``, ``next_value`` or the masks.  Returns ``hpc_vtrace_loss``.
+    """
+    pg, v, e = hpc_rl_utils.vtrace_continuous(mu_target, sigma_target, mu_behaviour, sigma_behaviour, action, value, reward,
+                                              done, traj_flag, next_value, weight, gamma, lambda_, rho_clip_ratio,
+                                              c_clip_ratio, rho_pg_clip_ratio)
+    return hpc_vtrace_loss(pg, v, e)
+
+
+class VTraceContinuous(torch.nn.Module):
+    """Module form of :func:`vtrace_continuous`, with the data-parallel option of :class:`MaskedVTrace`
+    (``sharded=True``: 1/(global count) scale and the three losses in one all-reduce)."""
+
+    def __init__(self, T, B, A, sharded: bool = False, group=None):
+        super().__init__()
+        self.T, self.B, self.A, self.sharded, self.group = T, B, A, sharded, group
+
+    def forward(self, mu_target, sigma_target, mu_behaviour, sigma_behaviour, action, value, reward, done=None,
+                weight=None, gamma: float = 0.99, lambda_: float = 0.95, rho_clip_ratio: float = 1.0,
+                c_clip_ratio: float = 1.0, rho_pg_clip_ratio: float = 1.0, next_value=None, traj_flag=None):
+        scale = _dp.loss_scale(reward.numel(), self.group, True) if self.sharded else None
+        pg, v, e = hpc_rl_utils.vtrace_continuous(mu_target, sigma_target, mu_behaviour, sigma_behaviour, action, value,
+                                                  reward, done, traj_flag, next_value, weight, gamma, lambda_,
+                                                  rho_clip_ratio, c_clip_ratio, rho_pg_clip_ratio, scale)
         if self.sharded:
             pg, v, e = _dp.all_reduce_sum((pg, v, e), self.group)     # the three scalars in ONE all-reduce
         return hpc_vtrace_loss(pg, v, e)

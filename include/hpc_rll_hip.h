@@ -317,6 +317,44 @@ int hpc_rll_ppo_continuous_backward(const float* g_policy, const float* g_value,
                                     const float* sigma_new, const float* action, const float* ws, float* grad_mu,
                                     float* grad_sigma, float* grad_value, int B, int A, void* stream);
 
+/* Gaussian heads and V-trace for diagonal-Gaussian policies (continuous actions; no reference counterpart, semantics of
+ * DI-engine's vtrace_error_continuous_action).  sigma is the standard deviation and must be > 0 (not checked: device values);
+ * 1 <= A <= 1024, beyond that HPC_RLL_EUNSUPPORTED.
+ * hpc_rll_gaussian_forward -- the head alone for a PAIR of policies over one action, the analogue of
+ *   hpc_rll_categorical_forward: mu, sigma (the policy whose logp and entropy are wanted), mu_b, sigma_b (the other policy),
+ *   action (rows,A) fp32 -> logp, entropy, logp_b (rows,), all eight pointers required.  With z = (a - mu)/sigma:
+ *     logp = sum_j [-z_j^2/2 - log sigma_j] - A log(2 pi)/2,   entropy = A (1/2 + log(2 pi)/2) + sum_j log sigma_j,
+ *     logp_b = logp - d,   d = sum_j [(z_b,j - z_j)(z_b,j + z_j)/2 + (log sigma_b,j - log sigma_j)]
+ *   so that logp - logp_b recovers the log ratio d to within half an ulp of logp (|logp| ~ 1.4 A) instead of subtracting two
+ *   independently rounded sums of size ~A; identical policies give logp_b == logp bit for bit.  rows == 0: OK, nothing launched.
+ * hpc_rll_vtrace_continuous_forward -- that head over T*B rows into the workspace, then the scan of
+ *   hpc_rll_vtrace_masked_forward: masks, mask_dtype, the two value forms, the formulas, losses (3,), the workspace
+ *   (hpc_rll_vtrace_workspace_floats(T,B), layout coef_pg | coef_ent | gv_unit | logp_t | ent | d | partials) and the
+ *   dispatch record (HPC_RLL_SCAN_OP_VTRACE_MASKED) are that entry point's.  One difference: the head hands the scan the log
+ *   ratio d itself (the slot that holds logp_b for the categorical op) and the scan forms IS = exp(d): logp is of size ~1.4 A,
+ *   and a logp_b rounded to fp32 would give d back only to half an ulp of logp (6e-5 at A = 1024), an error the policy loss
+ *   would carry whatever T*B is.  T == 0 or B == 0 zeroes losses.
+ * hpc_rll_vtrace_continuous_backward -- g_* device scalars (NULL = 1); grad_mu, grad_sigma (T,B,A) and grad_value may each be
+ *   NULL (not wanted): grad_mu = k1 z/sigma, grad_sigma = (k1 (z^2 - 1) + k2)/sigma, k1 = g_pg*ws[i], k2 = g_ent*ws[T*B + i].
+ *   grad_value is the STACKED form's (T+1,B) = g_value*ws[2*T*B + i] with the bootstrap row zeroed; in the next-value form
+ *   pass grad_value = NULL and call hpc_rll_scale_rows(g_value, ws + 2*T*B, grad_value, T*B, T*B), as for
+ *   hpc_rll_vtrace_masked_forward.  Nothing flows to the behaviour policy or the action.
+ * Argument errors, before any HIP call: HPC_RLL_EINVAL (null operands, negative sizes, A <= 0, bad mask_dtype), HPC_RLL_EALIGN
+ * (a pointer off 4-byte alignment), then HPC_RLL_EUNSUPPORTED (A > 1024). */
+int hpc_rll_gaussian_forward(const float* mu, const float* sigma, const float* mu_b, const float* sigma_b,
+                             const float* action, float* logp, float* entropy, float* logp_b,
+                             int64_t rows, int A, void* stream);
+int hpc_rll_vtrace_continuous_forward(const float* mu_target, const float* sigma_target, const float* mu_behaviour,
+                                      const float* sigma_behaviour, const float* action, const float* value,
+                                      const float* next_value, const float* reward, const float* weight,
+                                      const void* done, const void* traj_flag, int mask_dtype, float* losses, float* ws,
+                                      int T, int B, int A, float gamma, float lambda, float rho_clip, float c_clip,
+                                      float rho_pg_clip, float scale, void* stream);
+int hpc_rll_vtrace_continuous_backward(const float* g_pg, const float* g_value, const float* g_ent,
+                                       const float* mu_target, const float* sigma_target, const float* action,
+                                       const float* ws, float* grad_mu, float* grad_sigma, float* grad_value,
+                                       int T, int B, int A, void* stream);
+
 /* q n-step TD (rescale=0)/ with value rescaling (rescale=1) -- replaces QNStepTd{,Rescale}Forward/Backward
  * (rl_utils/entry.h:89-109).  q,next_n_q (B,N); action,next_n_action (B,) int64; reward (nstep,B); done,
  * weight (B,) float (weight NULL = ones).  loss (1,), td_err (B,), grad_buf (B,). */
