@@ -281,8 +281,10 @@ inline unsigned scan_grid(const ScanCfg& c, int B) {
 // The episode-aware UPGO (scan_masked.hip) keeps its record in a slot PAST the header's op list: HPC_RLL_SCAN_OPS and the
 // range hpc_rll_scan_last_config accepts are part of ABI 6 and stay as they are; hpc_rll_upgo_masked_last_config is the
 // only reader of this slot.
+// Retrace (retrace.hip) has the next private slot, read only by hpc_rll_retrace_last_config.
 constexpr int kScanOpUpgoMasked = HPC_RLL_SCAN_OPS;
-constexpr int kScanRecords = HPC_RLL_SCAN_OPS + 1;
+constexpr int kScanOpRetrace = HPC_RLL_SCAN_OPS + 1;
+constexpr int kScanRecords = HPC_RLL_SCAN_OPS + 2;
 void scan_note_launch(int op, int v, int lc, int nw, int sub, int ntl, int mask_dtype, int mask_mode, int nvf, long grid);
 void scan_note_final(int op, int how);
 template <class Op, class = void> struct ScanDiagMask { static constexpr int mt = 0, mm = 0, nvf = 0; };

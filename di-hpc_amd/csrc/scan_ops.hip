@@ -271,8 +271,9 @@ ScanFold make_fold(hipStream_t st, int nacc, const float* scale, float* out, lon
 }
 
 // The scan family's dispatch record (colscan.hpp: scan_note_launch / scan_note_final write it, hpc_rll_scan_last_config
-// reads it).  Plain ints of the host process, like the GAE record of gae.hip: not synchronised.  The last slot
-// (kScanOpUpgoMasked) is internal: only hpc_rll_upgo_masked_last_config reads it.
+// reads it).  Plain ints of the host process, like the GAE record of gae.hip: not synchronised.  The last two
+// slots (kScanOpUpgoMasked, kScanOpRetrace) are internal: only hpc_rll_upgo_masked_last_config and
+// hpc_rll_retrace_last_config read them.
 namespace {
 int g_scan_last[kScanRecords][HPC_RLL_SCAN_CONFIG_INTS];   // [op][0] = launches so far; zero at load
 int read_scan_record(int slot, int* out) {
@@ -305,6 +306,11 @@ extern "C" int hpc_rll_scan_last_config(int op, int* out) {
 extern "C" int hpc_rll_upgo_masked_last_config(int* out) {
     if (!out) return HPC_RLL_EINVAL;
     return read_scan_record(kScanOpUpgoMasked, out);
+}
+
+extern "C" int hpc_rll_retrace_last_config(int* out) {
+    if (!out) return HPC_RLL_EINVAL;
+    return read_scan_record(kScanOpRetrace, out);
 }
 
 // ------------------------------------------------------------------------------------------------ TD(lambda)

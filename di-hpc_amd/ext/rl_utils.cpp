@@ -3,7 +3,7 @@
 // Two layers in one module:
 //   * the reference's L2 functions `XxxForward(inputs, outputs, scalars...)` / `XxxBackward(inputs, outputs)`
 //     (declared in include/hpc/rll/cuda/rl_utils/entry.h:10-165) -- validated, launched on torch's current stream;
-//   * fused autograd ops (`gae`, `td_lambda`, `vtrace`, `upgo`, `upgo_masked`, `ppo`, `ppo_continuous`, `vtrace_continuous`, `q_nstep_td`, `dist_nstep_td`, `iqn_nstep_td`,
+//   * fused autograd ops (`gae`, `td_lambda`, `vtrace`, `upgo`, `upgo_masked`, `ppo`, `ppo_continuous`, `vtrace_continuous`, `retrace_loss`, `q_nstep_td`, `dist_nstep_td`, `iqn_nstep_td`,
 //     `qrdqn_nstep_td`) -- torch::autograd::Function nodes that allocate outputs, launch and register backward in ONE
 //     pybind call; these are what hpc_rll.rl_utils.* modules use.
 // Host-only C++: every kernel lives behind the C ABI of libhpc_rll_hip.so (include/hpc_rll_hip.h).
@@ -821,6 +821,110 @@ struct VtraceContinuousFn : public ag::Function<VtraceContinuousFn> {
     }
 };
 
+// ======================================================================================================= Retrace
+// Retrace(lambda) Q targets for discrete actions (hpc_rll_retrace_*; DI-engine's compute_q_retraces / acer_value_error).
+// Shapes and dtypes are checked before the device so that a wrong argument is named even on host tensors.
+Tensor retrace_workspace(int64_t T, int64_t B, const at::Device& dev) {
+    return new_f32({hpc_rll_retrace_workspace_floats(to_int(T, "T"), to_int(B, "B"))}, dev);
+}
+void retrace_check_n(const char* op, int64_t N) {
+    TORCH_CHECK(N >= 1 && N <= 1024, op, ": an action count of ", N, " is not supported by the gfx950 kernels (1 <= N <= 1024)");
+}
+
+// The drop-in form: v_pred (T+1,B,1) and ratio (T,B,N) are given; q_retraces (T+1,B,1), no gradient.
+Tensor retrace_targets(const Tensor& q, const Tensor& v_pred, const Tensor& reward, const Tensor& action,
+                       const OptTensor& weights, const Tensor& ratio, double gamma, double lambda) {
+    TORCH_CHECK(q.defined(), "q_values: expected a tensor, got None");
+    TORCH_CHECK(q.dim() == 3 && q.size(0) >= 1, "q_values: expected (T+1,B,N), got ", q.sizes());
+    const int64_t T = q.size(0) - 1, B = q.size(1), N = q.size(2);
+    check_shape(q, "q_values", {T + 1, B, N});
+    check_shape(v_pred, "v_pred", {T + 1, B, 1});
+    check_shape(reward, "rewards", {T, B});
+    check_shape(action, "actions", {T, B}, at::kLong);
+    if (has(weights)) check_shape(*weights, "weights", {T, B});
+    check_shape(ratio, "ratio", {T, B, N});
+    retrace_check_n("retrace", N);
+    const at::Device dev = q.device();
+    req(q, "q_values", dev);
+    req(v_pred, "v_pred", dev);
+    req(reward, "rewards", dev);
+    req(action, "actions", dev, at::kLong);
+    if (has(weights)) req(*weights, "weights", dev);
+    req(ratio, "ratio", dev);
+    c10::DeviceGuard g(dev);
+    if (T == 0 || B == 0) return v_pred.detach().clone();   // no step: Q_T = v_T
+    Tensor out = new_f32({T + 1, B, 1}, dev);
+    Tensor ws = new_f32({2 * T * B}, dev);
+    check(hpc_rll_retrace_forward(fptr(q), fptr(v_pred), fptr(reward), iptr(action), fptr(weights), fptr(ratio), fmut(out),
+                                  fmut(ws), to_int(T, "T"), to_int(B, "B"), to_int(N, "N"), (float)gamma, (float)lambda,
+                                  stream_of(dev)),
+          "hpc_rll_retrace_forward");
+    return out;
+}
+
+// The fused form: heads, scan and critic loss; the gradient flows to q_values only.  Saves action and the workspace (delta).
+struct RetraceLossFn : public ag::Function<RetraceLossFn> {
+    static ag::tensor_list forward(ag::AutogradContext* ctx, const Tensor& q, const Tensor& target, const Tensor& behaviour,
+                                   const Tensor& action, const Tensor& reward, const OptTensor& weights,
+                                   const OptTensor& loss_weight, double gamma, double lambda, std::optional<double> scale) {
+        TORCH_CHECK(q.defined(), "q_values: expected a tensor, got None");
+        TORCH_CHECK(q.dim() == 3 && q.size(0) >= 1, "q_values: expected (T+1,B,N), got ", q.sizes());
+        const int64_t T = q.size(0) - 1, B = q.size(1), N = q.size(2);
+        check_shape(q, "q_values", {T + 1, B, N});
+        check_shape(target, "target_output", {T + 1, B, N});
+        check_shape(behaviour, "behaviour_output", {T, B, N});
+        check_shape(action, "action", {T, B}, at::kLong);
+        check_shape(reward, "reward", {T, B});
+        if (has(weights)) check_shape(*weights, "weights", {T, B});
+        if (has(loss_weight)) check_shape(*loss_weight, "loss_weight", {T, B});
+        retrace_check_n("retrace_loss", N);
+        const at::Device dev = q.device();
+        req(q, "q_values", dev);
+        req(target, "target_output", dev);
+        req(behaviour, "behaviour_output", dev);
+        req(action, "action", dev, at::kLong);
+        req(reward, "reward", dev);
+        if (has(weights)) req(*weights, "weights", dev);
+        if (has(loss_weight)) req(*loss_weight, "loss_weight", dev);
+        c10::DeviceGuard g(dev);
+        const bool empty = T == 0 || B == 0;
+        Tensor loss = new_f32({1}, dev);
+        // no step: the loss is zero and nothing is launched; the outputs are then zeros
+        Tensor q_ret = empty ? at::zeros({T + 1, B}, q.options()) : new_f32({T + 1, B}, dev);
+        Tensor v = empty ? at::zeros({T + 1, B}, q.options()) : new_f32({T + 1, B}, dev);
+        Tensor ws = retrace_workspace(T, B, dev);
+        check(hpc_rll_retrace_loss_forward(fptr(q), fptr(target), fptr(behaviour), iptr(action), fptr(reward), fptr(weights),
+                                           fptr(loss_weight), fmut(loss), fmut(q_ret), fmut(v), fmut(ws), to_int(T, "T"),
+                                           to_int(B, "B"), to_int(N, "N"), (float)gamma, (float)lambda,
+                                           loss_scale(scale, T * B), stream_of(dev)),
+              "hpc_rll_retrace_loss_forward");
+        ctx->save_for_backward({action, ws});
+        ctx->saved_data["N"] = N;
+        ctx->mark_non_differentiable({q_ret, v});
+        return {loss, q_ret, v};
+    }
+    static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
+        ag::tensor_list out(10);
+        if (!ctx->needs_input_grad(0)) return out;
+        const auto saved = ctx->get_saved_variables();
+        const Tensor &action = saved[0], &ws = saved[1];
+        const at::Device dev = action.device();
+        c10::DeviceGuard g(dev);
+        const int64_t T = action.size(0), B = action.size(1), N = ctx->saved_data["N"].toInt();
+        Tensor gl = grad1(grads[0], dev, "grad_loss");
+        if (T == 0 || B == 0) {
+            out[0] = at::zeros({T + 1, B, N}, gl.options());
+            return out;
+        }
+        Tensor grad_q = new_f32({T + 1, B, N}, dev);
+        check(hpc_rll_retrace_loss_backward(fptr(gl), iptr(action), fptr(ws), fmut(grad_q), (int)T, (int)B, (int)N,
+                                            stream_of(dev)),
+              "hpc_rll_retrace_loss_backward");
+        out[0] = grad_q;
+        return out;
+    }
+};
+
 // ==================================================================================================== q n-step TD
 struct QDims { int64_t B, N, nstep; at::Device dev; };
 int64_t check_nstep_reward(const Tensor& reward, int64_t B, const at::Device& dev) {
@@ -1373,6 +1477,18 @@ PYBIND11_MODULE(hpc_rl_utils, m) {
           py::arg("rho_pg_clip_ratio") = 1.0, py::arg("scale") = py::none(),
           "episode-aware V-trace losses (policy, value, entropy) for diagonal-Gaussian policies: mu / sigma / action (T,B,A) "
           "fp32, sigma > 0; differentiable wrt mu_target, sigma_target and value");
+    m.def("retrace", &retrace_targets, py::arg("q_values"), py::arg("v_pred"), py::arg("rewards"), py::arg("actions"),
+          py::arg("weights"), py::arg("ratio"), py::arg("gamma") = 0.9, py::arg("lambda_") = 1.0,
+          "Retrace(lambda) Q targets (T+1,B,1) from given state values (T+1,B,1) and importance ratios (T,B,N); no gradient");
+    m.def("retrace_loss", [](const Tensor& q, const Tensor& target, const Tensor& behaviour, const Tensor& action,
+                             const Tensor& reward, const OptTensor& weights, const OptTensor& loss_weight, double gamma,
+                             double lambda, std::optional<double> scale) {
+        return RetraceLossFn::apply(q, target, behaviour, action, reward, weights, loss_weight, gamma, lambda, scale);
+    }, py::arg("q_values"), py::arg("target_output"), py::arg("behaviour_output"), py::arg("action"), py::arg("reward"),
+          py::arg("weights") = py::none(), py::arg("loss_weight") = py::none(), py::arg("gamma") = 0.9,
+          py::arg("lambda_") = 1.0, py::arg("scale") = py::none(),
+          "Retrace(lambda) critic loss (1,), Q targets (T+1,B) and state values (T+1,B) from q_values and the two policies' "
+          "logits; differentiable wrt q_values");
     m.def("q_nstep_td", [](const Tensor& q, const Tensor& nq, const Tensor& action, const Tensor& naction,
                            const Tensor& reward, const Tensor& done, const OptTensor& weight, double gamma, bool rescale,
                            std::optional<double> scale) {

@@ -284,6 +284,42 @@ int hpc_rll_upgo_masked_forward(const float* target_output, const float* rho, co
                                 void* stream);
 int hpc_rll_upgo_masked_last_config(int* out);
 
+/* Retrace(lambda): off-policy multi-step Q targets for discrete actions and ACER's critic loss (no reference counterpart;
+ * the semantics are DI-engine's compute_q_retraces and acer_value_error).  q_values (T+1,B,N), action (T,B) int64,
+ * reward, weights, loss_weight (T,B) (weights = continuation weight, e.g. 1 - done; NULL = ones, as is loss_weight).
+ * With a_t = action[t,b], qa_t = q_values[t,b,a_t], v_t the state value (t = 0..T) and c_t = lambda*min(1, ratio_t):
+ *   Q_T = v_T,   Q_t = r_t + gamma*w_t*(c_{t+1}*(Q_{t+1} - qa_{t+1}) + v_{t+1}),  the c*(Q - qa) term := 0 at t+1 = T
+ *   scan form: a_t = (gamma*w_t)*c_{t+1},  b_t = fmaf(gamma*w_t, fmaf(-c_{t+1}, qa_{t+1}, v_{t+1}), r_t).
+ * A zero weight gives Q_t = r_t exactly.  1 <= N <= 1024, beyond that HPC_RLL_EUNSUPPORTED.
+ * An action outside [0,N) never addresses memory: it matches no column, so qa = 0, the gathered ratio is 0 (c = 0) in the
+ * drop-in form, the fused form takes 0 for both selected logits, and the sample's gradient row is all zeros.
+ * hpc_rll_retrace_forward -- the drop-in form: v_pred (T+1,B) and ratio (T,B,N) are given, ratio_t = ratio[t,b,a_t].
+ *   Writes q_retraces (T+1,B).  ws: at least 2*T*B floats, layout qa (T*B) | c (T*B).
+ * hpc_rll_retrace_loss_forward -- the fused form: target_output (T+1,B,N) and behaviour_output (T,B,N) are logits,
+ *   pi = softmax(target_output), v_t = sum_n pi_n q_n (written to v_pred (T+1,B)), ratio_t = exp(log pi_t(a_t) - log mu_t(a_t));
+ *   loss (1,) = scale * 0.5 * sum_{t<T,b} lw (Q_t - qa_t)^2 with Q a constant; q_retraces (T+1,B).
+ *   ws: hpc_rll_retrace_workspace_floats(T,B) floats, layout delta (T*B) | qa (T*B) | c (T*B) | partial sums, with
+ *   delta = lw*(qa_t - Q_t)*scale.  T == 0 or B == 0 zeroes loss and launches nothing.
+ * hpc_rll_retrace_loss_backward -- grad_q_values (T+1,B,N), every element written once:
+ *   grad[t,b,n] = g_loss*delta[t,b]*[n == a_t] for t < T, row T is zero.  g_loss is a device scalar (NULL = 1).
+ * hpc_rll_retrace_last_config -- the HPC_RLL_SCAN_CONFIG_INTS ints of hpc_rll_scan_last_config for the Retrace scan of either
+ *   form ({0, -1 ...} before its first launch; HPC_RLL_EINVAL for out == NULL).  [7] (mask mode) holds bit 0 = weights
+ *   given, bit 1 = loss_weight given; [8] is 1 for the drop-in form, 0 for the fused form; [10] is 0 for the drop-in form
+ *   (no loss).  The record is private to this entry point, as hpc_rll_upgo_masked_last_config's is.
+ * Argument errors, before any HIP call: HPC_RLL_EINVAL (null operands, then negative sizes or N <= 0), HPC_RLL_EALIGN (a
+ * pointer off 4-byte alignment, action off 8), then HPC_RLL_EUNSUPPORTED (N > 1024); then empty shapes return 0. */
+int64_t hpc_rll_retrace_workspace_floats(int T, int B);
+int hpc_rll_retrace_forward(const float* q_values, const float* v_pred, const float* rewards, const int64_t* actions,
+                            const float* weights, const float* ratio, float* q_retraces, float* ws, int T, int B, int N,
+                            float gamma, float lambda, void* stream);
+int hpc_rll_retrace_loss_forward(const float* q_values, const float* target_output, const float* behaviour_output,
+                                 const int64_t* action, const float* reward, const float* weights,
+                                 const float* loss_weight, float* loss, float* q_retraces, float* v_pred, float* ws, int T,
+                                 int B, int N, float gamma, float lambda, float scale, void* stream);
+int hpc_rll_retrace_loss_backward(const float* g_loss, const int64_t* action, const float* ws, float* grad_q_values, int T,
+                                  int B, int N, void* stream);
+int hpc_rll_retrace_last_config(int* out);
+
 /* PPO -- replaces PPOForward/Backward (rl_utils/entry.h:158-165, src/rl_utils/ppo.cu:8-111).
  * logits (B,N), action (B,), value_new/old, adv, ret, weight (B,) (weight NULL = ones).
  * out5 = policy_loss, value_loss, entropy_loss, approx_kl, clipfrac.  dual_clip < 1 disables dual clip
