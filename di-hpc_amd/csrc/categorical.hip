@@ -8,7 +8,8 @@
 // Reference design: one 256-thread block per row, 5-6 passes over the N logits through 5 block reductions,
 // and three N-wide gradient buffers written in forward and re-read in backward.  Here:
 //   * a row is owned by a GROUP of G lanes (G = 1..64, a power of two) that keeps the whole row in VGPRs:
-//     logits are read from HBM exactly once per kernel, 16 B per lane when N % 4 == 0;
+//     logits are read from HBM exactly once per kernel, 16 B per lane when N % 4 == 0 (the mapping -- lane slice, (G, VEC, E)
+//     rule, group all-reduce -- is rowgroup.hpp, shared with gaussian.hip and retrace.hip);
 //   * max / sum-exp / sum p*log p are G-lane butterflies (no LDS, no barrier);
 //   * forward emits only per-row scalars (log pi(a), entropy); backward RECOMPUTES the softmax from the
 //     logits instead of loading saved buffers:  forward writes 8 B/row instead of 12*N B/row.
@@ -26,7 +27,10 @@
 #include "hpc_rll_hip.h"
 #include "wave.hpp"
 #include "colscan.hpp"
+#include "heads.hpp"
+#include "hostutil.hpp"
 #include "ppo_op.hpp"
+#include "rowgroup.hpp"
 
 namespace hpc_rll {
 namespace {
@@ -39,10 +43,7 @@ constexpr float kFltMax = 3.402823466e38f;
 // the raw logit on load has the same effect (its probability underflows to exactly 0).  NaN passes through.
 __device__ __forceinline__ float clamp_logit(float x) { return fmaxf(x, -kFltMax); }   // -inf (masked) -> finite
 
-// ---- all-reduce butterflies over aligned groups of G lanes: DPP inside a 16-lane row, ds_bpermute above it.
-template <int CTRL> __device__ __forceinline__ float dpp(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xF, 0xF, true));
-}
+// ---- the ops of the group all-reduces (group_all, rowgroup.hpp)
 struct SumOp { static __device__ __forceinline__ float f(float a, float b) { return a + b; } };
 // max of two values that are never NaN here (finish() removed NaNs): med3(a, b, +inf) is ONE v_med3_f32, whereas fmaxf
 // first canonicalises an operand the compiler cannot prove quiet (every DPP move): 3 instructions per butterfly step -> 2
@@ -52,51 +53,20 @@ struct MaxOp { static __device__ __forceinline__ float f(float a, float b) { ret
 // log of a partition sum relative to the row maximum: s is in [1, N], so the bare v_log_f32 (log2) needs neither the
 // denormal pre-scaling nor the two-word ln2 product of __logf (14 instructions per row -> 2)
 __device__ __forceinline__ float log_sum(float s) { return __builtin_amdgcn_logf(s) * 0.69314718055994530942f; }
-template <int G, class Op> __device__ __forceinline__ float group_all(float x) {
-    if (G >= 2) x = Op::f(x, dpp<0xB1>(x));    // quad_perm [1,0,3,2]
-    if (G >= 4) x = Op::f(x, dpp<0x4E>(x));    // quad_perm [2,3,0,1]
-    if (G >= 8) x = Op::f(x, dpp<0x141>(x));   // row_half_mirror: lane i <-> 7-i
-    if (G >= 16) x = Op::f(x, dpp<0x140>(x));  // row_mirror: lane i <-> 15-i
-    if (G >= 32) x = Op::f(x, __shfl_xor(x, 16, 64));
-    if (G >= 64) x = Op::f(x, __shfl_xor(x, 32, 64));
-    return x;
-}
 
-// Per-lane slice of one row: E pieces of VEC consecutive floats, piece e at column (e*G + gl)*VEC.
-// Two phases.  load() only ISSUES the (nontemporal: logits are read exactly once) loads: every lane loads
-// unconditionally -- padding lanes re-read column 0 -- so there is no divergent branch around a load and all E loads of
-// all R rows of an iteration are in flight before the first use.  finish() then clamps with ONE v_med3_f32 per
-// element: -inf (masked action) becomes the most negative finite float, padding (hi = -FLT_MAX there) becomes that
-// same value, a NaN logit becomes -FLT_MAX exactly as fmaxf(x, -FLT_MAX) made it.  (The first version clamped inside
-// `if (c < N)`, which compiled to a branch and s_waitcnt vmcnt(0) per load plus two v_max per element; in an in-process
-// A/B the two builds time the same to 1 % at every N (tests/tools/cat_ab_probe.py: the kernels are VALU-bound and
-// eight waves per SIMD hid the serialised loads) -- this form is kept for being branch-free and 40 instructions shorter.)
+// The second phase of a row's load (RowSlice::load, rowgroup.hpp, only issues the loads): ONE v_med3_f32 per element.
+// -inf (masked action) becomes the most negative finite float, padding (hi = -FLT_MAX there) becomes that same value, a
+// NaN logit becomes -FLT_MAX exactly as fmaxf(x, -FLT_MAX) made it.
 template <int G, int VEC, int E>
-struct RowSlice {
-    float x[E * VEC];
-    __device__ __forceinline__ void load(const float* __restrict__ row, int N, int gl) {
+__device__ __forceinline__ void finish(RowSlice<G, VEC, E>& r, int N, int gl) {
 #pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const int c = (e * G + gl) * VEC;
-            const int cc = (c < N) ? c : 0;
-            if (VEC == 4) {
-                const vfloat4 t = __builtin_nontemporal_load(reinterpret_cast<const vfloat4*>(row + cc));
-                x[e * 4 + 0] = t.x; x[e * 4 + 1] = t.y; x[e * 4 + 2] = t.z; x[e * 4 + 3] = t.w;
-            } else {
-                x[e] = __builtin_nontemporal_load(row + cc);
-            }
-        }
+    for (int e = 0; e < E; ++e) {
+        const int c = (e * G + gl) * VEC;
+        const float hi = (c < N) ? __builtin_inff() : -kFltMax;   // padding: finite, so that merges stay NaN-free
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) r.x[e * VEC + k] = __builtin_amdgcn_fmed3f(r.x[e * VEC + k], -kFltMax, hi);
     }
-    __device__ __forceinline__ void finish(int N, int gl) {
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const int c = (e * G + gl) * VEC;
-            const float hi = (c < N) ? __builtin_inff() : -kFltMax;   // padding: finite, so that merges stay NaN-free
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) x[e * VEC + k] = __builtin_amdgcn_fmed3f(x[e * VEC + k], -kFltMax, hi);
-        }
-    }
-};
+}
 
 // ---- Softmax statistics of the row held by a G-lane group.
 // Instruction count matters here: at N = 128 the first version issued ~130 VALU instructions per row pair and the
@@ -111,10 +81,10 @@ struct RowSlice {
 //     moves (VALU, no ds_bpermute), leaving the result in the LAST lane of the group, which writes the outputs;
 //   * backward needs p_i in every lane: three all-reduces (max, s, t) instead of four.
 template <int G, class Op> __device__ __forceinline__ float row_all(float x) {   // all-reduce over min(G,16) lanes
-    if (G >= 2) x = Op::f(x, dpp<0xB1>(x));
-    if (G >= 4) x = Op::f(x, dpp<0x4E>(x));
-    if (G >= 8) x = Op::f(x, dpp<0x141>(x));
-    if (G >= 16) x = Op::f(x, dpp<0x140>(x));
+    if (G >= 2) x = Op::f(x, dpp_mov<0xB1>(x));
+    if (G >= 4) x = Op::f(x, dpp_mov<0x4E>(x));
+    if (G >= 8) x = Op::f(x, dpp_mov<0x141>(x));
+    if (G >= 16) x = Op::f(x, dpp_mov<0x140>(x));
     return x;
 }
 // rows 1,3 <- lane 15 of rows 0,2 (CTRL 0x142, mask 0xA); rows 2,3 <- lane 31 (CTRL 0x143, mask 0xC); others keep x
@@ -248,9 +218,6 @@ __device__ __forceinline__ void row_stats(const RowSlice<G, VEC, E>& r, int N, i
     ent = ls - t * inv_sum;
 }
 
-// R rows per group per iteration: R independent load + reduction chains in flight.
-template <int G, int VEC, int E> struct RowsPerIter { static constexpr int value = (E * VEC <= 4) ? 4 : ((E * VEC <= 8) ? 2 : 1); };
-
 // ENT = false (no entropy output: V-trace's behaviour head, PPO's old policy, UPGO): the entropy accumulation, its
 // reduction and its part of the row merges are dead code and disappear (~10 % of the instructions of a VALU-bound kernel)
 template <int G, int VEC, int E, bool ENT>
@@ -259,7 +226,7 @@ __device__ __forceinline__ void categorical_fwd_body(const float* __restrict__ l
                                                      float* __restrict__ logp_out,
                                                      float* __restrict__ ent_out, long rows, int N) {
     constexpr int GPB = 256 / G;  // groups per block
-    constexpr int R = RowsPerIter<G, VEC, E>::value;
+    constexpr int R = RowsPerIter<VEC, E>::value;
     const int gl = threadIdx.x % G;
     const int gi = threadIdx.x / G;
     const bool full = N == G * VEC * E;   // uniform: no padding lanes
@@ -285,7 +252,7 @@ __device__ __forceinline__ void categorical_fwd_body(const float* __restrict__ l
 #pragma unroll
         for (int k = 0; k < R; ++k) {
             const int ai = (a[k] >= 0 && a[k] < (long)N) ? (int)a[k] : -1;
-            r[k].finish(N, gl);
+            finish(r[k], N, gl);
             row_stats_fwd<G, VEC, E>(r[k], N, gl, ai, full, lp[k], h[k]);
         }
         if (gl == G - 1) {
@@ -352,8 +319,8 @@ __global__ __launch_bounds__(256) void ppo_fwd_fused_kernel(const float* __restr
         for (int k = 0; k < R; ++k) {
             const int ai = (a[k] >= 0 && a[k] < (long)N) ? (int)a[k] : -1;
             float lpn, h, lpo, h_unused;
-            rn[k].finish(N, gl);
-            ro[k].finish(N, gl);
+            finish(rn[k], N, gl);
+            finish(ro[k], N, gl);
             row_stats_fwd<G, VEC, E>(rn[k], N, gl, ai, full, lpn, h);
             row_stats_fwd<G, VEC, E>(ro[k], N, gl, ai, full, lpo, h_unused);
             const long row = bb + (long)k * GPB + gi;
@@ -383,7 +350,7 @@ __global__ __launch_bounds__(256) void categorical_bwd_kernel(const float* __res
                                                               const float* __restrict__ g2,
                                                               float* __restrict__ grad, long rows, int N) {
     constexpr int GPB = 256 / G;
-    constexpr int R = RowsPerIter<G, VEC, E>::value;
+    constexpr int R = RowsPerIter<VEC, E>::value;
     const int gl = threadIdx.x % G;
     const int gi = threadIdx.x / G;
     const float u1 = g1 ? g1[0] : 1.f;
@@ -410,7 +377,7 @@ __global__ __launch_bounds__(256) void categorical_bwd_kernel(const float* __res
         for (int k = 0; k < R; ++k) {
             float ex[E * VEC], lse, inv, h;
             const int ai = (a[k] >= 0 && a[k] < (long)N) ? (int)a[k] : -1;
-            r[k].finish(N, gl);
+            finish(r[k], N, gl);
             row_stats<G, VEC, E>(r[k], N, gl, ai, full, ex, lse, inv, h);
             if (w0 + (long)k * GPB >= rows) continue;
             float* __restrict__ out = grad + (off0 + (long)k * GPB * N);
@@ -746,52 +713,42 @@ constexpr int g_blocks_per_cu = 1024;  // cap of the row kernels' grids, in work
 // short-lived workgroups that each write one aligned block beats long-lived ones) lifted the cap -- at the C3 shape every workgroup
 // now takes ONE slice of 32 rows and retires: V-trace 0.755 / 0.784 -> 0.72 / 0.68 ms, UPGO 0.366 / 0.736 -> 0.323 / 0.680
 // (24 -> 64 -> 256 -> 1024 workgroups per CU: backward 0.784, 0.714, 0.686, 0.678 ms)
+constexpr long kRowGridCap = 256L * g_blocks_per_cu;   // 256 CUs x workgroups per CU (above it the workgroups loop)
 namespace {
-inline unsigned grid_for(long rows, int rows_per_block) {
-    long g = (rows + rows_per_block - 1) / rows_per_block;
-    const long cap = 256L * g_blocks_per_cu;  // 256 CUs x workgroups per CU (above it the workgroups loop)
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (unsigned)g;
-}
 
-struct RowCfg { int g, vec, e; };
+// row_cfg with 8 pieces: a row is held by at most 16 lanes (one DPP row) whenever 8 pieces per lane suffice: the per-row
+// reductions are then four DPP steps with no cross-row merge, and their cost is amortised over more elements per lane (the
+// kernels are VALU-bound, not bandwidth-bound, at one float4 per lane).  Longer rows take the whole wave.
+// (8 lanes per row measured no better at N = 64..128, worse at 256)
+constexpr int kRowPieces = 8;
+constexpr int kMaxE = 8;   // row_cfg(...).e > kMaxE means "use the long-row fallback"
 
-inline RowCfg row_cfg(int N, bool can_vec4) {
-    RowCfg c;
-    c.vec = (can_vec4 && (N % 4) == 0) ? 4 : 1;
-    const int pieces = (N + c.vec - 1) / c.vec;
-    // A row is held by at most 16 lanes (one DPP row) whenever 8 pieces per lane suffice: the per-row reductions are
-    // then four DPP steps with no cross-row merge, and their cost is amortised over more elements per lane (the
-    // kernels are VALU-bound, not bandwidth-bound, at one float4 per lane).  Longer rows take the whole wave.
-    const int gmax = pieces <= 16 * 8 ? 16 : 64;   // (8 lanes per row measured no better at N = 64..128, worse at 256)
-    c.g = 1;
-    while (c.g < gmax && c.g < pieces) c.g <<= 1;
-    const int e = (pieces + c.g - 1) / c.g;
-    c.e = 1;
-    while (c.e < e) c.e <<= 1;
-    return c;  // e > 8 means "use the long-row fallback"
+// the (G, VEC, E) of row_cfg(N, ., kRowPieces) below that fallback: N <= 64 lanes x kMaxE pieces x 4 floats
+#define HPC_RLL_CAT_TABLE(CASE, ...)                                                                       \
+    CASE(1, 1, 1, __VA_ARGS__) CASE(2, 1, 1, __VA_ARGS__) CASE(4, 1, 1, __VA_ARGS__) CASE(8, 1, 1, __VA_ARGS__)     \
+    CASE(16, 1, 1, __VA_ARGS__) CASE(16, 1, 2, __VA_ARGS__) CASE(16, 1, 4, __VA_ARGS__) CASE(16, 1, 8, __VA_ARGS__) \
+    CASE(64, 1, 4, __VA_ARGS__) CASE(64, 1, 8, __VA_ARGS__)                                                         \
+    CASE(1, 4, 1, __VA_ARGS__) CASE(2, 4, 1, __VA_ARGS__) CASE(4, 4, 1, __VA_ARGS__) CASE(8, 4, 1, __VA_ARGS__)     \
+    CASE(16, 4, 1, __VA_ARGS__) CASE(16, 4, 2, __VA_ARGS__) CASE(16, 4, 4, __VA_ARGS__) CASE(16, 4, 8, __VA_ARGS__) \
+    CASE(64, 4, 4, __VA_ARGS__) CASE(64, 4, 8, __VA_ARGS__)
+constexpr bool cat_table_complete() {
+    for (int n = 1; n <= 64 * kMaxE * 4; ++n)   // (above it every configuration has e > kMaxE)
+        for (int v4 = 0; v4 < 2; ++v4) {
+            const RowCfg c = row_cfg(n, v4 != 0, kRowPieces);
+            if (c.e <= kMaxE && !(false HPC_RLL_CAT_TABLE(HPC_RLL_ROW_MATCH))) return false;
+        }
+    return true;
 }
+static_assert(cat_table_complete(), "HPC_RLL_CAT_TABLE misses a configuration row_cfg(N, ., kRowPieces) returns with e <= kMaxE");
 
 #define HPC_RLL_ROW_CASE(G_, V_, E_, KERNEL, ...)                                                         \
     if (cfg.g == G_ && cfg.vec == V_ && cfg.e == E_) {                                                    \
         hipLaunchKernelGGL((KERNEL<G_, V_, E_>),                                                           \
-                           dim3(grid_for(rows, (256 / G_) * RowsPerIter<G_, V_, E_>::value)), dim3(256), 0, st, \
+                           dim3(row_grid(rows, (256 / G_) * RowsPerIter<V_, E_>::value, kRowGridCap)), dim3(256), 0, st, \
                            __VA_ARGS__);                                                                  \
         return true;                                                                                      \
     }
-#define HPC_RLL_ROW_DISPATCH(KERNEL, ...)                                                                  \
-    HPC_RLL_ROW_CASE(1, 1, 1, KERNEL, __VA_ARGS__) HPC_RLL_ROW_CASE(2, 1, 1, KERNEL, __VA_ARGS__)          \
-    HPC_RLL_ROW_CASE(4, 1, 1, KERNEL, __VA_ARGS__) HPC_RLL_ROW_CASE(8, 1, 1, KERNEL, __VA_ARGS__)          \
-    HPC_RLL_ROW_CASE(16, 1, 1, KERNEL, __VA_ARGS__) HPC_RLL_ROW_CASE(16, 1, 2, KERNEL, __VA_ARGS__)        \
-    HPC_RLL_ROW_CASE(16, 1, 4, KERNEL, __VA_ARGS__) HPC_RLL_ROW_CASE(16, 1, 8, KERNEL, __VA_ARGS__)        \
-    HPC_RLL_ROW_CASE(64, 1, 4, KERNEL, __VA_ARGS__) HPC_RLL_ROW_CASE(64, 1, 8, KERNEL, __VA_ARGS__)        \
-    HPC_RLL_ROW_CASE(1, 4, 1, KERNEL, __VA_ARGS__) HPC_RLL_ROW_CASE(2, 4, 1, KERNEL, __VA_ARGS__)          \
-    HPC_RLL_ROW_CASE(4, 4, 1, KERNEL, __VA_ARGS__) HPC_RLL_ROW_CASE(8, 4, 1, KERNEL, __VA_ARGS__)          \
-    HPC_RLL_ROW_CASE(16, 4, 1, KERNEL, __VA_ARGS__) HPC_RLL_ROW_CASE(16, 4, 2, KERNEL, __VA_ARGS__)        \
-    HPC_RLL_ROW_CASE(16, 4, 4, KERNEL, __VA_ARGS__) HPC_RLL_ROW_CASE(16, 4, 8, KERNEL, __VA_ARGS__)        \
-    HPC_RLL_ROW_CASE(64, 4, 4, KERNEL, __VA_ARGS__) HPC_RLL_ROW_CASE(64, 4, 8, KERNEL, __VA_ARGS__)        \
-    return false;
+#define HPC_RLL_ROW_DISPATCH(KERNEL, ...) HPC_RLL_CAT_TABLE(HPC_RLL_ROW_CASE, KERNEL, __VA_ARGS__) return false;
 
 bool launch_fwd(const RowCfg& cfg, hipStream_t st, const float* logits, const int64_t* action, float* logp,
                 float* ent, long rows, int N) {
@@ -805,20 +762,15 @@ bool launch_bwd(const RowCfg& cfg, hipStream_t st, const float* logits, const in
     HPC_RLL_ROW_DISPATCH(categorical_bwd_kernel, logits, action, c1, g1, c2, g2, grad, rows, N)
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 #define HPC_RLL_PPO_CASE(G_, V_, E_)                                                                                      \
     if (cfg.g == G_ && cfg.vec == V_ && cfg.e == E_) {                                                                    \
-        const long per = (256 / G_) * 4;                                                                                  \
-        long grid = (rows + per - 1) / per;                                                                               \
-        const long gmax = kFoldMaxGrid;   /* (2048 / 4096 workgroups + a finalize launch: slower, round 4; 1024-thread */ \
-                                          /*  workgroups instead of looping 256-thread ones: 22 -> 27.5 us, round 5)   */ \
-        if (grid > gmax) grid = gmax;                                                                                     \
+        /* cap: 2048 / 4096 workgroups + a finalize launch: slower, round 4; 1024-thread workgroups instead of looping */ \
+        /* 256-thread ones: 22 -> 27.5 us, round 5 */                                                                     \
+        const long grid = row_grid(rows, (256 / G_) * 4, kFoldMaxGrid);                                                   \
         const ScanFold fold = make_fold(st, PpoOp::NACC, scales, out5, grid);                                             \
         hipLaunchKernelGGL((ppo_fwd_fused_kernel<G_, V_, E_>), dim3((unsigned)grid), dim3(256), 0, st, logits_new,        \
                            logits_old, action, op, rows, N, partials, fold);                                              \
-        const hipError_t e = hipGetLastError();                                                                           \
-        *rc = e == hipSuccess ? HPC_RLL_OK : (int)e;                                                                      \
+        *rc = last_error();                                                                                               \
         if (*rc == HPC_RLL_OK && !fold.out) *rc = finalize_sums(partials, (int)grid, PpoOp::NACC, scales, out5, st);      \
         return true;                                                                                                      \
     }
@@ -833,7 +785,7 @@ bool ppo_forward_fused(const float* logits_new, const float* logits_old, const i
                        int N, float* partials, const float* scales, float* out5, hipStream_t st, int* rc) {
     if (rows <= 0 || N <= 0) return false;
     if ((N % 4) != 0 && N <= kSmallMaxN) return false;          // (the small-N forward has its own kernel)
-    const RowCfg cfg = row_cfg(N, al16(logits_new) && al16(logits_old));
+    const RowCfg cfg = row_cfg(N, aligned(logits_new, 16) && aligned(logits_old, 16), kRowPieces);
     if (cfg.e > 2 || cfg.g > 16) return false;                  // registers: two heads x R rows x E pieces per lane
     HPC_RLL_PPO_CASE(1, 4, 1) HPC_RLL_PPO_CASE(2, 4, 1) HPC_RLL_PPO_CASE(4, 4, 1) HPC_RLL_PPO_CASE(8, 4, 1)
     HPC_RLL_PPO_CASE(16, 4, 1) HPC_RLL_PPO_CASE(16, 4, 2)
@@ -848,33 +800,31 @@ int categorical_forward(const float* logits, const int64_t* action, float* logp,
     if (rows < 0 || N <= 0) return HPC_RLL_EINVAL;
     if (rows == 0) return HPC_RLL_OK;
     if (!logits || !action || !logp) return HPC_RLL_EINVAL;
-    if ((N % 4) != 0 && N <= kSmallMaxN && al16(logits)) {
-        hipLaunchKernelGGL(categorical_small_kernel<false>, dim3(grid_for(rows, kSmallRows)), dim3(256),
+    if ((N % 4) != 0 && N <= kSmallMaxN && aligned(logits, 16)) {
+        hipLaunchKernelGGL(categorical_small_kernel<false>, dim3(row_grid(rows, kSmallRows, kRowGridCap)), dim3(256),
                            (size_t)kSmallRows * N * sizeof(float), st, logits,
                            action, logp, ent, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
                            (const float*)nullptr, (float*)nullptr, rows, N);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? HPC_RLL_OK : (int)e;
+        return last_error();
     }
-    const RowCfg cfg = row_cfg(N, al16(logits));
-    if (cfg.e > 8 && cfg.vec == 4 && N <= 16384) {
-        const dim3 grid(grid_for(rows, 1));
+    const RowCfg cfg = row_cfg(N, aligned(logits, 16), kRowPieces);
+    if (cfg.e > kMaxE && cfg.vec == 4 && N <= 16384) {
+        const dim3 grid(row_grid(rows, 1, kRowGridCap));
 #define HPC_RLL_BLOCKROW(E_)                                                                                          \
         hipLaunchKernelGGL((categorical_blockrow_kernel<E_, false>), grid, dim3(256), 0, st, logits, action, logp, ent,   \
                            (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,   \
                            (float*)nullptr, rows, N)
         if (N <= 4096) HPC_RLL_BLOCKROW(4); else if (N <= 8192) HPC_RLL_BLOCKROW(8); else HPC_RLL_BLOCKROW(16);
 #undef HPC_RLL_BLOCKROW
-    } else if (cfg.e > 8 && N <= 16384) {
-        hipLaunchKernelGGL(categorical_ldsrow_kernel<false>, dim3(grid_for(rows, 1)), dim3(256), (size_t)N * sizeof(float),
+    } else if (cfg.e > kMaxE && N <= 16384) {
+        hipLaunchKernelGGL(categorical_ldsrow_kernel<false>, dim3(row_grid(rows, 1, kRowGridCap)), dim3(256), (size_t)N * sizeof(float),
                            st, logits, action, logp, ent, (const float*)nullptr, (const float*)nullptr,
                            (const float*)nullptr, (const float*)nullptr, (float*)nullptr, rows, N);
-    } else if (cfg.e > 8 || !launch_fwd(cfg, st, logits, action, logp, ent, rows, N)) {
-        hipLaunchKernelGGL(categorical_fwd_long_kernel, dim3(grid_for(rows, 4)), dim3(256), 0, st, logits, action,
+    } else if (cfg.e > kMaxE || !launch_fwd(cfg, st, logits, action, logp, ent, rows, N)) {
+        hipLaunchKernelGGL(categorical_fwd_long_kernel, dim3(row_grid(rows, 4, kRowGridCap)), dim3(256), 0, st, logits, action,
                            logp, ent, rows, N);
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? HPC_RLL_OK : (int)e;
+    return last_error();
 }
 
 int categorical_backward(const float* logits, const int64_t* action, const float* c1, const float* g1,
@@ -882,30 +832,28 @@ int categorical_backward(const float* logits, const int64_t* action, const float
     if (rows < 0 || N <= 0) return HPC_RLL_EINVAL;
     if (rows == 0) return HPC_RLL_OK;
     if (!logits || !action || !c1 || !grad) return HPC_RLL_EINVAL;
-    if ((N % 4) != 0 && N <= kSmallMaxN && al16(logits) && al16(grad)) {
-        hipLaunchKernelGGL(categorical_small_kernel<true>, dim3(grid_for(rows, kSmallRows)), dim3(256),
+    if ((N % 4) != 0 && N <= kSmallMaxN && aligned(logits, 16) && aligned(grad, 16)) {
+        hipLaunchKernelGGL(categorical_small_kernel<true>, dim3(row_grid(rows, kSmallRows, kRowGridCap)), dim3(256),
                            (size_t)kSmallRows * N * sizeof(float), st, logits,
                            action, (float*)nullptr, (float*)nullptr, c1, g1, c2, g2, grad, rows, N);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? HPC_RLL_OK : (int)e;
+        return last_error();
     }
-    const RowCfg cfg = row_cfg(N, al16(logits) && al16(grad));
-    if (cfg.e > 8 && cfg.vec == 4 && N <= 16384) {
-        const dim3 grid(grid_for(rows, 1));
+    const RowCfg cfg = row_cfg(N, aligned(logits, 16) && aligned(grad, 16), kRowPieces);
+    if (cfg.e > kMaxE && cfg.vec == 4 && N <= 16384) {
+        const dim3 grid(row_grid(rows, 1, kRowGridCap));
 #define HPC_RLL_BLOCKROW(E_)                                                                                          \
         hipLaunchKernelGGL((categorical_blockrow_kernel<E_, true>), grid, dim3(256), 0, st, logits, action,              \
                            (float*)nullptr, (float*)nullptr, c1, g1, c2, g2, grad, rows, N)
         if (N <= 4096) HPC_RLL_BLOCKROW(4); else if (N <= 8192) HPC_RLL_BLOCKROW(8); else HPC_RLL_BLOCKROW(16);
 #undef HPC_RLL_BLOCKROW
-    } else if (cfg.e > 8 && N <= 16384) {
-        hipLaunchKernelGGL(categorical_ldsrow_kernel<true>, dim3(grid_for(rows, 1)), dim3(256), (size_t)N * sizeof(float),
+    } else if (cfg.e > kMaxE && N <= 16384) {
+        hipLaunchKernelGGL(categorical_ldsrow_kernel<true>, dim3(row_grid(rows, 1, kRowGridCap)), dim3(256), (size_t)N * sizeof(float),
                            st, logits, action, (float*)nullptr, (float*)nullptr, c1, g1, c2, g2, grad, rows, N);
-    } else if (cfg.e > 8 || !launch_bwd(cfg, st, logits, action, c1, g1, c2, g2, grad, rows, N)) {
-        hipLaunchKernelGGL(categorical_bwd_long_kernel, dim3(grid_for(rows, 4)), dim3(256), 0, st, logits, action,
+    } else if (cfg.e > kMaxE || !launch_bwd(cfg, st, logits, action, c1, g1, c2, g2, grad, rows, N)) {
+        hipLaunchKernelGGL(categorical_bwd_long_kernel, dim3(row_grid(rows, 4, kRowGridCap)), dim3(256), 0, st, logits, action,
                            c1, g1, c2, g2, grad, rows, N);
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? HPC_RLL_OK : (int)e;
+    return last_error();
 }
 
 }  // namespace hpc_rll

@@ -56,6 +56,11 @@ namespace hpc_rll {
 // groups own SUB DIFFERENT chunks of the time axis ("virtual waves", as gae.hip's half-wave tiles): SUB x more
 // workgroups and SUB x more steps per barrier.  At the reference's TD-lambda test shape (T=1024, B=64) the 64-column
 // tiling is ONE workgroup walking 8 barriers.
+// `ok` is false for columns past B (the last tile of a row): an Op still issues every load, at row_off, and stores nothing.
+inline __device__ size_t row_off(int t, long col, bool ok, int B, int V) {   // out-of-range columns load the last pack of the row
+    return (size_t)t * B + (ok ? col : (long)B - V);
+}
+
 // Where the last workgroup leaves the NACC sums (x scale[k]); out == nullptr: partials only (the caller finalises).
 // `ticket` is zero before the launch and is left at zero by it.
 struct ScanFold { float* out; unsigned* ticket; float scale[8]; };

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "colscan.hpp"
+#include "hostutil.hpp"
 #include "hpc_rll_hip.h"
 #include "nstep.hpp"
 
@@ -25,11 +26,6 @@ int onehot_scatter(const float* g, const float* buf, const int64_t* action, floa
                    hipStream_t st, int planes = 1);
 
 namespace {
-
-inline int last_error() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? HPC_RLL_OK : (int)e;
-}
 
 // 4 waves (= 4 samples) per workgroup; workgroup partial = sum of its 4 per-sample weighted losses.
 template <class F>

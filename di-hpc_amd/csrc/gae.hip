@@ -29,6 +29,7 @@
 #include <new>
 #include <type_traits>
 
+#include "hostutil.hpp"
 #include "hpc_rll_hip.h"
 #include "wave.hpp"
 
@@ -700,8 +701,6 @@ inline void launch(K kernel, dim3 grid, dim3 block, hipStream_t st, int kind, A.
         hipLaunchKernelGGL(kernel, grid, block, 0, st, args...);
     }
 }
-
-inline bool aligned(const void* p, size_t a) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
 // Widest pack the shape and pointers allow.
 inline int max_vec(int B, std::initializer_list<const void*> ptrs) {

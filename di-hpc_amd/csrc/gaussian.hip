@@ -5,9 +5,10 @@
 //   logp = sum_j [-z_j^2/2 - log sigma_j - log(2 pi)/2],   H = sum_j [1/2 + log(2 pi)/2 + log sigma_j]   (new policy)
 // and from ratio = exp(logp_new - logp_old) onward the arithmetic is PpoOp::apply (ppo_op.hpp), shared with the categorical op.
 //
-// Mapping (categorical.hip is the model): a row of A values is owned by a GROUP of G lanes (G = 1..64, a power of two), lane gl
-// holds E pieces of VEC consecutive floats, piece e at column (e*G + gl)*VEC, of each of the five (B,A) inputs; R rows per group
-// and iteration give R independent load + reduction chains.  A Gaussian row needs no maximum, so one pass forms the two sums.
+// Mapping (rowgroup.hpp): a row of A values is owned by a GROUP of G lanes (G = 1..64, a power of two), lane gl holds a
+// RowSlice -- E pieces of VEC consecutive floats, piece e at column (e*G + gl)*VEC -- of each of the five (B,A) inputs; R rows
+// per group and iteration give R independent load + reduction chains: 5 (forward) or 3 (backward) inputs x R rows x E*VEC
+// floats per lane stay within ~80 VGPRs.  A Gaussian row needs no maximum, so one pass forms the two sums.
 //   * logp_new - logp_old is accumulated as a sum of PER-DIMENSION differences
 //         (z_old - z_new)(z_old + z_new)/2 + (log sigma_old - log sigma_new):
 //     log(2 pi) cancels and no two sums of size ~A are subtracted (torch's fp32 formula loses 7e-5 of max|grad_mu| at A = 376 to
@@ -36,51 +37,21 @@
 #include "hpc_rll_hip.h"
 #include "wave.hpp"
 #include "colscan.hpp"
+#include "heads.hpp"
+#include "hostutil.hpp"
 #include "ppo_op.hpp"
+#include "rowgroup.hpp"
 
 namespace hpc_rll {
 namespace {
 
-constexpr int kGaussMaxA = 1024;                        // 64 lanes x 16 floats per lane and input
+constexpr int kGaussMaxA = kRowTableMaxN;               // 64 lanes x 16 floats per lane and input
 constexpr float kLn2 = 0.69314718055994530942f;
 constexpr float kEntConst = 1.41893853320467274178f;    // 1/2 + log(2 pi)/2: entropy of a unit normal
 constexpr float kHalfLn2Pi = 0.91893853320467274178f;   // log(2 pi)/2
 
-// sum over an aligned group of G lanes, valid in the group's LAST lane (G <= 16: in every lane)
-template <int G> __device__ __forceinline__ float gsum_last(float x) {
-    if (G >= 2) x = dpp_add<0xB1, 0xF>(x);     // quad_perm [1,0,3,2]
-    if (G >= 4) x = dpp_add<0x4E, 0xF>(x);     // quad_perm [2,3,0,1]
-    if (G >= 8) x = dpp_add<0x141, 0xF>(x);    // row_half_mirror
-    if (G >= 16) x = dpp_add<0x140, 0xF>(x);   // row_mirror
-    if (G >= 32) x = dpp_add<0x142, 0xA>(x);   // row_bcast:15 -> rows 1 and 3
-    if (G >= 64) x = dpp_add<0x143, 0xC>(x);   // row_bcast:31 -> row 3
-    return x;
-}
-
 // log sigma as log2: sigma > 0 is the caller's contract, the bare v_log_f32 is within 1 ulp
 __device__ __forceinline__ float log2_(float s) { return __builtin_amdgcn_logf(s); }
-
-// one lane's slice of one row of one (B,A) input; load() only issues the (nontemporal: read once per kernel) loads
-template <int G, int VEC, int E>
-struct GaussSlice {
-    float x[E * VEC];
-    __device__ __forceinline__ void load(const float* __restrict__ row, int A, int gl) {
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const int c = (e * G + gl) * VEC;
-            const int cc = (c < A) ? c : 0;
-            if (VEC == 4) {
-                const vfloat4 t = __builtin_nontemporal_load(reinterpret_cast<const vfloat4*>(row + cc));
-                x[e * 4 + 0] = t.x; x[e * 4 + 1] = t.y; x[e * 4 + 2] = t.z; x[e * 4 + 3] = t.w;
-            } else {
-                x[e] = __builtin_nontemporal_load(row + cc);
-            }
-        }
-    }
-};
-
-// rows per group and iteration: 5 (forward) or 3 (backward) inputs x R rows x E*VEC floats per lane stay within ~80 VGPRs
-template <int VEC, int E> struct GaussRows { static constexpr int value = (E * VEC <= 4) ? 4 : ((E * VEC <= 8) ? 2 : 1); };
 
 template <int G, int VEC, int E>
 __global__ __launch_bounds__(256) void ppo_gauss_fwd_kernel(const float* __restrict__ mu_new,
@@ -90,7 +61,7 @@ __global__ __launch_bounds__(256) void ppo_gauss_fwd_kernel(const float* __restr
                                                             const float* __restrict__ action, const PpoOp op, long rows,
                                                             int A, float* __restrict__ partials, const ScanFold fold) {
     constexpr int GPB = 256 / G;
-    constexpr int R = GaussRows<VEC, E>::value;
+    constexpr int R = RowsPerIter<VEC, E>::value;
     __shared__ float red[PpoOp::NACC * 4];
     const int gl = threadIdx.x % G;
     const int gi = threadIdx.x / G;
@@ -101,7 +72,7 @@ __global__ __launch_bounds__(256) void ppo_gauss_fwd_kernel(const float* __restr
 #pragma unroll
     for (int k = 0; k < PpoOp::NACC; ++k) acc[k] = 0.f;
     for (long bb = (long)blockIdx.x * GPB * R; bb < rows; bb += stride) {
-        GaussSlice<G, VEC, E> mn[R], sn[R], mo[R], so[R], ac[R];
+        RowSlice<G, VEC, E> mn[R], sn[R], mo[R], so[R], ac[R];
         PpoOp::In in[R];
 #pragma unroll
         for (int k = 0; k < R; ++k) {
@@ -132,8 +103,8 @@ __global__ __launch_bounds__(256) void ppo_gauss_fwd_kernel(const float* __restr
                     d += ok ? t : 0.f;
                     h += ok ? ln : 0.f;
                 }
-            d = gsum_last<G>(d);
-            h = gsum_last<G>(h);
+            d = group_sum_last<G>(d);
+            h = group_sum_last<G>(h);
             const long row = bb + (long)k * GPB + gi;
             if (gl == G - 1 && row < rows) op.apply(row, in[k], d, fmaf(h, kLn2, hconst), 0.f, acc);
         }
@@ -162,7 +133,7 @@ __global__ __launch_bounds__(256) void ppo_gauss_bwd_kernel(const float* __restr
                                                             float* __restrict__ grad_sigma, float* __restrict__ grad_value,
                                                             long rows, int A) {
     constexpr int GPB = 256 / G;
-    constexpr int R = GaussRows<VEC, E>::value;
+    constexpr int R = RowsPerIter<VEC, E>::value;
     const int gl = threadIdx.x % G;
     const int gi = threadIdx.x / G;
     const float u1 = g_p ? g_p[0] : 1.f;
@@ -170,7 +141,7 @@ __global__ __launch_bounds__(256) void ppo_gauss_bwd_kernel(const float* __restr
     const float u3 = (grad_value && g_v) ? g_v[0] : 1.f;
     const long stride = (long)gridDim.x * GPB * R;
     for (long bb = (long)blockIdx.x * GPB * R; bb < rows; bb += stride) {
-        GaussSlice<G, VEC, E> mn[R], sn[R], ac[R];
+        RowSlice<G, VEC, E> mn[R], sn[R], ac[R];
         float k1[R], k2[R], k3[R];
 #pragma unroll
         for (int k = 0; k < R; ++k) {
@@ -239,14 +210,14 @@ __global__ __launch_bounds__(256) void gauss_heads_fwd_kernel(const float* __res
                                                               float* __restrict__ ent, float* __restrict__ logp_b,
                                                               const bool log_ratio, long rows, int A) {
     constexpr int GPB = 256 / G;
-    constexpr int R = GaussRows<VEC, E>::value;
+    constexpr int R = RowsPerIter<VEC, E>::value;
     const int gl = threadIdx.x % G;
     const int gi = threadIdx.x / G;
     const bool full = A == G * VEC * E;   // uniform: no padding lanes
     const float hconst = (float)A * kEntConst, lconst = (float)A * kHalfLn2Pi;
     const long stride = (long)gridDim.x * GPB * R;
     for (long bb = (long)blockIdx.x * GPB * R; bb < rows; bb += stride) {
-        GaussSlice<G, VEC, E> mt[R], st[R], mb[R], sb[R], ac[R];
+        RowSlice<G, VEC, E> mt[R], st[R], mb[R], sb[R], ac[R];
 #pragma unroll
         for (int k = 0; k < R; ++k) {
             long row = bb + (long)k * GPB + gi;
@@ -280,9 +251,9 @@ __global__ __launch_bounds__(256) void gauss_heads_fwd_kernel(const float* __res
                     h += ok ? lt : 0.f;
                     d += ok ? t : 0.f;
                 }
-            q = gsum_last<G>(q);
-            h = gsum_last<G>(h);
-            d = gsum_last<G>(d);
+            q = group_sum_last<G>(q);
+            h = group_sum_last<G>(h);
+            d = group_sum_last<G>(d);
             const long row = bb + (long)k * GPB + gi;
             if (gl == G - 1 && row < rows) {
                 const float lp = fmaf(-0.5f, q, -fmaf(h, kLn2, lconst));
@@ -294,46 +265,22 @@ __global__ __launch_bounds__(256) void gauss_heads_fwd_kernel(const float* __res
     }
 }
 
-struct GaussCfg { int g, vec, e; };
-
-// The group is one DPP row (16 lanes) or less while 4 pieces per lane suffice (A <= 256 with 16-byte loads, A <= 64 without);
-// longer rows take the whole wave with up to 4 (16-byte) or 16 (4-byte) pieces per lane: A <= 1024 either way.
-inline GaussCfg gauss_cfg(int A, bool can_vec4) {
-    GaussCfg c;
-    c.vec = (can_vec4 && (A % 4) == 0) ? 4 : 1;
-    const int pieces = (A + c.vec - 1) / c.vec;
-    const int gmax = pieces <= 16 * 4 ? 16 : 64;
-    c.g = 1;
-    while (c.g < gmax && c.g < pieces) c.g <<= 1;
-    const int e = (pieces + c.g - 1) / c.g;
-    c.e = 1;
-    while (c.e < e) c.e <<= 1;
-    return c;
-}
-
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-inline int last_error() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? HPC_RLL_OK : (int)e;
-}
-
-// every (G, VEC, E) gauss_cfg can return for 1 <= A <= kGaussMaxA
-#define HPC_RLL_GAUSS_DISPATCH(CASE)                                                                                  \
-    CASE(1, 4, 1) CASE(2, 4, 1) CASE(4, 4, 1) CASE(8, 4, 1) CASE(16, 4, 1) CASE(16, 4, 2) CASE(16, 4, 4)             \
-    CASE(64, 4, 2) CASE(64, 4, 4)                                                                                     \
-    CASE(1, 1, 1) CASE(2, 1, 1) CASE(4, 1, 1) CASE(8, 1, 1) CASE(16, 1, 1) CASE(16, 1, 2) CASE(16, 1, 4)             \
-    CASE(64, 1, 2) CASE(64, 1, 4) CASE(64, 1, 8) CASE(64, 1, 16)
+// row_cfg with 4 pieces: the group is one DPP row (16 lanes) or less while 4 pieces per lane suffice (A <= 256 with 16-byte
+// loads, A <= 64 without); longer rows take the whole wave with up to 4 (16-byte) or 16 (4-byte) pieces per lane: A <= 1024
+// either way.  4, not categorical.hip's 8: eight 16-byte pieces of five inputs would be 160 VGPRs for one row.
+constexpr int kRowPieces = 4;
+constexpr long kRowGridCap = 256L * 1024;   // short-lived workgroups, as the categorical row kernels; above it they loop
 
 int gauss_forward(const float* mu_new, const float* sigma_new, const float* mu_old, const float* sigma_old,
                   const float* action, const PpoOp& op, long rows, int A, float* partials, const float* scales, float* out5,
                   hipStream_t st) {
-    const GaussCfg cfg = gauss_cfg(A, al16(mu_new) && al16(sigma_new) && al16(mu_old) && al16(sigma_old) && al16(action));
+    const bool v4 = aligned(mu_new, 16) && aligned(sigma_new, 16) && aligned(mu_old, 16) && aligned(sigma_old, 16) &&
+                    aligned(action, 16);
+    const RowCfg cfg = row_cfg(A, v4, kRowPieces);
 #define HPC_RLL_GAUSS_FWD_CASE(G_, V_, E_)                                                                            \
     if (cfg.g == G_ && cfg.vec == V_ && cfg.e == E_) {                                                                \
-        const long per = (256 / G_) * GaussRows<V_, E_>::value;                                                       \
-        long grid = (rows + per - 1) / per;                                                                           \
-        if (grid > kFoldMaxGrid) grid = kFoldMaxGrid;   /* the workgroups loop; the sums are folded inside the launch */ \
+        /* at most kFoldMaxGrid workgroups, which loop: the sums are folded inside the launch */                       \
+        const long grid = row_grid(rows, (256 / G_) * RowsPerIter<V_, E_>::value, kFoldMaxGrid);                      \
         const ScanFold fold = make_fold(st, PpoOp::NACC, scales, out5, grid);                                         \
         hipLaunchKernelGGL((ppo_gauss_fwd_kernel<G_, V_, E_>), dim3((unsigned)grid), dim3(256), 0, st, mu_new,         \
                            sigma_new, mu_old, sigma_old, action, op, rows, A, partials, fold);                        \
@@ -341,7 +288,7 @@ int gauss_forward(const float* mu_new, const float* sigma_new, const float* mu_o
         if (rc || fold.out) return rc;                                                                                \
         return finalize_sums(partials, (int)grid, PpoOp::NACC, scales, out5, st);                                     \
     }
-    HPC_RLL_GAUSS_DISPATCH(HPC_RLL_GAUSS_FWD_CASE)
+    HPC_RLL_ROW4_TABLE(HPC_RLL_GAUSS_FWD_CASE)
 #undef HPC_RLL_GAUSS_FWD_CASE
     return HPC_RLL_EUNSUPPORTED;
 }
@@ -349,17 +296,17 @@ int gauss_forward(const float* mu_new, const float* sigma_new, const float* mu_o
 int gauss_backward(const float* mu_new, const float* sigma_new, const float* action, const float* c1, const float* c2,
                    const float* c3, const float* g_p, const float* g_e, const float* g_v, float* grad_mu, float* grad_sigma,
                    float* grad_value, long rows, int A, hipStream_t st) {
-    const GaussCfg cfg = gauss_cfg(A, al16(mu_new) && al16(sigma_new) && al16(action) && al16(grad_mu) && al16(grad_sigma));
+    const bool v4 = aligned(mu_new, 16) && aligned(sigma_new, 16) && aligned(action, 16) && aligned(grad_mu, 16) &&
+                    aligned(grad_sigma, 16);   // (a gradient that is not asked for restricts nothing)
+    const RowCfg cfg = row_cfg(A, v4, kRowPieces);
 #define HPC_RLL_GAUSS_BWD_CASE(G_, V_, E_)                                                                            \
     if (cfg.g == G_ && cfg.vec == V_ && cfg.e == E_) {                                                                \
-        const long per = (256 / G_) * GaussRows<V_, E_>::value;                                                       \
-        long grid = (rows + per - 1) / per;                                                                           \
-        if (grid > 256L * 1024) grid = 256L * 1024;     /* short-lived workgroups, as the categorical row kernels */  \
-        hipLaunchKernelGGL((ppo_gauss_bwd_kernel<G_, V_, E_>), dim3((unsigned)grid), dim3(256), 0, st, mu_new,         \
+        const unsigned grid = row_grid(rows, (256 / G_) * RowsPerIter<V_, E_>::value, kRowGridCap);                   \
+        hipLaunchKernelGGL((ppo_gauss_bwd_kernel<G_, V_, E_>), dim3(grid), dim3(256), 0, st, mu_new,                   \
                            sigma_new, action, c1, c2, c3, g_p, g_e, g_v, grad_mu, grad_sigma, grad_value, rows, A);   \
         return last_error();                                                                                          \
     }
-    HPC_RLL_GAUSS_DISPATCH(HPC_RLL_GAUSS_BWD_CASE)
+    HPC_RLL_ROW4_TABLE(HPC_RLL_GAUSS_BWD_CASE)
 #undef HPC_RLL_GAUSS_BWD_CASE
     return HPC_RLL_EUNSUPPORTED;
 }
@@ -374,20 +321,19 @@ int gaussian_heads_forward(const float* mu_t, const float* sigma_t, const float*
     if (rows > 0 && (!mu_t || !sigma_t || !mu_b || !sigma_b || !action || !logp_t || !ent || !logp_b)) return HPC_RLL_EINVAL;
     for (const void* p : {(const void*)mu_t, (const void*)sigma_t, (const void*)mu_b, (const void*)sigma_b,
                           (const void*)action, (const void*)logp_t, (const void*)ent, (const void*)logp_b})
-        if (reinterpret_cast<uintptr_t>(p) & 3) return HPC_RLL_EALIGN;
+        if (!aligned(p, 4)) return HPC_RLL_EALIGN;
     if (A > kGaussMaxA) return HPC_RLL_EUNSUPPORTED;
     if (rows == 0) return HPC_RLL_OK;
-    const GaussCfg cfg = gauss_cfg(A, al16(mu_t) && al16(sigma_t) && al16(mu_b) && al16(sigma_b) && al16(action));
+    const bool v4 = aligned(mu_t, 16) && aligned(sigma_t, 16) && aligned(mu_b, 16) && aligned(sigma_b, 16) && aligned(action, 16);
+    const RowCfg cfg = row_cfg(A, v4, kRowPieces);
 #define HPC_RLL_GAUSS_HEADS_CASE(G_, V_, E_)                                                                          \
     if (cfg.g == G_ && cfg.vec == V_ && cfg.e == E_) {                                                                \
-        const long per = (256 / G_) * GaussRows<V_, E_>::value;                                                       \
-        long grid = (rows + per - 1) / per;                                                                           \
-        if (grid > 256L * 1024) grid = 256L * 1024;     /* short-lived workgroups, as gauss_backward; they loop */    \
-        hipLaunchKernelGGL((gauss_heads_fwd_kernel<G_, V_, E_>), dim3((unsigned)grid), dim3(256), 0, st, mu_t,         \
+        const unsigned grid = row_grid(rows, (256 / G_) * RowsPerIter<V_, E_>::value, kRowGridCap);                   \
+        hipLaunchKernelGGL((gauss_heads_fwd_kernel<G_, V_, E_>), dim3(grid), dim3(256), 0, st, mu_t,                   \
                            sigma_t, mu_b, sigma_b, action, logp_t, ent, logp_b, log_ratio, rows, A);                  \
         return last_error();                                                                                          \
     }
-    HPC_RLL_GAUSS_DISPATCH(HPC_RLL_GAUSS_HEADS_CASE)
+    HPC_RLL_ROW4_TABLE(HPC_RLL_GAUSS_HEADS_CASE)
 #undef HPC_RLL_GAUSS_HEADS_CASE
     return HPC_RLL_EUNSUPPORTED;
 }
@@ -461,7 +407,7 @@ extern "C" int hpc_rll_vtrace_continuous_backward(const float* g_pg, const float
     for (const void* p : {(const void*)g_pg, (const void*)g_value, (const void*)g_ent, (const void*)mu_target,
                           (const void*)sigma_target, (const void*)action, (const void*)ws, (const void*)grad_mu,
                           (const void*)grad_sigma, (const void*)grad_value})
-        if (reinterpret_cast<uintptr_t>(p) & 3) return HPC_RLL_EALIGN;
+        if (!aligned(p, 4)) return HPC_RLL_EALIGN;
     if (A > kGaussMaxA) return HPC_RLL_EUNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     if (grad_value) {

@@ -23,6 +23,7 @@
 #include <atomic>
 
 #include "gemm_f32.hpp"
+#include "hostutil.hpp"
 #include "hpc_rll_hip.h"
 #include "wave.hpp"
 
@@ -37,11 +38,6 @@ constexpr int g_cell_rows_wgs = 512;  // workgroups of the row-walking backward 
 namespace {
 
 constexpr float kLnEps = 1e-5f;
-
-inline int last_error() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? HPC_RLL_OK : (int)e;
-}
 
 // Sum K values over the 256 threads of the workgroup; every thread gets the totals.  `lds` holds >= K*4 floats.
 template <int K>

@@ -15,6 +15,7 @@
 #include <initializer_list>
 #include <type_traits>
 
+#include "hostutil.hpp"
 #include "wave.hpp"
 
 namespace hpc_rll {
@@ -42,8 +43,6 @@ template <int V> struct MaskRow<V, 1> {
     }
     __device__ __forceinline__ float keep(int k) const { return 1.f - x.v[k]; }
 };
-
-inline bool aligned(const void* p, size_t a) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
 template <int N> using I = std::integral_constant<int, N>;
 

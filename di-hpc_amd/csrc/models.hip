@@ -4,16 +4,12 @@
 // product with a butterfly instead of a 32-thread block reduce; guarded, 64-bit indexing).
 #include <hip/hip_runtime.h>
 
+#include "hostutil.hpp"
 #include "hpc_rll_hip.h"
 #include "wave.hpp"
 
 namespace hpc_rll {
 namespace {
-
-inline int last_error() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? HPC_RLL_OK : (int)e;
-}
 
 // ae[b,:] += (sample_entity[b] == entity_num[b]) ? 0 : key_embeddings[b, sample_entity[b], :]
 __global__ __launch_bounds__(256) void update_ae_kernel(const float* __restrict__ key, const int64_t* __restrict__ sample,

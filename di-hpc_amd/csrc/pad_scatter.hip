@@ -31,17 +31,13 @@
 #include <cstring>
 #include <vector>
 
+#include "hostutil.hpp"
 #include "hpc_rll_hip.h"
 #include "wave.hpp"
 #include "pad_group.hpp"
 
 namespace hpc_rll {
 namespace {
-
-inline int last_error() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? HPC_RLL_OK : (int)e;
-}
 
 // ------------------------------------------------------------------------------------------------ pad
 // table[i] = {src pointer, d0, d1, d2}; output (n, m0, m1, m2); one thread per output element.

@@ -12,8 +12,8 @@
 // Three stages, every array read or written once:
 //   * per (t,b) streams v (T+1,B), qa (T,B), c (T,B).  The drop-in form (v_pred and a (T,B,N) ratio are given) gathers qa and c
 //     with one thread per sample (retrace_gather_kernel).  The fused form computes them from the logits in
-//     retrace_heads_fwd_kernel on gaussian.hip's mapping: a row of N values is owned by a group of G lanes, lane gl holds E
-//     pieces of VEC floats of the q_values, target_output and behaviour_output rows; pi = softmax(target), v = sum pi q,
+//     retrace_heads_fwd_kernel on the mapping of rowgroup.hpp: a row of N values is owned by a group of G lanes, lane gl
+//     holds a RowSlice of the q_values, target_output and behaviour_output rows (3 inputs x R rows x E*VEC floats per lane); pi = softmax(target), v = sum pi q,
 //     log ratio = ((x_a - max_t) - (y_a - max_b)) - (log s_t - log s_b) in ONE expression from the two rows' statistics (no
 //     two separately rounded log-probabilities).  Rows of N % 4 != 0 (or a base off 16 bytes) take 4-byte loads.  Rows of
 //     t = T have no behaviour row and no action: they re-read behaviour row (T-1,b) (every load stays unconditional and in
@@ -34,20 +34,16 @@
 #include <hip/hip_runtime.h>
 
 #include "colscan.hpp"
+#include "hostutil.hpp"
 #include "hpc_rll_hip.h"
+#include "rowgroup.hpp"
 #include "wave.hpp"
 
 namespace hpc_rll {
 namespace {
 
-constexpr int kRetraceMaxN = 1024;   // 64 lanes x 16 floats per lane and input
+constexpr int kRetraceMaxN = kRowTableMaxN;   // 64 lanes x 16 floats per lane and input
 constexpr float kFltMax = 3.402823466e38f;
-
-inline bool aligned(const void* p, size_t a) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-inline int last_error() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? HPC_RLL_OK : (int)e;
-}
 
 // ================================================================================================
 // drop-in form: qa = q_values[t,b,a], c = lambda*min(1, ratio[t,b,a]) as coalesced (T,B) streams
@@ -66,51 +62,15 @@ __global__ __launch_bounds__(256) void retrace_gather_kernel(const float* __rest
 }
 
 // ================================================================================================
-// fused form: the heads.  all-reduces over aligned groups of G lanes: DPP inside a 16-lane row, a lane exchange above it
-// (categorical.hip's group_all)
+// fused form: the heads, with the ops of their group all-reduces (group_all, rowgroup.hpp)
 // ================================================================================================
-template <int CTRL> __device__ __forceinline__ float dpp_mov(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xF, 0xF, true));
-}
 struct AddOp { static __device__ __forceinline__ float f(float a, float b) { return a + b; } };
 struct MaxOp { static __device__ __forceinline__ float f(float a, float b) { return fmaxf(a, b); } };
-template <int G, class Op> __device__ __forceinline__ float group_all(float x) {
-    if (G >= 2) x = Op::f(x, dpp_mov<0xB1>(x));    // quad_perm [1,0,3,2]
-    if (G >= 4) x = Op::f(x, dpp_mov<0x4E>(x));    // quad_perm [2,3,0,1]
-    if (G >= 8) x = Op::f(x, dpp_mov<0x141>(x));   // row_half_mirror
-    if (G >= 16) x = Op::f(x, dpp_mov<0x140>(x));  // row_mirror
-    if (G >= 32) x = Op::f(x, __shfl_xor(x, 16, 64));
-    if (G >= 64) x = Op::f(x, __shfl_xor(x, 32, 64));
-    return x;
-}
-
-// one lane's slice of one row of one (rows,N) input; load() only issues the (nontemporal: read once) loads, padding lanes
-// re-read column 0
-template <int G, int VEC, int E>
-struct HeadSlice {
-    float x[E * VEC];
-    __device__ __forceinline__ void load(const float* __restrict__ row, int N, int gl) {
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const int c = (e * G + gl) * VEC;
-            const int cc = (c < N) ? c : 0;
-            if (VEC == 4) {
-                const vfloat4 t = __builtin_nontemporal_load(reinterpret_cast<const vfloat4*>(row + cc));
-                x[e * 4 + 0] = t.x; x[e * 4 + 1] = t.y; x[e * 4 + 2] = t.z; x[e * 4 + 3] = t.w;
-            } else {
-                x[e] = __builtin_nontemporal_load(row + cc);
-            }
-        }
-    }
-};
-
-// rows per group and iteration: 3 inputs x R rows x E*VEC floats per lane
-template <int VEC, int E> struct HeadRows { static constexpr int value = (E * VEC <= 4) ? 4 : ((E * VEC <= 8) ? 2 : 1); };
 
 // maximum, partition sum (relative to the maximum) and the selected logit of a row, in every lane of the group; -inf logits
 // (masked actions) are clamped to the most negative finite float as categorical.hip does, padding counts as that value
 template <int G, int VEC, int E>
-__device__ __forceinline__ void softmax_stats(const HeadSlice<G, VEC, E>& r, int N, int gl, int ai, float (&ex)[E * VEC],
+__device__ __forceinline__ void softmax_stats(const RowSlice<G, VEC, E>& r, int N, int gl, int ai, float (&ex)[E * VEC],
                                               float& m, float& s, float& xa) {
     float mx = -kFltMax;
 #pragma unroll
@@ -145,12 +105,12 @@ __global__ __launch_bounds__(256) void retrace_heads_fwd_kernel(const float* __r
                                                                 float* __restrict__ qa_out, float* __restrict__ c_out,
                                                                 long rows, long TB, long B, int N, float lambda) {
     constexpr int GPB = 256 / G;
-    constexpr int R = HeadRows<VEC, E>::value;
+    constexpr int R = RowsPerIter<VEC, E>::value;
     const int gl = threadIdx.x % G;
     const int gi = threadIdx.x / G;
     const long stride = (long)gridDim.x * GPB * R;
     for (long bb = (long)blockIdx.x * GPB * R; bb < rows; bb += stride) {
-        HeadSlice<G, VEC, E> qs[R], ts[R], bs[R];
+        RowSlice<G, VEC, E> qs[R], ts[R], bs[R];
         long a[R];
 #pragma unroll
         for (int k = 0; k < R; ++k) {
@@ -195,44 +155,21 @@ __global__ __launch_bounds__(256) void retrace_heads_fwd_kernel(const float* __r
     }
 }
 
-struct HeadCfg { int g, vec, e; };
-
-// gaussian.hip's rule: the group is one DPP row (16 lanes) or less while 4 pieces per lane suffice (N <= 256 with 16-byte
-// loads, N <= 64 without); longer rows take the whole wave with up to 4 (16-byte) or 16 (4-byte) pieces per lane.
-inline HeadCfg head_cfg(int N, bool can_vec4) {
-    HeadCfg c;
-    c.vec = (can_vec4 && (N % 4) == 0) ? 4 : 1;
-    const int pieces = (N + c.vec - 1) / c.vec;
-    const int gmax = pieces <= 16 * 4 ? 16 : 64;
-    c.g = 1;
-    while (c.g < gmax && c.g < pieces) c.g <<= 1;
-    const int e = (pieces + c.g - 1) / c.g;
-    c.e = 1;
-    while (c.e < e) c.e <<= 1;
-    return c;
-}
-
-// every (G, VEC, E) head_cfg can return for 1 <= N <= kRetraceMaxN
-#define HPC_RLL_RETRACE_DISPATCH(CASE)                                                                                \
-    CASE(1, 4, 1) CASE(2, 4, 1) CASE(4, 4, 1) CASE(8, 4, 1) CASE(16, 4, 1) CASE(16, 4, 2) CASE(16, 4, 4)             \
-    CASE(64, 4, 2) CASE(64, 4, 4)                                                                                     \
-    CASE(1, 1, 1) CASE(2, 1, 1) CASE(4, 1, 1) CASE(8, 1, 1) CASE(16, 1, 1) CASE(16, 1, 2) CASE(16, 1, 4)             \
-    CASE(64, 1, 2) CASE(64, 1, 4) CASE(64, 1, 8) CASE(64, 1, 16)
-
 int retrace_heads(const float* q, const float* tgt, const float* beh, const int64_t* action, float* v_out, float* qa_out,
                   float* c_out, int T, int B, int N, float lambda, hipStream_t st) {
     const long rows = ((long)T + 1) * B, TB = (long)T * B;
-    const HeadCfg cfg = head_cfg(N, aligned(q, 16) && aligned(tgt, 16) && aligned(beh, 16));
+    // row_cfg with 4 pieces, as gaussian.hip (at 8, the three slices and two sets of exponentials of ONE row would be 160
+    // VGPRs): one DPP row (16 lanes) or less while 4 pieces per lane suffice (N <= 256 with 16-byte loads, N <= 64 without)
+    const RowCfg cfg = row_cfg(N, aligned(q, 16) && aligned(tgt, 16) && aligned(beh, 16), 4);
 #define HPC_RLL_RETRACE_HEADS_CASE(G_, V_, E_)                                                                        \
     if (cfg.g == G_ && cfg.vec == V_ && cfg.e == E_) {                                                                \
-        const long per = (256 / G_) * HeadRows<V_, E_>::value;                                                        \
-        long grid = (rows + per - 1) / per;                                                                           \
-        if (grid > 256L * 1024) grid = 256L * 1024;     /* short-lived workgroups, as gaussian.hip's heads; they loop */ \
-        hipLaunchKernelGGL((retrace_heads_fwd_kernel<G_, V_, E_>), dim3((unsigned)grid), dim3(256), 0, st, q, tgt, beh, \
+        /* short-lived workgroups, as gaussian.hip's heads; above the cap they loop */                                \
+        const unsigned grid = row_grid(rows, (256 / G_) * RowsPerIter<V_, E_>::value, 256L * 1024);                   \
+        hipLaunchKernelGGL((retrace_heads_fwd_kernel<G_, V_, E_>), dim3(grid), dim3(256), 0, st, q, tgt, beh,          \
                            action, v_out, qa_out, c_out, rows, TB, (long)B, N, lambda);                               \
         return last_error();                                                                                          \
     }
-    HPC_RLL_RETRACE_DISPATCH(HPC_RLL_RETRACE_HEADS_CASE)
+    HPC_RLL_ROW4_TABLE(HPC_RLL_RETRACE_HEADS_CASE)
 #undef HPC_RLL_RETRACE_HEADS_CASE
     return HPC_RLL_EUNSUPPORTED;
 }
@@ -240,10 +177,6 @@ int retrace_heads(const float* q, const float* tgt, const float* beh, const int6
 // ================================================================================================
 // the scan.  HW / HLW: weights / loss_weight given (the null case loads nothing); LOSS: the fused form (loss and delta)
 // ================================================================================================
-inline __device__ size_t row_off(int t, long col, bool ok, int B, int V) {   // out-of-range columns load the last pack of the row
-    return (size_t)t * B + (ok ? col : (long)B - V);
-}
-
 template <bool HW, bool HLW, bool LOSS>
 struct RetraceOp {
     static constexpr int NACC = LOSS ? 1 : 0, DIAG_OP = kScanOpRetrace, DIAG_MT = 0, DIAG_MM = (HW ? 1 : 0) | (HLW ? 2 : 0),

@@ -13,29 +13,15 @@
 #include <cstdlib>
 
 #include "colscan.hpp"
+#include "heads.hpp"
+#include "hostutil.hpp"
 #include "hpc_rll_hip.h"
 #include "nstep.hpp"
 #include "ppo_op.hpp"
 #include "stream_write.hpp"
 
 namespace hpc_rll {
-
-int categorical_forward(const float* logits, const int64_t* action, float* logp, float* ent, long rows, int N,
-                        hipStream_t st);
-int categorical_backward(const float* logits, const int64_t* action, const float* c1, const float* g1,
-                         const float* c2, const float* g2, float* grad, long rows, int N, hipStream_t st);
-struct PpoOp;
-// categorical.hip: both policy heads and the per-sample loss in ONE launch; false = shape not covered (caller runs three)
-bool ppo_forward_fused(const float* logits_new, const float* logits_old, const int64_t* action, const PpoOp& op, long rows,
-                       int N, float* partials, const float* scales, float* out5, hipStream_t st, int* rc);
-extern int g_ppo_fused;
-
 namespace {
-
-inline int last_error() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? HPC_RLL_OK : (int)e;
-}
 
 // Generic "one lane per sample + NACC sums" kernel: workgroups of NT threads walk the samples grid-stride.
 // Round 5: the launch keeps its grid within the fold's 512 workgroups (colscan.hpp) -- batches above 131072 samples take

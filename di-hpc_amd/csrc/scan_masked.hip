@@ -30,23 +30,12 @@
 #include <hip/hip_runtime.h>
 
 #include "colscan.hpp"
+#include "heads.hpp"
 #include "hpc_rll_hip.h"
 #include "masks.hpp"
 
 namespace hpc_rll {
-
-int categorical_forward(const float* logits, const int64_t* action, float* logp, float* ent, long rows, int N,
-                        hipStream_t st);
-int gaussian_heads_forward(const float* mu_t, const float* sigma_t, const float* mu_b, const float* sigma_b,
-                           const float* action, float* logp_t, float* ent, float* logp_b, bool log_ratio, long rows, int A,
-                           hipStream_t st);
-
 namespace {
-
-// Out-of-range columns load the last pack of the row (as MaskedGaeFwdOp) and store nothing.
-inline __device__ size_t row_off(int t, long col, bool ok, int B, int V) {
-    return (size_t)t * B + (ok ? col : (long)B - V);
-}
 
 // ================================================================================================
 // TD(lambda) with masks: loss = 0.5 * scale * sum w (G_t - V_t)^2 ;  grad_buf_t = -w (G_t - V_t) * scale

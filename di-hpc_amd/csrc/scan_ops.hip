@@ -16,6 +16,8 @@
 #include <unordered_map>
 
 #include "colscan.hpp"
+#include "heads.hpp"
+#include "hostutil.hpp"
 #include "hpc_rll_hip.h"
 
 namespace hpc_rll {
@@ -31,14 +33,7 @@ int g_scan_fold = 1;   // fold the loss finalisation into the launch (tune key 2
 constexpr int kStreamTickets = 1024, kGraphTickets = 3072;
 __device__ unsigned g_scan_tickets[kStreamTickets + kGraphTickets];
 
-int categorical_forward(const float* logits, const int64_t* action, float* logp, float* ent, long rows, int N,
-                        hipStream_t st);
-int categorical_backward(const float* logits, const int64_t* action, const float* c1, const float* g1,
-                         const float* c2, const float* g2, float* grad, long rows, int N, hipStream_t st);
-
 namespace {
-
-inline bool al8(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
 struct TicketPool {
     std::mutex mu;
@@ -322,7 +317,7 @@ extern "C" int hpc_rll_td_lambda_forward(const float* value, const float* reward
     hipStream_t st = (hipStream_t)stream;
     if (T == 0 || B == 0) return (int)hipMemsetAsync(loss, 0, sizeof(float), st);
     if (!value || !reward || !grad_buf || !partials || (weight_mode != 0 && !weight)) return HPC_RLL_EINVAL;
-    const bool v2 = (B % 2 == 0) && al8(value) && al8(reward) && al8(weight) && al8(grad_buf);
+    const bool v2 = (B % 2 == 0) && aligned(value, 8) && aligned(reward, 8) && aligned(weight, 8) && aligned(grad_buf, 8);
     const ScanCfg c = scan_cfg(T, B, v2, true);
     // oracle arithmetic (origin/td.py:239-243): discounts = gamma*lambda ; (gammas - discounts) * V_{t+1}
     const float disc = gamma * lambda;

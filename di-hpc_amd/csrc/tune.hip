@@ -6,11 +6,12 @@
 // some shapes under the default rule -- so that tests and measurement tools can force either one and compare them on the
 // same inputs, plus the one deployment switch (key 3).  Keys keep their historical numbers; retired keys answer
 // HPC_RLL_EINVAL.  Process-global, not synchronised: set them before launching work, from one thread (tests do).
+#include "heads.hpp"   // g_ppo_fused
 #include "hpc_rll_hip.h"
 
 namespace hpc_rll {
 extern int g_lstm_persist, g_lstm_wave, g_gemm_tile256, g_scatter_lds_fwd, g_scatter_npb, g_scan_fold, g_split_algo, g_sample_batch,
-    g_gemm_dma, g_lstm_block, g_lstm_block_skew, g_pad_wave, g_lstm_mid, g_onehot_fill_mb, g_ppo_fused, g_lstm_mid_bwd, g_onehot_qpw,
+    g_gemm_dma, g_lstm_block, g_lstm_block_skew, g_pad_wave, g_lstm_mid, g_onehot_fill_mb, g_lstm_mid_bwd, g_onehot_qpw,
     g_scatter_build, g_scatter_bwd_xcd, g_scatter_bwd_tile;
 namespace {
 struct TuneKey {
