@@ -3,7 +3,7 @@
 // Two layers in one module:
 //   * the reference's L2 functions `XxxForward(inputs, outputs, scalars...)` / `XxxBackward(inputs, outputs)`
 //     (declared in include/hpc/rll/cuda/rl_utils/entry.h:10-165) -- validated, launched on torch's current stream;
-//   * fused autograd ops (`gae`, `td_lambda`, `vtrace`, `upgo`, `upgo_masked`, `ppo`, `ppo_continuous`, `vtrace_continuous`, `retrace_loss`, `q_nstep_td`, `dist_nstep_td`, `iqn_nstep_td`,
+//   * fused autograd ops (`gae`, `td_lambda`, `vtrace`, `upgo`, `upgo_masked`, `ppo`, `ppo_continuous`, `vtrace_continuous`, `retrace_loss`, `acer_policy_loss`, `q_nstep_td`, `dist_nstep_td`, `iqn_nstep_td`,
 //     `qrdqn_nstep_td`) -- torch::autograd::Function nodes that allocate outputs, launch and register backward in ONE
 //     pybind call; these are what hpc_rll.rl_utils.* modules use.
 // Host-only C++: every kernel lives behind the C ABI of libhpc_rll_hip.so (include/hpc_rll_hip.h).
@@ -925,6 +925,106 @@ struct RetraceLossFn : public ag::Function<RetraceLossFn> {
     }
 };
 
+// ========================================================================================================== ACER
+// ACER's actor loss (hpc_rll_acer_*; DI-engine's acer_policy_error and acer_trust_region_update).  T is action's; the tensors
+// retrace_loss takes and returns may keep their T+1 rows (only the first T are read).  Shapes and dtypes are checked before
+// the device so that a wrong argument is named even on host tensors.
+int64_t acer_check_rows(const Tensor& t, const char* name, int64_t T, std::initializer_list<int64_t> rest) {
+    TORCH_CHECK(t.defined(), name, ": expected a tensor, got None");
+    TORCH_CHECK(t.scalar_type() == at::kFloat, name, ": dtype ", t.scalar_type(), ", expected ", at::kFloat);
+    std::vector<int64_t> want{T};
+    want.insert(want.end(), rest.begin(), rest.end());
+    bool ok = t.dim() == (int64_t)want.size() && (t.size(0) == T || t.size(0) == T + 1);
+    for (size_t i = 1; ok && i < want.size(); ++i) ok = t.size(i) == want[i];
+    TORCH_CHECK(ok, name, ": shape ", t.sizes(), ", expected ", at::IntArrayRef(want), " or one more leading row");
+    return t.size(0);
+}
+
+// The gradient flows to target_output only.  Saves the unit gradient (T,B,N), which is allocated only when it is wanted.
+struct AcerPolicyFn : public ag::Function<AcerPolicyFn> {
+    static ag::tensor_list forward(ag::AutogradContext* ctx, const Tensor& target, const Tensor& behaviour, const Tensor& q,
+                                   const Tensor& q_ret, const Tensor& v_pred, const Tensor& action, const OptTensor& weights,
+                                   const OptTensor& avg, double c_clip, double entropy_weight, double trust_region,
+                                   std::optional<double> scale, bool want_grad) {
+        TORCH_CHECK(action.defined(), "action: expected a tensor, got None");
+        TORCH_CHECK(action.dim() == 2, "action: expected (T,B), got ", action.sizes());
+        TORCH_CHECK(target.defined(), "target_output: expected a tensor, got None");
+        TORCH_CHECK(target.dim() == 3, "target_output: expected (T,B,N) or (T+1,B,N), got ", target.sizes());
+        const int64_t T = action.size(0), B = action.size(1), N = target.size(2);
+        check_shape(action, "action", {T, B}, at::kLong);
+        const int64_t target_rows = acer_check_rows(target, "target_output", T, {B, N});
+        check_shape(behaviour, "behaviour_output", {T, B, N});
+        acer_check_rows(q, "q_values", T, {B, N});
+        acer_check_rows(q_ret, "q_retraces", T, {B});
+        acer_check_rows(v_pred, "v_pred", T, {B});
+        if (has(weights)) check_shape(*weights, "weights", {T, B});
+        if (has(avg)) check_shape(*avg, "avg_output", {T, B, N});
+        retrace_check_n("acer_policy_loss", N);
+        const at::Device dev = target.device();
+        req(target, "target_output", dev);
+        req(behaviour, "behaviour_output", dev);
+        req(q, "q_values", dev);
+        req(q_ret, "q_retraces", dev);
+        req(v_pred, "v_pred", dev);
+        req(action, "action", dev, at::kLong);
+        if (has(weights)) req(*weights, "weights", dev);
+        if (has(avg)) req(*avg, "avg_output", dev);
+        c10::DeviceGuard g(dev);
+        Tensor out4 = new_f32({4}, dev);
+        Tensor unit = (want_grad && T * B > 0) ? new_f32({T, B, N}, dev) : undef();
+        Tensor ws = new_f32({hpc_rll_acer_policy_workspace_floats(to_int(T, "T"), to_int(B, "B"))}, dev);
+        check(hpc_rll_acer_policy_forward(fptr(target), fptr(behaviour), fptr(avg), fptr(q), fptr(q_ret), fptr(v_pred),
+                                          iptr(action), fptr(weights), fmut(out4), fmut(unit), fmut(ws), to_int(T, "T"),
+                                          to_int(B, "B"), to_int(N, "N"), (float)c_clip, (float)entropy_weight,
+                                          (float)trust_region, loss_scale(scale, T * B), stream_of(dev)),
+              "hpc_rll_acer_policy_forward");
+        ctx->save_for_backward({unit});
+        ctx->saved_data["dims"] = std::vector<int64_t>{T, B, N, target_rows};
+        Tensor loss = alias_of(out4, 0, 1), actor = alias_of(out4, 1, 1), bc = alias_of(out4, 2, 1), ent = alias_of(out4, 3, 1);
+        ctx->mark_non_differentiable({actor, bc, ent});
+        return {loss, actor, bc, ent};
+    }
+    static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
+        ag::tensor_list out(13);
+        if (!ctx->needs_input_grad(0)) return out;
+        const Tensor unit = ctx->get_saved_variables()[0];
+        const std::vector<int64_t> d = ctx->saved_data["dims"].toIntVector();
+        const int64_t T = d[0], B = d[1], N = d[2], rows = d[3];
+        const at::Device dev = grads[0].device();
+        c10::DeviceGuard g(dev);
+        Tensor gl = grad1(grads[0], dev, "grad_loss");
+        if (T == 0 || B == 0) {
+            out[0] = at::zeros({rows, B, N}, gl.options());
+            return out;
+        }
+        TORCH_CHECK(unit.defined(), "acer_policy_loss: the gradient was not stored by the forward");
+        Tensor grad = new_f32({rows, B, N}, dev);
+        check(hpc_rll_acer_policy_backward(fptr(gl), fptr(unit), fmut(grad), (int)T, (int)B, (int)N, (int)rows, stream_of(dev)),
+              "hpc_rll_acer_policy_backward");
+        out[0] = grad;
+        return out;
+    }
+};
+
+// DI-engine's acer_trust_region_update for one gradient: both (..., N), avg_logit holds log-probabilities; no gradient.
+Tensor acer_trust_region(const Tensor& grad, const Tensor& avg_logit, double trust_region) {
+    TORCH_CHECK(grad.defined(), "actor_gradients: expected a tensor, got None");
+    TORCH_CHECK(grad.dim() >= 1, "actor_gradients: expected (..., N), got ", grad.sizes());
+    check_shape(grad, "actor_gradients", grad.sizes());
+    check_shape(avg_logit, "avg_logit", grad.sizes());
+    const int64_t N = grad.size(-1);
+    retrace_check_n("acer_trust_region_update", N);
+    const at::Device dev = grad.device();
+    req(grad, "actor_gradients", dev);
+    req(avg_logit, "avg_logit", dev);
+    c10::DeviceGuard g(dev);
+    Tensor out = at::empty_like(grad);
+    check(hpc_rll_acer_trust_region(fptr(grad), fptr(avg_logit), fmut(out), grad.numel() / N, to_int(N, "N"),
+                                    (float)trust_region, stream_of(dev)),
+          "hpc_rll_acer_trust_region");
+    return out;
+}
+
 // ==================================================================================================== q n-step TD
 struct QDims { int64_t B, N, nstep; at::Device dev; };
 int64_t check_nstep_reward(const Tensor& reward, int64_t B, const at::Device& dev) {
@@ -1489,6 +1589,23 @@ PYBIND11_MODULE(hpc_rl_utils, m) {
           py::arg("lambda_") = 1.0, py::arg("scale") = py::none(),
           "Retrace(lambda) critic loss (1,), Q targets (T+1,B) and state values (T+1,B) from q_values and the two policies' "
           "logits; differentiable wrt q_values");
+    m.def("acer_policy_loss", [](const Tensor& target, const Tensor& behaviour, const Tensor& q, const Tensor& q_ret,
+                                 const Tensor& v_pred, const Tensor& action, const OptTensor& weights, const OptTensor& avg,
+                                 double c_clip, double entropy_weight, double trust_region, std::optional<double> scale) {
+        // (inside the node grad mode is off: whether the unit gradient is worth storing is decided here)
+        const bool want_grad = at::GradMode::is_enabled() && target.defined() && target.requires_grad();
+        return AcerPolicyFn::apply(target, behaviour, q, q_ret, v_pred, action, weights, avg, c_clip, entropy_weight,
+                                   trust_region, scale, want_grad);
+    }, py::arg("target_output"), py::arg("behaviour_output"), py::arg("q_values"), py::arg("q_retraces"), py::arg("v_pred"),
+          py::arg("action"), py::arg("weights") = py::none(), py::arg("avg_output") = py::none(),
+          py::arg("c_clip_ratio") = 10.0, py::arg("entropy_weight") = 0.0, py::arg("trust_region_value") = 1.0,
+          py::arg("scale") = py::none(),
+          "ACER actor loss (1,) and its three detached monitors (actor, bias correction, entropy) from the two policies' "
+          "logits, the average policy's (optional: the trust region), q_values and Retrace's q_retraces / v_pred; "
+          "differentiable wrt target_output");
+    m.def("acer_trust_region_update", &acer_trust_region, py::arg("actor_gradient"), py::arg("avg_logit"),
+          py::arg("trust_region_value"),
+          "g - max(0, (sum k g - trust_region_value) / sum k^2) k with k = exp(avg_logit), per row of N; no gradient");
     m.def("q_nstep_td", [](const Tensor& q, const Tensor& nq, const Tensor& action, const Tensor& naction,
                            const Tensor& reward, const Tensor& done, const OptTensor& weight, double gamma, bool rescale,
                            std::optional<double> scale) {

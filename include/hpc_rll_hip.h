@@ -320,6 +320,45 @@ int hpc_rll_retrace_loss_backward(const float* g_loss, const int64_t* action, co
                                   int B, int N, void* stream);
 int hpc_rll_retrace_last_config(int* out);
 
+/* ACER's actor loss for discrete actions (no reference counterpart; the semantics restate DI-engine's acer_policy_error and
+ * acer_trust_region_update).  target_output, behaviour_output, avg_output, q_values: T*B rows of N logits / values;
+ * q_retraces, v_pred (T*B); action (T,B) int64; weights (T,B) (NULL = ones: nothing is multiplied); avg_output NULL = no
+ * trust region.  Only the first T*B rows of an operand are read, so the (T+1,B,..) tensors hpc_rll_retrace_loss_forward
+ * takes and returns pass as they are.  Per sample, with l = log_softmax(x), pi = exp l, d_n = l_n - log_softmax(y)_n,
+ * k = softmax(u), A^ret = q_retraces - v_pred, A_n = q_n - v_pred, c = c_clip_ratio, beta = entropy_weight:
+ *   ca = min(c, exp d_a) A^ret,   bc_n = max(0, 1 - c exp(-d_n)) pi_n A_n        (constants of the loss)
+ *   La = ca l_a,  Lb = sum_n bc_n l_n,  H = -sum_n pi_n l_n
+ *   out4 = { -scale sum w (La + Lb + beta H),  scale sum w La,  scale sum w Lb,  scale sum w H }
+ *   g_n = -([n = a] ca + bc_n - beta pi_n (l_n + 1)),  s = max(0, (sum k g - trust_region_value) / sum k^2) (0 without
+ *   avg_output),  z = g - s k,  unit_grad[t,b,n] = w scale (z_n - pi_n sum_m z_m).
+ * A target logit of -inf is clamped to the most negative finite float; its column has pi_n = 0, adds exactly 0 to every
+ * sum and gets gradient 0 (the sums select on pi_n > 0).  An action outside [0,N) never addresses memory: ca = 0.
+ * hpc_rll_acer_policy_forward -- one launch.  unit_grad (T,B,N) may be NULL: the gradient is then not formed.
+ *   ws: hpc_rll_acer_policy_workspace_floats(T,B) floats (the partial sums).  T == 0 or B == 0 zeroes out4, launches nothing.
+ * hpc_rll_acer_policy_backward -- grad_target_output (target_rows,B,N) = g_loss * unit_grad for the first T rows, zero in
+ *   row T when target_rows == T+1 (target_rows is T or T+1); g_loss is a device scalar (required); one streaming launch.
+ * hpc_rll_acer_trust_region -- the projection alone, for DI-engine's acer_trust_region_update: actor_gradient, avg_logit
+ *   (log-probabilities), out (rows,N):  out = g - max(0, (sum k g - trust_region_value) / sum k^2) k,  k = exp(avg_logit).
+ * hpc_rll_acer_last_config -- out[HPC_RLL_ACER_CONFIG_INTS] = { launches of the two forward entry points so far, G, VEC, E
+ *   (lanes per row, floats per load, loads per lane and row), R (rows per group and iteration), flags (bit 0 weights given,
+ *   bit 1 avg_output given, bit 2 unit_grad stored), workgroups, 1 if the latest launch was hpc_rll_acer_trust_region };
+ *   {0, -1 ...} before the first launch; HPC_RLL_EINVAL for out == NULL.
+ * 1 <= N <= 1024, beyond that HPC_RLL_EUNSUPPORTED.  Argument errors, before any HIP call: HPC_RLL_EINVAL (null operands,
+ * then negative sizes, N <= 0 or a bad target_rows), HPC_RLL_EALIGN (a pointer off 4-byte alignment, action off 8), then
+ * HPC_RLL_EUNSUPPORTED (N > 1024); then empty shapes return 0. */
+#define HPC_RLL_ACER_CONFIG_INTS (8)
+int64_t hpc_rll_acer_policy_workspace_floats(int T, int B);
+int hpc_rll_acer_policy_forward(const float* target_output, const float* behaviour_output, const float* avg_output,
+                                const float* q_values, const float* q_retraces, const float* v_pred, const int64_t* action,
+                                const float* weights, float* out4, float* unit_grad, float* ws, int T, int B, int N,
+                                float c_clip_ratio, float entropy_weight, float trust_region_value, float scale,
+                                void* stream);
+int hpc_rll_acer_policy_backward(const float* g_loss, const float* unit_grad, float* grad_target_output, int T, int B,
+                                 int N, int target_rows, void* stream);
+int hpc_rll_acer_trust_region(const float* actor_gradient, const float* avg_logit, float* out, int64_t rows, int N,
+                              float trust_region_value, void* stream);
+int hpc_rll_acer_last_config(int* out);
+
 /* PPO -- replaces PPOForward/Backward (rl_utils/entry.h:158-165, src/rl_utils/ppo.cu:8-111).
  * logits (B,N), action (B,), value_new/old, adv, ret, weight (B,) (weight NULL = ones).
  * out5 = policy_loss, value_loss, entropy_loss, approx_kl, clipfrac.  dual_clip < 1 disables dual clip
