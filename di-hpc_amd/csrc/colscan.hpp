@@ -287,9 +287,12 @@ inline unsigned scan_grid(const ScanCfg& c, int B) {
 // range hpc_rll_scan_last_config accepts are part of ABI 6 and stay as they are; hpc_rll_upgo_masked_last_config is the
 // only reader of this slot.
 // Retrace (retrace.hip) has the next private slot, read only by hpc_rll_retrace_last_config.
+// COMA (coma.hip) has the one after it, read only by hpc_rll_coma_last_config (through scan_read_record).
 constexpr int kScanOpUpgoMasked = HPC_RLL_SCAN_OPS;
 constexpr int kScanOpRetrace = HPC_RLL_SCAN_OPS + 1;
-constexpr int kScanRecords = HPC_RLL_SCAN_OPS + 2;
+constexpr int kScanOpComa = HPC_RLL_SCAN_OPS + 2;
+constexpr int kScanRecords = HPC_RLL_SCAN_OPS + 3;
+int scan_read_record(int slot, int* out);   // the HPC_RLL_SCAN_CONFIG_INTS ints of a slot ({0, -1 ...} before its first launch)
 void scan_note_launch(int op, int v, int lc, int nw, int sub, int ntl, int mask_dtype, int mask_mode, int nvf, long grid);
 void scan_note_final(int op, int how);
 template <class Op, class = void> struct ScanDiagMask { static constexpr int mt = 0, mm = 0, nvf = 0; };

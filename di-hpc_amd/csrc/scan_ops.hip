@@ -266,9 +266,9 @@ ScanFold make_fold(hipStream_t st, int nacc, const float* scale, float* out, lon
 }
 
 // The scan family's dispatch record (colscan.hpp: scan_note_launch / scan_note_final write it, hpc_rll_scan_last_config
-// reads it).  Plain ints of the host process, like the GAE record of gae.hip: not synchronised.  The last two
-// slots (kScanOpUpgoMasked, kScanOpRetrace) are internal: only hpc_rll_upgo_masked_last_config and
-// hpc_rll_retrace_last_config read them.
+// reads it).  Plain ints of the host process, like the GAE record of gae.hip: not synchronised.  The last three
+// slots (kScanOpUpgoMasked, kScanOpRetrace, kScanOpComa) are internal: only hpc_rll_upgo_masked_last_config,
+// hpc_rll_retrace_last_config and hpc_rll_coma_last_config (coma.hip, through scan_read_record) read them.
 namespace {
 int g_scan_last[kScanRecords][HPC_RLL_SCAN_CONFIG_INTS];   // [op][0] = launches so far; zero at load
 int read_scan_record(int slot, int* out) {
@@ -277,6 +277,10 @@ int read_scan_record(int slot, int* out) {
     for (int i = 1; i < HPC_RLL_SCAN_CONFIG_INTS; ++i) out[i] = r[0] ? r[i] : -1;   // no launch yet: count 0, the rest -1
     return HPC_RLL_OK;
 }
+}
+int scan_read_record(int slot, int* out) {
+    if (slot < 0 || slot >= kScanRecords || !out) return HPC_RLL_EINVAL;
+    return read_scan_record(slot, out);
 }
 void scan_note_launch(int op, int v, int lc, int nw, int sub, int ntl, int mask_dtype, int mask_mode, int nvf, long grid) {
     if (op < 0 || op >= kScanRecords) return;

@@ -3,7 +3,7 @@
 // Two layers in one module:
 //   * the reference's L2 functions `XxxForward(inputs, outputs, scalars...)` / `XxxBackward(inputs, outputs)`
 //     (declared in include/hpc/rll/cuda/rl_utils/entry.h:10-165) -- validated, launched on torch's current stream;
-//   * fused autograd ops (`gae`, `td_lambda`, `vtrace`, `upgo`, `upgo_masked`, `ppo`, `ppo_continuous`, `vtrace_continuous`, `retrace_loss`, `acer_policy_loss`, `q_nstep_td`, `dist_nstep_td`, `iqn_nstep_td`,
+//   * fused autograd ops (`gae`, `td_lambda`, `vtrace`, `upgo`, `upgo_masked`, `ppo`, `ppo_continuous`, `vtrace_continuous`, `retrace_loss`, `acer_policy_loss`, `coma`, `q_nstep_td`, `dist_nstep_td`, `iqn_nstep_td`,
 //     `qrdqn_nstep_td`) -- torch::autograd::Function nodes that allocate outputs, launch and register backward in ONE
 //     pybind call; these are what hpc_rll.rl_utils.* modules use.
 // Host-only C++: every kernel lives behind the C ABI of libhpc_rll_hip.so (include/hpc_rll_hip.h).
@@ -1025,6 +1025,77 @@ Tensor acer_trust_region(const Tensor& grad, const Tensor& avg_logit, double tru
     return out;
 }
 
+// ========================================================================================================== COMA
+// The counterfactual multi-agent actor-critic loss (hpc_rll_coma_*; DI-engine's coma_error).  Shapes and dtypes are checked
+// before the device so that a wrong argument is named even on host tensors.  The gradient flows to logit and q_value; each
+// is formed only when its input needs it.  Saves logit, action, weight and the one workspace.
+struct ComaFn : public ag::Function<ComaFn> {
+    static ag::tensor_list forward(ag::AutogradContext* ctx, const Tensor& logit, const Tensor& action, const Tensor& q,
+                                   const Tensor& target_q, const Tensor& reward, const OptTensor& weight,
+                                   const OptTensor& done, double gamma, double lambda, std::optional<double> scale_pe,
+                                   std::optional<double> scale_q) {
+        TORCH_CHECK(logit.defined(), "logit: expected a tensor, got None");
+        TORCH_CHECK(logit.dim() == 4, "logit: expected (T,B,A,N), got ", logit.sizes());
+        const int64_t T = logit.size(0), B = logit.size(1), A = logit.size(2), N = logit.size(3);
+        check_shape(logit, "logit", {T, B, A, N});
+        check_shape(action, "action", {T, B, A}, at::kLong);
+        check_shape(q, "q_value", {T, B, A, N});
+        check_shape(target_q, "target_q_value", {T, B, A, N});
+        check_shape(reward, "reward", {T, B});
+        if (has(weight)) check_shape(*weight, "weight", {T, B, A});
+        int code = HPC_RLL_MASK_U8;
+        if (has(done)) {
+            code = mask_code(*done, "done");
+            TORCH_CHECK(done->sizes() == reward.sizes(), "done: shape ", done->sizes(), ", expected ", reward.sizes(),
+                        " (the shape of reward)");
+        }
+        retrace_check_n("coma", N);
+        TORCH_CHECK(B * A <= INT32_MAX, "coma: B*A = ", B * A, " does not fit the kernels' 32-bit column count");
+        const at::Device dev = logit.device();
+        req(logit, "logit", dev);
+        req(action, "action", dev, at::kLong);
+        req(q, "q_value", dev);
+        req(target_q, "target_q_value", dev);
+        req(reward, "reward", dev);
+        if (has(weight)) req(*weight, "weight", dev);
+        if (has(done)) req(*done, "done", dev, done->scalar_type());
+        c10::DeviceGuard g(dev);
+        Tensor losses = new_f32({3}, dev);
+        const int64_t nws = hpc_rll_coma_workspace_floats(to_int(T, "T"), to_int(B, "B"), to_int(A, "A"));
+        TORCH_CHECK(nws >= 0, "coma: the workspace size of (T,B,A) = (", T, ",", B, ",", A, ") is not representable");
+        Tensor ws = new_f32({nws}, dev);
+        const float s_pe = loss_scale(scale_pe, T * B * A), s_q = loss_scale(scale_q, (T - 1) * B * A);
+        check(hpc_rll_coma_forward(fptr(logit), iptr(action), fptr(q), fptr(target_q), fptr(reward), fptr(weight),
+                                   has(done) ? vptr(*done) : nullptr, code, fmut(losses), fmut(ws), (int)T, (int)B, (int)A,
+                                   to_int(N, "N"), (float)gamma, (float)lambda, s_pe, s_q, stream_of(dev)),
+              "hpc_rll_coma_forward");
+        ctx->save_for_backward({logit, action, has(weight) ? *weight : undef(), ws});
+        ctx->saved_data["scale_pe"] = (double)s_pe;
+        return {alias_of(losses, 0, 1), alias_of(losses, 1, 1), alias_of(losses, 2, 1)};
+    }
+    static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
+        ag::tensor_list out(11);
+        const bool need_l = ctx->needs_input_grad(0), need_q = ctx->needs_input_grad(2);
+        if (!(need_l || need_q)) return out;
+        const auto saved = ctx->get_saved_variables();
+        const Tensor &logit = saved[0], &action = saved[1], &weight = saved[2], &ws = saved[3];
+        const at::Device dev = logit.device();
+        c10::DeviceGuard g(dev);
+        const int64_t T = logit.size(0), B = logit.size(1), A = logit.size(2), N = logit.size(3);
+        Tensor g_p = grad1(grads[0], dev, "grad_policy_loss"), g_q = grad1(grads[1], dev, "grad_q_value_loss"),
+               g_e = grad1(grads[2], dev, "grad_entropy_loss");
+        Tensor grad_logit = need_l ? at::empty_like(logit) : undef();
+        Tensor grad_q = need_q ? at::empty_like(logit) : undef();
+        check(hpc_rll_coma_backward(fptr(g_p), fptr(g_q), fptr(g_e), fptr(logit), iptr(action), fptr(weight), fptr(ws),
+                                    fmut(grad_logit), fmut(grad_q), (int)T, (int)B, (int)A, (int)N,
+                                    (float)ctx->saved_data["scale_pe"].toDouble(), stream_of(dev)),
+              "hpc_rll_coma_backward");
+        out[0] = grad_logit;
+        out[2] = grad_q;
+        return out;
+    }
+};
+
 // ==================================================================================================== q n-step TD
 struct QDims { int64_t B, N, nstep; at::Device dev; };
 int64_t check_nstep_reward(const Tensor& reward, int64_t B, const at::Device& dev) {
@@ -1606,6 +1677,17 @@ PYBIND11_MODULE(hpc_rl_utils, m) {
     m.def("acer_trust_region_update", &acer_trust_region, py::arg("actor_gradient"), py::arg("avg_logit"),
           py::arg("trust_region_value"),
           "g - max(0, (sum k g - trust_region_value) / sum k^2) k with k = exp(avg_logit), per row of N; no gradient");
+    m.def("coma", [](const Tensor& logit, const Tensor& action, const Tensor& q, const Tensor& target_q, const Tensor& reward,
+                     const OptTensor& weight, const OptTensor& done, double gamma, double lambda,
+                     std::optional<std::pair<double, double>> scales) {
+        std::optional<double> s_pe, s_q;
+        if (scales.has_value()) { s_pe = scales->first; s_q = scales->second; }
+        return ComaFn::apply(logit, action, q, target_q, reward, weight, done, gamma, lambda, s_pe, s_q);
+    }, py::arg("logit"), py::arg("action"), py::arg("q_value"), py::arg("target_q_value"), py::arg("reward"),
+          py::arg("weight") = py::none(), py::arg("done") = py::none(), py::arg("gamma") = 0.99, py::arg("lambda_") = 0.8,
+          py::arg("scales") = py::none(),
+          "COMA losses (policy, q_value, entropy; (1,) each) from (T,B,A,N) logits and action values, (T,B,A) int64 actions "
+          "and (T,B) rewards; differentiable wrt logit and q_value; scales = (scale_pe, scale_q) for a sharded caller");
     m.def("q_nstep_td", [](const Tensor& q, const Tensor& nq, const Tensor& action, const Tensor& naction,
                            const Tensor& reward, const Tensor& done, const OptTensor& weight, double gamma, bool rescale,
                            std::optional<double> scale) {

@@ -359,6 +359,52 @@ int hpc_rll_acer_trust_region(const float* actor_gradient, const float* avg_logi
                               float trust_region_value, void* stream);
 int hpc_rll_acer_last_config(int* out);
 
+/* COMA: the counterfactual multi-agent actor-critic loss (no reference counterpart; the semantics restate DI-engine's
+ * coma_error, Foerster et al. 2018).  logit, q_value, target_q_value (T,B,A,N); action (T,B,A) int64; reward (T,B), row T-1
+ * is not read; weight (T,B,A) (NULL = ones: nothing is multiplied); done (T,B) of `mask_dtype` (HPC_RLL_MASK_U8 /
+ * HPC_RLL_MASK_F32; NULL = no episode ends), k = 1 - done.  Per row (t,b,i) with x the logit row, q / q' the value rows,
+ * a the action, l = log_softmax(x), pi = exp l, H = -sum_n pi_n l_n, qa = q[a], tqa = q'[a], adv = qa - sum_n pi_n q_n
+ * (a constant of the loss), and per column (b,i), disc = gamma*lambda (in fp32), rest = gamma - disc:
+ *   R_{T-2} = r[T-2,b] + k_{T-2} gamma tqa_{T-1},   R_t = r[t,b] + k_t (disc R_{t+1} + rest tqa_{t+1})   (a constant of the loss)
+ *   scan form over T-1 steps and B*A columns: s_{T-1} = tqa_{T-1}, a_t = k_t disc, b_t = fmaf(k_t rest, tqa_{t+1}, r_t)
+ *   loss[3] = { -scale_pe sum w l_a adv,   scale_q sum_{t<T-1} w (R_t - qa_t)^2,   scale_pe sum w H }
+ *   grad_logit[n]   = -g_policy w adv scale_pe ([n = a] - pi_n) + g_entropy w scale_pe (-pi_n (l_n + H))
+ *   grad_q_value[n] =  g_q 2 w (qa - R) scale_q [n = a]  for t < T-1;  row T-1 is zero.
+ * A logit of -inf is clamped to the most negative finite float: its column has pi_n = 0, adds exactly 0 to H and to the
+ * baseline and gets gradient 0.  An action outside [0,N) never addresses memory: qa = tqa = 0, the row's policy term and
+ * q term are dropped and neither gradient row has a one-hot part; the entropy is unaffected.  1 <= N <= 1024, beyond that
+ * HPC_RLL_EUNSUPPORTED; B*A must fit an int (HPC_RLL_EINVAL otherwise); element offsets are 64-bit.
+ * hpc_rll_coma_forward -- two launches (heads over T*B*A rows, the return scan over T-1 steps; T == 1: the heads only,
+ *   loss[1] = 0).  ws: hpc_rll_coma_workspace_floats(T,B,A) floats, with R = T*B*A the layout is
+ *   delta (R; rows t < T-1 are written: 2 w (qa - R_t) scale_q) | qa (R) | tqa (R) | lse (R) | H (R) |
+ *   w adv scale_pe (R; 0 for an action outside) | partial sums of the heads | partial sums of the scan.
+ *   T, B or A == 0 zeroes loss[3] and launches nothing.
+ * hpc_rll_coma_backward -- one streaming launch without reductions or atomics: reads logit once and the saved per-row
+ *   floats of ws, writes every element of grad_logit and grad_q_value (T,B,A,N) once.  Either output may be NULL (it is then
+ *   neither computed nor written; logit may then be NULL when grad_logit is); with both NULL nothing is launched.
+ *   g_policy, g_q, g_entropy are device scalars (NULL = 1); weight and scale_pe as given to the forward.
+ * hpc_rll_coma_last_config -- out[HPC_RLL_COMA_CONFIG_INTS] = {
+ *    [0..10]  the HPC_RLL_SCAN_CONFIG_INTS ints of hpc_rll_scan_last_config for the COMA scan (private to this entry point, as
+ *             hpc_rll_retrace_last_config's are): [6] the mask element type, [7] 1 = done given, [8] 1 = weight given,
+ *    [11..17] the heads: launches so far, G, VEC, E (lanes per row, floats per load, loads per lane and row), R (rows per
+ *             group and iteration), flags (bit 0 weight given), workgroups,
+ *    [18..24] the backward: launches so far, G, VEC, E, R, flags (bit 0 grad_logit written, bit 1 grad_q_value written,
+ *             bit 2 weight given), workgroups };
+ *   each of the three parts is {0, -1 ...} before its first launch; HPC_RLL_EINVAL for out == NULL.
+ * Argument errors, before any HIP call: HPC_RLL_EINVAL (null operands, then negative sizes, N <= 0, a B*A past an int or an
+ * unknown mask_dtype), HPC_RLL_EALIGN (a pointer off 4-byte alignment, action off 8; a byte mask has none), then
+ * HPC_RLL_EUNSUPPORTED (N > 1024); then empty shapes return 0. */
+#define HPC_RLL_COMA_CONFIG_INTS (25)
+int64_t hpc_rll_coma_workspace_floats(int T, int B, int A);
+int hpc_rll_coma_forward(const float* logit, const int64_t* action, const float* q_value, const float* target_q_value,
+                         const float* reward, const float* weight, const void* done, int mask_dtype, float* loss,
+                         float* ws, int T, int B, int A, int N, float gamma, float lambda, float scale_pe, float scale_q,
+                         void* stream);
+int hpc_rll_coma_backward(const float* g_policy, const float* g_q, const float* g_entropy, const float* logit,
+                          const int64_t* action, const float* weight, const float* ws, float* grad_logit,
+                          float* grad_q_value, int T, int B, int A, int N, float scale_pe, void* stream);
+int hpc_rll_coma_last_config(int* out);
+
 /* PPO -- replaces PPOForward/Backward (rl_utils/entry.h:158-165, src/rl_utils/ppo.cu:8-111).
  * logits (B,N), action (B,), value_new/old, adv, ret, weight (B,) (weight NULL = ones).
  * out5 = policy_loss, value_loss, entropy_loss, approx_kl, clipfrac.  dual_clip < 1 disables dual clip
