@@ -23,7 +23,7 @@
 //     are loaded at +B by a chunk's last row (at t = T-1: v_T, c = 0, and the row's own address for c and qa).  The own v and
 //     c of a chunk's first row feed nothing and their loads are dropped by the compiler.  finish stores Q_t and, in the fused
 //     form, accumulates the loss and stores delta = lw*(qa_t - Q_t)*scale.  init writes row T of q_retraces (= v_T).
-//   * retrace_bwd_kernel writes all (T+1)*B*N gradient floats once with the stores of stream_write.hpp (16-byte nontemporal
+//   * the backward (onehot_stream_kernel of stream_write.hpp) writes all (T+1)*B*N gradient floats once (16-byte nontemporal
 //     stores, every workgroup's 256 stores one 4 KiB-aligned block): g*delta at column a_t, zeros elsewhere.  No atomics,
 //     q_values is not read.
 //
@@ -37,6 +37,7 @@
 #include "hostutil.hpp"
 #include "hpc_rll_hip.h"
 #include "rowgroup.hpp"
+#include "stream_write.hpp"
 #include "wave.hpp"
 
 namespace hpc_rll {
@@ -278,79 +279,23 @@ int retrace_scan(const float* reward, const float* weights, const float* loss_we
 }
 
 // ================================================================================================
-// backward: every float of grad (n = (T+1)*B*N) written once.  Vector v of the launch covers elements [(v - shift)*VEC, +VEC):
-// the loop runs from the 4 KiB boundary below grad (stream_write.hpp).  (row, col) of a thread's first element advance by
-// (step_row, step_col) = divmod(threads * VEC, N) per sweep: one 64-bit division per thread, not per store.
+// backward: every float of grad (n = (T+1)*B*N) written once by the one-hot writer of stream_write.hpp
 // ================================================================================================
-template <int VEC>
-__global__ __launch_bounds__(256) void retrace_bwd_kernel(const float* __restrict__ g, const int64_t* __restrict__ action,
-                                                          const float* __restrict__ delta, float* __restrict__ grad,
-                                                          size_t n, unsigned shift, long TB, int N, long step_row,
-                                                          int step_col) {
-    const float u = g ? g[0] : 1.f;
-    auto value = [&](long r, int c) {
+struct RetraceGrad {
+    const int64_t* action; const float* delta; long TB;
+    __device__ __forceinline__ float operator()(float u, long r, int c) const {
         const long rr = r < TB ? r : TB - 1;            // rows of t = T: an in-bounds load whose result is unused
         const long a = action[rr];
         const float d = delta[rr];
         return (r < TB && a == (long)c) ? u * d : 0.f;
-    };
-    const size_t nv = n / VEC, nt = (size_t)gridDim.x * 256, end = nv + shift;
-    size_t v = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (v < shift) v += nt;                             // shift < 256 <= nt: one step passes the boundary
-    if (v < end) {
-        const size_t pos = (v - shift) * VEC;
-        long row = (long)(pos / (size_t)N);
-        int col = (int)(pos % (size_t)N);
-        for (; v < end; v += nt) {
-            float out[VEC];
-            long r = row;
-            int c = col;
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) {
-                out[k] = value(r, c);
-                if (++c == N) { c = 0; ++r; }
-            }
-            if (VEC == 4) {
-                vfloat4 t;
-                t.x = out[0]; t.y = out[1]; t.z = out[2]; t.w = out[3];
-                __builtin_nontemporal_store(t, reinterpret_cast<vfloat4*>(grad) + (v - shift));
-            } else {
-                __builtin_nontemporal_store(out[0], grad + (v - shift));
-            }
-            row += step_row;
-            col += step_col;
-            if (col >= N) { col -= N; ++row; }
-        }
     }
-    if (VEC > 1 && blockIdx.x == 0 && threadIdx.x < n - nv * VEC) {   // the last n % VEC floats
-        const size_t i = nv * VEC + threadIdx.x;
-        grad[i] = value((long)(i / (size_t)N), (int)(i % (size_t)N));
-    }
-}
+};
 
-// Grid: unlike a pure fill, every store here waits for two small loads (action, delta), so one workgroup per CU -- the
-// fill's best shape -- leaves a single wave per SIMD walking load -> store round trips (measured 282 us for 302 MB at
-// T=256, B=16384, N=18).  Short-lived workgroups of at most kBwdVecPerThread vectors per thread keep many loads in flight.
-constexpr size_t kBwdVecPerThread = 4;
 int retrace_backward(const float* g, const int64_t* action, const float* delta, float* grad, int T, int B, int N,
                      hipStream_t st) {
     const long TB = (long)T * B;
-    const size_t n = (size_t)(TB + B) * N;
-    const bool vec4 = aligned(grad, 16);
-    const unsigned shift = vec4 ? (unsigned)((reinterpret_cast<uintptr_t>(grad) & 4095) / 16) : 0u;
-    const size_t end = (vec4 ? n / 4 : n) + shift;
-    size_t grid = (end + 256 * kBwdVecPerThread - 1) / (256 * kBwdVecPerThread);
-    if (grid < 1) grid = 1;
-    if (grid > 256 * 1024) grid = 256 * 1024;   // the threads loop
-    const size_t nt = grid * 256;
-    if (vec4) {
-        hipLaunchKernelGGL(retrace_bwd_kernel<4>, dim3((unsigned)grid), dim3(256), 0, st, g, action, delta, grad, n, shift, TB,
-                           N, (long)(nt * 4 / N), (int)(nt * 4 % N));
-    } else {
-        hipLaunchKernelGGL(retrace_bwd_kernel<1>, dim3((unsigned)grid), dim3(256), 0, st, g, action, delta, grad, n, 0u, TB, N,
-                           (long)(nt / N), (int)(nt % N));
-    }
-    return last_error();
+    const int rc = launch_onehot_stream(RetraceGrad{action, delta, TB}, g, grad, (size_t)(TB + B) * N, N, st);
+    return rc == (int)hipSuccess ? HPC_RLL_OK : rc;
 }
 
 }  // namespace

@@ -19,6 +19,7 @@
 #include "nstep.hpp"
 #include "ppo_op.hpp"
 #include "stream_write.hpp"
+#include "value_rescale.hpp"
 
 namespace hpc_rll {
 namespace {
@@ -68,16 +69,6 @@ inline int launch_sample(const Op& op, long n, float* partials, int nacc, const 
 }
 
 // ---------------------------------------------------------------------------------------------- q n-step TD
-__device__ __forceinline__ float h_transform(float x, float eps) {
-    const float s = (x > 0.f) ? 1.f : ((x < 0.f) ? -1.f : 0.f);
-    return s * (sqrtf(fabsf(x) + 1.f) - 1.f) + eps * x;
-}
-__device__ __forceinline__ float h_inverse(float x, float eps) {
-    const float s = (x > 0.f) ? 1.f : ((x < 0.f) ? -1.f : 0.f);
-    const float t = (sqrtf(1.f + 4.f * eps * (fabsf(x) + 1.f + eps)) - 1.f) / (2.f * eps);
-    return s * (t * t - 1.f);
-}
-
 struct QNStepOp {
     static constexpr int NACC = 1;
     const float *q, *next_q; const int64_t *action, *next_action; const float *reward, *done, *weight;

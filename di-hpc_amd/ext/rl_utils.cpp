@@ -3,7 +3,7 @@
 // Two layers in one module:
 //   * the reference's L2 functions `XxxForward(inputs, outputs, scalars...)` / `XxxBackward(inputs, outputs)`
 //     (declared in include/hpc/rll/cuda/rl_utils/entry.h:10-165) -- validated, launched on torch's current stream;
-//   * fused autograd ops (`gae`, `td_lambda`, `vtrace`, `upgo`, `upgo_masked`, `ppo`, `ppo_continuous`, `vtrace_continuous`, `retrace_loss`, `acer_policy_loss`, `coma`, `q_nstep_td`, `dist_nstep_td`, `iqn_nstep_td`,
+//   * fused autograd ops (`gae`, `td_lambda`, `vtrace`, `upgo`, `upgo_masked`, `ppo`, `ppo_continuous`, `vtrace_continuous`, `retrace_loss`, `acer_policy_loss`, `coma`, `r2d2_td`, `q_nstep_td`, `dist_nstep_td`, `iqn_nstep_td`,
 //     `qrdqn_nstep_td`) -- torch::autograd::Function nodes that allocate outputs, launch and register backward in ONE
 //     pybind call; these are what hpc_rll.rl_utils.* modules use.
 // Host-only C++: every kernel lives behind the C ABI of libhpc_rll_hip.so (include/hpc_rll_hip.h).
@@ -1096,6 +1096,84 @@ struct ComaFn : public ag::Function<ComaFn> {
     }
 };
 
+// ========================================================================================================== R2D2
+// The R2D2 sequence loss (hpc_rll_r2d2_*): the n-step (double-)Q TD error of every step of a (T,B,N) unroll, its loss and the
+// replay priority.  Shapes and dtypes are checked before the device so that a wrong argument is named even on host tensors.
+// The gradient flows to q only; saves action and the workspace (delta).
+struct R2d2Fn : public ag::Function<R2d2Fn> {
+    static ag::tensor_list forward(ag::AutogradContext* ctx, const Tensor& q, const Tensor& target_q, const Tensor& action,
+                                   const Tensor& reward, const OptTensor& done, const OptTensor& weight, double gamma,
+                                   int64_t nstep, int64_t burnin, bool value_rescale, bool double_q, double priority_eta,
+                                   std::optional<double> scale) {
+        TORCH_CHECK(q.defined(), "q: expected a tensor, got None");
+        TORCH_CHECK(q.dim() == 3, "q: expected (T,B,N), got ", q.sizes());
+        const int64_t T = q.size(0), B = q.size(1), N = q.size(2);
+        check_shape(q, "q", {T, B, N});
+        check_shape(target_q, "target_q", {T, B, N});
+        check_shape(action, "action", {T, B}, at::kLong);
+        check_shape(reward, "reward", {T, B});
+        int code = HPC_RLL_MASK_U8;
+        if (has(done)) {
+            code = mask_code(*done, "done");
+            TORCH_CHECK(done->sizes() == reward.sizes(), "done: shape ", done->sizes(), ", expected ", reward.sizes(),
+                        " (the shape of reward)");
+        }
+        const int wm = masked_td_weight_mode(weight, T, B);
+        TORCH_CHECK(nstep >= 1, "r2d2_td: nstep = ", nstep, ", expected nstep >= 1");
+        TORCH_CHECK(burnin >= 0, "r2d2_td: burnin = ", burnin, ", expected burnin >= 0");
+        retrace_check_n("r2d2_td", N);
+        const at::Device dev = q.device();
+        req(q, "q", dev);
+        req(target_q, "target_q", dev);
+        req(action, "action", dev, at::kLong);
+        req(reward, "reward", dev);
+        if (has(done)) req(*done, "done", dev, done->scalar_type());
+        if (has(weight)) req(*weight, "weight", dev);
+        c10::DeviceGuard g(dev);
+        const int64_t L = std::max<int64_t>(T - std::min(nstep, T) - std::min(burnin, T), 0);
+        const bool empty = B == 0 || L == 0;
+        Tensor loss = new_f32({1}, dev);
+        // no valid step: the loss is zero and nothing is launched; the outputs are then zeros
+        Tensor td = new_f32({L, B}, dev);
+        Tensor priority = empty ? at::zeros({B}, q.options()) : new_f32({B}, dev);
+        Tensor ws = new_f32({empty ? 0 : hpc_rll_r2d2_workspace_floats(to_int(T, "T"), to_int(B, "B"))}, dev);
+        const int n = empty ? 1 : to_int(nstep, "nstep"), bi = empty ? (int)T : to_int(burnin, "burnin");
+        check(hpc_rll_r2d2_forward(fptr(q), fptr(target_q), iptr(action), fptr(reward), has(done) ? vptr(*done) : nullptr, code,
+                                   fptr(weight), wm, fmut(loss), fmut(td), fmut(priority), fmut(ws), to_int(T, "T"),
+                                   to_int(B, "B"), to_int(N, "N"), n, bi, (float)gamma, value_rescale ? 1 : 0,
+                                   double_q ? 1 : 0, (float)priority_eta, loss_scale(scale, L * B), stream_of(dev)),
+              "hpc_rll_r2d2_forward");
+        ctx->save_for_backward({action, ws});
+        ctx->saved_data["N"] = N;
+        ctx->saved_data["nstep"] = (int64_t)n;
+        ctx->saved_data["burnin"] = (int64_t)bi;
+        ctx->saved_data["empty"] = empty;
+        ctx->mark_non_differentiable({td, priority});
+        return {loss, td, priority};
+    }
+    static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
+        ag::tensor_list out(13);
+        if (!ctx->needs_input_grad(0)) return out;
+        const auto saved = ctx->get_saved_variables();
+        const Tensor &action = saved[0], &ws = saved[1];
+        const at::Device dev = action.device();
+        c10::DeviceGuard g(dev);
+        const int64_t T = action.size(0), B = action.size(1), N = ctx->saved_data["N"].toInt();
+        Tensor gl = grad1(grads[0], dev, "grad_loss");
+        if (ctx->saved_data["empty"].toBool()) {
+            out[0] = at::zeros({T, B, N}, gl.options());
+            return out;
+        }
+        Tensor grad_q = new_f32({T, B, N}, dev);
+        check(hpc_rll_r2d2_backward(fptr(gl), iptr(action), fptr(ws), fmut(grad_q), (int)T, (int)B, (int)N,
+                                    (int)ctx->saved_data["nstep"].toInt(), (int)ctx->saved_data["burnin"].toInt(),
+                                    stream_of(dev)),
+              "hpc_rll_r2d2_backward");
+        out[0] = grad_q;
+        return out;
+    }
+};
+
 // ==================================================================================================== q n-step TD
 struct QDims { int64_t B, N, nstep; at::Device dev; };
 int64_t check_nstep_reward(const Tensor& reward, int64_t B, const at::Device& dev) {
@@ -1688,6 +1766,17 @@ PYBIND11_MODULE(hpc_rl_utils, m) {
           py::arg("scales") = py::none(),
           "COMA losses (policy, q_value, entropy; (1,) each) from (T,B,A,N) logits and action values, (T,B,A) int64 actions "
           "and (T,B) rewards; differentiable wrt logit and q_value; scales = (scale_pe, scale_q) for a sharded caller");
+    m.def("r2d2_td", [](const Tensor& q, const Tensor& target_q, const Tensor& action, const Tensor& reward,
+                        const OptTensor& done, const OptTensor& weight, double gamma, int64_t nstep, int64_t burnin,
+                        bool value_rescale, bool double_q, double priority_eta, std::optional<double> scale) {
+        return R2d2Fn::apply(q, target_q, action, reward, done, weight, gamma, nstep, burnin, value_rescale, double_q,
+                             priority_eta, scale);
+    }, py::arg("q"), py::arg("target_q"), py::arg("action"), py::arg("reward"), py::arg("done") = py::none(),
+          py::arg("weight") = py::none(), py::arg("gamma") = 0.997, py::arg("nstep") = 5, py::arg("burnin") = 0,
+          py::arg("value_rescale") = true, py::arg("double_q") = true, py::arg("priority_eta") = 0.9,
+          py::arg("scale") = py::none(),
+          "R2D2 sequence loss over a (T,B,N) unroll: (loss (1,), td_error (L,B), priority (B,)) with L = T - nstep - burnin; "
+          "differentiable wrt q; scale = 1/(global count) for a sharded caller");
     m.def("q_nstep_td", [](const Tensor& q, const Tensor& nq, const Tensor& action, const Tensor& naction,
                            const Tensor& reward, const Tensor& done, const OptTensor& weight, double gamma, bool rescale,
                            std::optional<double> scale) {

@@ -405,6 +405,50 @@ int hpc_rll_coma_backward(const float* g_policy, const float* g_q, const float* 
                           float* grad_q_value, int T, int B, int A, int N, float scale_pe, void* stream);
 int hpc_rll_coma_last_config(int* out);
 
+/* R2D2 sequence loss: the n-step (double-)Q TD error of every step of a whole unroll, its loss, the replay priority and the
+ * gradient, in a number of launches that does not depend on T (no reference counterpart; the semantics restate the loop of
+ * DI-engine's r2d2 policy over q_nstep_td_error / q_nstep_td_error_with_rescale).  q, target_q (T,B,N); action (T,B) int64;
+ * reward (T,B); done (T,B) of `mask_dtype` (HPC_RLL_MASK_U8 / HPC_RLL_MASK_F32; NULL = no episode ends), k_t = 1 - done_t;
+ * weight with weight_mode 0 none (NULL: nothing is multiplied), 1 (B,), 2 (T,B) indexed by the absolute t.  The valid steps
+ * are t = burnin .. T-nstep-1, L = T - nstep - burnin of them.  For a valid (t,b), with n = nstep:
+ *   a = action[t,b], qa = q[t,b,a];  a* = the LOWEST index of max_n sel[t+n,b,:], sel = q (double_q) or target_q;
+ *   v = target_q[t+n,b,a*], h_inverse(v) with value_rescale (eps = 1e-2, as hpc_rll_q_nstep_td_forward's rescale form);
+ *   p_0 = 1, p_{j+1} = (p_j gamma) k_{t+j};  G = sum_{j<n} p_j reward[t+j,b] + p_n v, h_transform(G) with value_rescale;
+ *   d = qa - G;  td_error[t-burnin,b] = d^2;  loss = scale sum_{t,b} w d^2  (G is a constant);
+ *   priority[b] = eta max_t td_error[.,b] + (1 - eta) mean_t td_error[.,b]  (unweighted);
+ *   grad_q[t,b,n] = g 2 w d scale [n = a] on valid rows and 0 on every other row.
+ * A done at step t+j keeps reward[t+j] and cuts everything after it in that window; a done at t+n or later does not touch
+ * step t.  An action outside [0,N) never addresses memory: the step is dropped (d = 0: nothing for the loss or the priority,
+ * a zero gradient row).  NaN in sel is not supported.  1 <= N <= 1024, beyond that HPC_RLL_EUNSUPPORTED.
+ * hpc_rll_r2d2_forward -- three launches: the heads over the rows t >= burnin (qa and v per row), the window over the L*B
+ *   valid steps (td_error, delta, the loss), the priority over td_error (L,B) (fixed-order sums, no atomics).  ws:
+ *   hpc_rll_r2d2_workspace_floats(T,B) floats, with R = T*B the layout is
+ *   delta (R; rows burnin .. T-nstep-1 are written: 2 w d scale) | qa (R) | v (R) (rows burnin .. T-1 of both are written) |
+ *   partial sums of the window launch (one per workgroup, at most 512).
+ *   T == 0, B == 0 or L <= 0 zeroes loss and priority (B,) and launches nothing.
+ * hpc_rll_r2d2_backward -- one streaming launch: every float of grad_q (T,B,N) written once, q is not read.  g_loss is a
+ *   device scalar (NULL = 1); nstep and burnin as given to the forward.
+ * hpc_rll_r2d2_last_config -- out[HPC_RLL_R2D2_CONFIG_INTS] = {
+ *    [0..6]   the heads: launches so far, G, VEC, E (lanes per row, floats per load, loads per lane and row), R (rows per
+ *             group and iteration), flags (bit 0 double_q, bit 1 value_rescale), workgroups,
+ *    [7..11]  the window: launches so far, threads per workgroup, flags (bits 0-1 the mask: 0 none, 1 bytes, 2 floats;
+ *             bits 2-3 weight_mode; bit 4 value_rescale), workgroups, finalisation (1 = inside the launch, 2 = one more launch),
+ *    [12..13] the priority: launches so far, workgroups,
+ *    [14..16] the backward: launches so far, floats per store, workgroups };
+ *   each of the four parts is {0, -1 ...} before its first launch; HPC_RLL_EINVAL for out == NULL.
+ * Argument errors, before any HIP call: HPC_RLL_EINVAL (null operands, then negative sizes, N <= 0, nstep < 1, burnin < 0,
+ * an unknown mask_dtype or weight_mode, a weight that does not match its mode), HPC_RLL_EALIGN (a pointer off 4-byte
+ * alignment, action off 8; a byte mask has none), then HPC_RLL_EUNSUPPORTED (N > 1024); then empty shapes return 0. */
+#define HPC_RLL_R2D2_CONFIG_INTS (17)
+int64_t hpc_rll_r2d2_workspace_floats(int T, int B);
+int hpc_rll_r2d2_forward(const float* q, const float* target_q, const int64_t* action, const float* reward, const void* done,
+                         int mask_dtype, const float* weight, int weight_mode, float* loss, float* td_error, float* priority,
+                         float* ws, int T, int B, int N, int nstep, int burnin, float gamma, int value_rescale, int double_q,
+                         float priority_eta, float scale, void* stream);
+int hpc_rll_r2d2_backward(const float* g_loss, const int64_t* action, const float* ws, float* grad_q, int T, int B, int N,
+                          int nstep, int burnin, void* stream);
+int hpc_rll_r2d2_last_config(int* out);
+
 /* PPO -- replaces PPOForward/Backward (rl_utils/entry.h:158-165, src/rl_utils/ppo.cu:8-111).
  * logits (B,N), action (B,), value_new/old, adv, ret, weight (B,) (weight NULL = ones).
  * out5 = policy_loss, value_loss, entropy_loss, approx_kl, clipfrac.  dual_clip < 1 disables dual clip
