@@ -1,0 +1,586 @@
+// grpo.hip -- the language-model policy losses on gfx950: the per-token log-probability of a chosen token over a large
+// vocabulary, GRPO's clipped-ratio + k3-KL token loss with per-sequence masked means, and the streaming gradient.
+//
+// No reference counterpart; the semantics restate DI-engine's rl_utils grpo_policy_error / rloo_policy_error and the
+// log_prob_utils helper they share.  logits (rows, V) fp32 or bf16 (rows = B*S), action (rows) int64, per token, with
+// lp(x) = x[a] - logsumexp(x):
+//   pn = lp(logit_new)   po = lp(old) or old   pr = lp(ref) or ref
+//   d  = pr - pn         kl = exp(d) - d - 1
+//   r  = exp(pn - po)    rc = clamp(r, 1 - clip, 1 + clip)
+//   l  = -min(r adv_b, rc adv_b) + beta kl
+//   loss = scale sum_b (sum_s w l / sum_s w)                                           (scale = 1/B unless a sharded caller gives it)
+//   dl/dpn = -adv_b r [not (rc adv_b < r adv_b)] - beta (exp(d) - 1)
+//   grad[b,s,v] = g w scale / (sum_s w) dl/dpn ([v = a] - exp(x_v - lse))
+//
+// Three kernels:
+//   * token_logp_kernel<Elem, ALIGNED, NT>: ONE read of the row.  Every lane keeps an online (max, sum exp) pair over the
+//     16-byte vectors it visits, kInFlight loads in flight, the running sum rescaled once per batch of loads; the pairs of a
+//     wave meet in a butterfly, the four waves of a workgroup through 8 LDS words.  NT = 256: a workgroup per row (V above
+//     kWaveRowMaxV); NT = 64: a wave per row, four rows per workgroup.  ALIGNED = false peels the elements in front of the
+//     first and behind the last 16-byte boundary of the row (at most 2 (P - 1), one lane each), so no wide load is
+//     misaligned or leaves the row.  A dropped row (action outside [0,V), or weight 0) is not read: logp = lse = 0.
+//   * grpo_token_kernel: a wave per sequence walks s twice (the weight sum, then everything); wave butterflies in a fixed
+//     order, the batch sums leave through publish_sums (colscan.hpp).  No float atomics.
+//   * token_grad_kernel<Elem, WIDE, NT>: reads the row once, writes c ([v = a] - exp(x - lse)) with nontemporal stores in the
+//     logits' dtype (bf16: round to nearest even).  A row whose coefficient is exactly 0 is zero-filled WITHOUT reading its
+//     logits; the decision is the device's.  WIDE needs both bases and the row pitch on 16 bytes; otherwise one element per
+//     access (input and output rows do not share an alignment, so peeling cannot serve both).
+// -inf logits are clamped to the most negative finite float on load (probability exactly 0), as categorical.hip does; the same
+// clamp turns a NaN logit of a LIVE row into an entry of probability 0: NaN there is not propagated to the loss or the gradient.
+#include <hip/hip_runtime.h>
+
+#include "colscan.hpp"
+#include "hostutil.hpp"
+#include "hpc_rll_hip.h"
+#include "wave.hpp"
+
+namespace hpc_rll {
+namespace {
+
+constexpr int kGrpoMaxV = 262144;
+constexpr int kWaveRowMaxV = 2048;   // up to here a wave per row, above a workgroup per row
+constexpr int kInFlight = 4;         // 16-byte loads a lane issues before it uses the first
+constexpr float kFltMaxG = 3.402823466e+38f;
+constexpr float kLog2eG = 1.44269504088896340736f, kLn2G = 0.69314718055994530942f;
+constexpr int kGrpoSums = 5;         // loss, sum w kl, sum w r, sum w clipped, sum w
+constexpr long kRowGridMax = 1L << 16;   // workgroups of a row launch; above it they loop (far more than the device holds at once)
+
+typedef unsigned int vuint4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ float clampf(float x) { return fmaxf(x, -kFltMaxG); }   // -inf (masked) and NaN -> finite
+__device__ __forceinline__ float ex2(float y) { return __builtin_amdgcn_exp2f(y); }
+__device__ __forceinline__ float as_f(unsigned u) { return __builtin_bit_cast(float, u); }
+__device__ __forceinline__ unsigned as_u(float f) { return __builtin_bit_cast(unsigned, f); }
+
+// ---- the two element types: P elements per 16 bytes
+template <class Elem> struct ElemIO;
+template <> struct ElemIO<float> {
+    static constexpr int P = 4;
+    static constexpr int kCode = 0;
+    static __device__ __forceinline__ float get(const float* p) { return *p; }
+    static __device__ __forceinline__ void put(float* p, float v) { __builtin_nontemporal_store(v, p); }
+    static __device__ __forceinline__ void unpack(const vuint4& v, float* x) {
+        x[0] = as_f(v.x); x[1] = as_f(v.y); x[2] = as_f(v.z); x[3] = as_f(v.w);
+    }
+    static __device__ __forceinline__ vuint4 pack(const float* x) {
+        vuint4 v = {as_u(x[0]), as_u(x[1]), as_u(x[2]), as_u(x[3])};
+        return v;
+    }
+};
+__device__ __forceinline__ unsigned bf16_bits(float f) {   // round to nearest even
+    return (unsigned)__builtin_bit_cast(unsigned short, static_cast<__bf16>(f));
+}
+template <> struct ElemIO<uint16_t> {
+    static constexpr int P = 8;
+    static constexpr int kCode = 1;
+    static __device__ __forceinline__ float get(const uint16_t* p) { return as_f((unsigned)*p << 16); }
+    static __device__ __forceinline__ void put(uint16_t* p, float v) { __builtin_nontemporal_store((uint16_t)bf16_bits(v), p); }
+    static __device__ __forceinline__ void unpack(const vuint4& v, float* x) {
+        const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            x[2 * i] = as_f(w[i] << 16);
+            x[2 * i + 1] = as_f(w[i] & 0xffff0000u);
+        }
+    }
+    static __device__ __forceinline__ vuint4 pack(const float* x) {
+        unsigned w[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) w[i] = bf16_bits(x[2 * i]) | (bf16_bits(x[2 * i + 1]) << 16);
+        vuint4 v = {w[0], w[1], w[2], w[3]};
+        return v;
+    }
+};
+
+// ---- online softmax statistics: s = sum exp(x - m) over what has been seen, m its maximum (never below -FLT_MAX)
+struct MS { float m, s; };
+__device__ __forceinline__ MS ms_merge(const MS& a, const MS& b) {
+    MS r;
+    r.m = fmaxf(a.m, b.m);
+    r.s = a.s * ex2((a.m - r.m) * kLog2eG) + b.s * ex2((b.m - r.m) * kLog2eG);
+    return r;
+}
+__device__ __forceinline__ MS ms_wave(MS a) {   // all 64 lanes end with the wave's pair
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1) {
+        MS o;
+        o.m = __shfl_xor(a.m, k, 64);
+        o.s = __shfl_xor(a.s, k, 64);
+        a = ms_merge(a, o);
+    }
+    return a;
+}
+
+// One batch of kInFlight vectors: a single rescale of the running sum.  GUARD: vector k counts only when ok[k].
+template <class Elem, bool GUARD>
+__device__ __forceinline__ void ms_batch(MS& a, const vuint4 (&r)[kInFlight], const bool (&ok)[kInFlight]) {
+    constexpr int P = ElemIO<Elem>::P;
+    float x[kInFlight * P];
+    float bm = -kFltMaxG;
+#pragma unroll
+    for (int k = 0; k < kInFlight; ++k) {
+        ElemIO<Elem>::unpack(r[k], x + k * P);
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+            float v = clampf(x[k * P + j]);
+            if (GUARD) v = ok[k] ? v : -kFltMaxG;
+            x[k * P + j] = v;
+            bm = fmaxf(bm, v);
+        }
+    }
+    const float m2 = fmaxf(a.m, bm);
+    float s = a.s * ex2((a.m - m2) * kLog2eG);
+#pragma unroll
+    for (int i = 0; i < kInFlight * P; ++i) s += ex2((x[i] - m2) * kLog2eG);
+    a.m = m2;
+    a.s = s;
+}
+
+// The pair of lane `tid` of the NT that share the row p[0, V).
+template <class Elem, bool ALIGNED, int NT>
+__device__ __forceinline__ MS row_stats(const Elem* __restrict__ p, int V, int tid) {
+    using IO = ElemIO<Elem>;
+    constexpr int P = IO::P;
+    int h = 0;
+    if (!ALIGNED) {
+        h = (int)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u) / sizeof(Elem));
+        h = h < V ? h : V;
+    }
+    const int nvec = (V - h) / P;
+    MS a{-kFltMaxG, 0.f};
+    if (!ALIGNED) {   // the elements outside the 16-byte grid of the row: fewer than 2 P, one lane each
+        const int tail = V - h - nvec * P;
+        if (tid < h + tail) {
+            const int i = tid < h ? tid : h + nvec * P + (tid - h);
+            a.m = clampf(IO::get(p + i));
+            a.s = 1.f;
+        }
+    }
+    const vuint4* __restrict__ pv = reinterpret_cast<const vuint4*>(p + h);
+    const bool all[kInFlight] = {true, true, true, true};
+    int v = tid;
+    for (; v + (kInFlight - 1) * NT < nvec; v += kInFlight * NT) {
+        vuint4 r[kInFlight];
+#pragma unroll
+        for (int k = 0; k < kInFlight; ++k) r[k] = __builtin_nontemporal_load(pv + v + k * NT);
+        ms_batch<Elem, false>(a, r, all);
+    }
+    if (v < nvec) {
+        vuint4 r[kInFlight];
+        bool ok[kInFlight];
+#pragma unroll
+        for (int k = 0; k < kInFlight; ++k) {
+            ok[k] = v + k * NT < nvec;
+            const vuint4 z = {0u, 0u, 0u, 0u};
+            r[k] = z;
+            if (ok[k]) r[k] = __builtin_nontemporal_load(pv + v + k * NT);
+        }
+        ms_batch<Elem, true>(a, r, ok);
+    }
+    return a;
+}
+
+// ================================================================================================
+// the head: logp[row] = x[a] - lse, lse[row] (lse may be NULL)
+// ================================================================================================
+template <class Elem, bool ALIGNED, int NT>
+__global__ __launch_bounds__(256) void token_logp_kernel(const Elem* __restrict__ x, const int64_t* __restrict__ action,
+                                                         const float* __restrict__ weight, float* __restrict__ logp,
+                                                         float* __restrict__ lse, long rows, int V) {
+    constexpr int RPW = 256 / NT;
+    __shared__ float red[2][4][2];
+    const int tid = threadIdx.x % NT, sub = threadIdx.x / NT;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int par = 0;
+    for (long r0 = (long)blockIdx.x * RPW; r0 < rows; r0 += (long)gridDim.x * RPW) {
+        const long row = r0 + sub;
+        const bool have = row < rows;
+        long a = -1;
+        float w = 1.f;
+        if (have) {
+            a = action[row];
+            if (weight) w = weight[row];
+        }
+        const bool live = have && a >= 0 && a < (long)V && w != 0.f;   // the same for all NT threads of the row
+        MS st{-kFltMaxG, 0.f};
+        float xa = 0.f;
+        if (live) {
+            const Elem* p = x + (size_t)row * (size_t)V;
+            if (tid == 0) xa = clampf(ElemIO<Elem>::get(p + a));
+            st = ms_wave(row_stats<Elem, ALIGNED, NT>(p, V, tid));
+            if (NT == 256) {   // a workgroup per row: `live` is uniform over it
+                if (lane == 0) {
+                    red[par][wv][0] = st.m;
+                    red[par][wv][1] = st.s;
+                }
+                __syncthreads();
+                if (threadIdx.x == 0) {
+                    MS w0{red[par][0][0], red[par][0][1]}, w1{red[par][1][0], red[par][1][1]};
+                    MS w2{red[par][2][0], red[par][2][1]}, w3{red[par][3][0], red[par][3][1]};
+                    st = ms_merge(ms_merge(w0, w1), ms_merge(w2, w3));
+                }
+                par ^= 1;   // the next row writes the other half: one barrier per row
+            }
+        }
+        if (tid == 0 && have) {
+            float l = 0.f, lp = 0.f;
+            if (live) {
+                l = st.m + __builtin_amdgcn_logf(st.s) * kLn2G;   // s is in [1, V]: the bare log2
+                lp = xa - l;
+            }
+            logp[row] = lp;
+            if (lse) lse[row] = l;
+        }
+    }
+}
+
+// The dispatch records (hpc_rll_grpo_last_config): plain ints of the host process, not synchronised.  [0] = launches so far.
+constexpr int kHeadInts = 7, kTokenInts = 3, kGradInts = 6;
+int g_grpo_head[kHeadInts], g_grpo_token[kTokenInts], g_grpo_grad[kGradInts];
+template <int K> void grpo_note(int (&rec)[K], const int (&vals)[K - 1]) {
+    ++rec[0];
+    for (int i = 1; i < K; ++i) rec[i] = vals[i - 1];
+}
+
+long row_grid_of(long rows, int rpw) {
+    long grid = (rows + rpw - 1) / rpw;
+    return grid < 1 ? 1 : (grid > kRowGridMax ? kRowGridMax : grid);
+}
+
+template <class Elem>
+int token_logp_launch(const void* xv, const int64_t* action, const float* weight, float* logp, float* lse, long rows, int V,
+                      hipStream_t st) {
+    const Elem* x = static_cast<const Elem*>(xv);
+    const bool al = aligned(x, 16) && ((size_t)V * sizeof(Elem)) % 16 == 0;
+    const bool wide_row = V > kWaveRowMaxV;
+    const int rpw = wide_row ? 1 : 4;
+    const long grid = row_grid_of(rows, rpw);
+#define HPC_RLL_GRPO_HEAD(AL_, NT_)                                                                                  \
+    hipLaunchKernelGGL((token_logp_kernel<Elem, AL_, NT_>), dim3((unsigned)grid), dim3(256), 0, st, x, action, weight, \
+                       logp, lse, rows, V)
+    if (al && wide_row) HPC_RLL_GRPO_HEAD(true, 256);
+    else if (al) HPC_RLL_GRPO_HEAD(true, 64);
+    else if (wide_row) HPC_RLL_GRPO_HEAD(false, 256);
+    else HPC_RLL_GRPO_HEAD(false, 64);
+#undef HPC_RLL_GRPO_HEAD
+    const int rc = last_error();
+    if (!rc) grpo_note(g_grpo_head, {ElemIO<Elem>::kCode, 16, al ? 0 : 1, wide_row ? 256 : 64, rpw, (int)grid});
+    return rc;
+}
+int token_logp_any(const void* x, int elem, const int64_t* action, const float* weight, float* logp, float* lse, long rows,
+                   int V, hipStream_t st) {
+    return elem == 1 ? token_logp_launch<uint16_t>(x, action, weight, logp, lse, rows, V, st)
+                     : token_logp_launch<float>(x, action, weight, logp, lse, rows, V, st);
+}
+
+// ================================================================================================
+// the token loss: a wave per sequence
+// ================================================================================================
+struct GrpoTokenArgs {
+    const float *pn, *po, *pr; const int64_t* action; const float* adv; const float* weight; float* coef;
+    int B, S, V; float clip, beta, scale;
+};
+
+__global__ __launch_bounds__(256) void grpo_token_kernel(const GrpoTokenArgs p, float* __restrict__ partials,
+                                                         const ScanFold fold) {
+    __shared__ float red[4][kGrpoSums];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const float lo = 1.f - p.clip, hi = 1.f + p.clip;
+    float acc[kGrpoSums] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    for (long b = (long)blockIdx.x * 4 + wv; b < (long)p.B; b += (long)gridDim.x * 4) {
+        const size_t base = (size_t)b * (size_t)p.S;
+        float sw = 0.f;
+        for (int s = lane; s < p.S; s += 64) {
+            const long a = p.action[base + s];
+            const float w = p.weight ? p.weight[base + s] : 1.f;
+            sw += (a >= 0 && a < (long)p.V && w != 0.f) ? w : 0.f;
+        }
+        sw = wave_sum(sw);
+        const float adv = p.adv[b];
+        const float inv = sw != 0.f ? 1.f / sw : 0.f;   // a sequence without weight contributes 0 and still counts in B
+        const float cs = p.scale * inv;
+        float sl = 0.f, skl = 0.f, sr = 0.f, sc = 0.f;
+        for (int s = lane; s < p.S; s += 64) {
+            const size_t i = base + s;
+            const long a = p.action[i];
+            float w = p.weight ? p.weight[i] : 1.f;
+            const bool live = a >= 0 && a < (long)p.V && w != 0.f;
+            float pn = p.pn[i], po = p.po[i];
+            float pr = p.pr ? p.pr[i] : pn;
+            w = live ? w : 0.f;                          // a dropped token: selected away, whatever its values are
+            pn = live ? pn : 0.f;
+            po = live ? po : 0.f;
+            pr = live ? pr : 0.f;
+            const float d = pr - pn;
+            const float em1 = expm1f(d);
+            const float kl = em1 - d;
+            const float r = expf(pn - po);
+            const float rc = fminf(fmaxf(r, lo), hi);
+            const float t1 = r * adv, t2 = rc * adv;
+            const float l = -(t2 < t1 ? t2 : t1) + p.beta * kl;
+            const float dl = -(t2 < t1 ? 0.f : t1) - p.beta * em1;
+            const float clipped = (r > hi || r < lo) ? 1.f : 0.f;
+            sl = fmaf(w, l, sl);
+            skl = fmaf(w, kl, skl);
+            sr = fmaf(w, r, sr);
+            sc = fmaf(w, clipped, sc);
+            p.coef[i] = live ? (w * cs) * dl : 0.f;
+        }
+        sl = wave_sum(sl);
+        skl = wave_sum(skl);
+        sr = wave_sum(sr);
+        sc = wave_sum(sc);
+        acc[0] += sl * inv;
+        acc[1] += skl;
+        acc[2] += sr;
+        acc[3] += sc;
+        acc[4] += sw;
+    }
+    if (lane == 0)
+#pragma unroll
+        for (int k = 0; k < kGrpoSums; ++k) red[wv][k] = acc[k];
+    __syncthreads();
+    float sum = 0.f;
+    if (threadIdx.x < kGrpoSums) {
+        const int k = threadIdx.x;
+        sum = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+    }
+    publish_sums<kGrpoSums, 256>(sum, partials, fold);
+}
+
+// sums = scale * loss sum, sum w kl, sum w r, sum w clipped, sum w  ->  out4 = loss, mean_kl, mean_ratio, mean_clipped
+__global__ __launch_bounds__(64) void grpo_info_kernel(const float* __restrict__ sums, float* __restrict__ out4) {
+    const int k = threadIdx.x;
+    if (k >= 4) return;
+    const float sw = sums[4];
+    out4[k] = k == 0 ? sums[0] : (sw != 0.f ? sums[k] / sw : 0.f);
+}
+
+// ================================================================================================
+// the gradient: grad[row, v] = c ([v = a] - exp(x_v - lse)),  c = coef[row] g  (g NULL = 1; an action outside: c = 0)
+// ================================================================================================
+template <class Elem, bool WIDE, int NT>
+__global__ __launch_bounds__(256) void token_grad_kernel(const Elem* __restrict__ x, const int64_t* __restrict__ action,
+                                                         const float* __restrict__ lse, const float* __restrict__ coef,
+                                                         const float* __restrict__ g, Elem* __restrict__ grad, long rows,
+                                                         int V) {
+    using IO = ElemIO<Elem>;
+    constexpr int P = IO::P;
+    constexpr int RPW = 256 / NT;
+    const int tid = threadIdx.x % NT, sub = threadIdx.x / NT;
+    const float u = g ? g[0] : 1.f;
+    for (long r0 = (long)blockIdx.x * RPW; r0 < rows; r0 += (long)gridDim.x * RPW) {
+        const long row = r0 + sub;
+        if (row >= rows) continue;
+        const long a = action[row];
+        const bool inr = a >= 0 && a < (long)V;
+        const float c = inr ? coef[row] * u : 0.f;
+        const int ai = inr ? (int)a : -1;
+        const Elem* p = x + (size_t)row * (size_t)V;
+        Elem* o = grad + (size_t)row * (size_t)V;
+        if (c == 0.f) {   // nothing of the row is read
+            if (WIDE) {
+                const vuint4 z = {0u, 0u, 0u, 0u};
+                vuint4* ov = reinterpret_cast<vuint4*>(o);
+                for (int v = tid; v < V / P; v += NT) __builtin_nontemporal_store(z, ov + v);
+            } else {
+                for (int i = tid; i < V; i += NT) IO::put(o + i, 0.f);
+            }
+            continue;
+        }
+        const float l = lse[row];
+        if (WIDE) {
+            const int nvec = V / P;
+            const vuint4* __restrict__ pv = reinterpret_cast<const vuint4*>(p);
+            vuint4* ov = reinterpret_cast<vuint4*>(o);
+            for (int v = tid; v < nvec; v += kInFlight * NT) {
+                vuint4 r[kInFlight];
+#pragma unroll
+                for (int k = 0; k < kInFlight; ++k)
+                    if (v + k * NT < nvec) r[k] = __builtin_nontemporal_load(pv + v + k * NT);
+#pragma unroll
+                for (int k = 0; k < kInFlight; ++k)
+                    if (v + k * NT < nvec) {
+                        float xx[P];
+                        IO::unpack(r[k], xx);
+                        const int da = ai - (v + k * NT) * P;
+#pragma unroll
+                        for (int j = 0; j < P; ++j) {
+                            const float e = ex2((clampf(xx[j]) - l) * kLog2eG);
+                            xx[j] = fmaf(-c, e, da == j ? c : 0.f);
+                        }
+                        __builtin_nontemporal_store(IO::pack(xx), ov + v + k * NT);
+                    }
+            }
+        } else {
+            for (int i = tid; i < V; i += kInFlight * NT) {
+                float xx[kInFlight];
+#pragma unroll
+                for (int k = 0; k < kInFlight; ++k)
+                    if (i + k * NT < V) xx[k] = IO::get(p + i + k * NT);
+#pragma unroll
+                for (int k = 0; k < kInFlight; ++k)
+                    if (i + k * NT < V) {
+                        const float e = ex2((clampf(xx[k]) - l) * kLog2eG);
+                        IO::put(o + i + k * NT, fmaf(-c, e, ai == i + k * NT ? c : 0.f));
+                    }
+            }
+        }
+    }
+}
+
+template <class Elem>
+int token_grad_launch(const void* xv, const int64_t* action, const float* lse, const float* coef, const float* g, void* gradv,
+                      long rows, int V, hipStream_t st) {
+    const Elem* x = static_cast<const Elem*>(xv);
+    Elem* grad = static_cast<Elem*>(gradv);
+    const bool wide = aligned(x, 16) && aligned(grad, 16) && ((size_t)V * sizeof(Elem)) % 16 == 0;
+    const bool wide_row = V > kWaveRowMaxV;
+    const int rpw = wide_row ? 1 : 4;
+    const long grid = row_grid_of(rows, rpw);
+#define HPC_RLL_GRPO_GRAD(W_, NT_)                                                                                    \
+    hipLaunchKernelGGL((token_grad_kernel<Elem, W_, NT_>), dim3((unsigned)grid), dim3(256), 0, st, x, action, lse, coef, g, \
+                       grad, rows, V)
+    if (wide && wide_row) HPC_RLL_GRPO_GRAD(true, 256);
+    else if (wide) HPC_RLL_GRPO_GRAD(true, 64);
+    else if (wide_row) HPC_RLL_GRPO_GRAD(false, 256);
+    else HPC_RLL_GRPO_GRAD(false, 64);
+#undef HPC_RLL_GRPO_GRAD
+    const int rc = last_error();
+    if (!rc)
+        grpo_note(g_grpo_grad, {ElemIO<Elem>::kCode, wide ? 16 : (int)sizeof(Elem), wide_row ? 256 : 64, rpw, (int)grid});
+    return rc;
+}
+int token_grad_any(const void* x, int elem, const int64_t* action, const float* lse, const float* coef, const float* g,
+                   void* grad, long rows, int V, hipStream_t st) {
+    return elem == 1 ? token_grad_launch<uint16_t>(x, action, lse, coef, g, grad, rows, V, st)
+                     : token_grad_launch<float>(x, action, lse, coef, g, grad, rows, V, st);
+}
+
+bool elem_ok(int e) { return e == HPC_RLL_ELEM_F32 || e == HPC_RLL_ELEM_BF16; }
+size_t elem_size(int e) { return e == HPC_RLL_ELEM_BF16 ? 2 : 4; }
+
+}  // namespace
+}  // namespace hpc_rll
+
+using namespace hpc_rll;
+
+extern "C" int hpc_rll_token_logp_forward(const void* logits, int elem, const int64_t* action, const float* weight,
+                                          float* logp, float* lse, int64_t rows, int V, void* stream) {
+    const bool empty = rows == 0 || V == 0;
+    if (!empty && (!logits || !action || !logp)) return HPC_RLL_EINVAL;
+    if (rows < 0 || V < 0 || !elem_ok(elem)) return HPC_RLL_EINVAL;
+    if (!aligned(logits, elem_size(elem)) || !aligned(action, 8) || !aligned(weight, 4) || !aligned(logp, 4) ||
+        !aligned(lse, 4))
+        return HPC_RLL_EALIGN;
+    if (V > kGrpoMaxV) return HPC_RLL_EUNSUPPORTED;
+    if (empty) {   // V == 0 with rows: no token has a probability; zeros
+        if (rows > 0 && logp) {
+            int rc = (int)hipMemsetAsync(logp, 0, (size_t)rows * sizeof(float), (hipStream_t)stream);
+            if (!rc && lse) rc = (int)hipMemsetAsync(lse, 0, (size_t)rows * sizeof(float), (hipStream_t)stream);
+            return rc;
+        }
+        return HPC_RLL_OK;
+    }
+    return token_logp_any(logits, elem, action, weight, logp, lse, (long)rows, V, (hipStream_t)stream);
+}
+
+extern "C" int hpc_rll_token_logp_backward(const float* g_logp, const void* logits, int elem, const int64_t* action,
+                                           const float* lse, void* grad_logits, int64_t rows, int V, void* stream) {
+    const bool empty = rows == 0 || V == 0;
+    if (!empty && (!g_logp || !logits || !action || !lse || !grad_logits)) return HPC_RLL_EINVAL;
+    if (rows < 0 || V < 0 || !elem_ok(elem)) return HPC_RLL_EINVAL;
+    if (!aligned(logits, elem_size(elem)) || !aligned(grad_logits, elem_size(elem)) || !aligned(action, 8) ||
+        !aligned(g_logp, 4) || !aligned(lse, 4))
+        return HPC_RLL_EALIGN;
+    if (V > kGrpoMaxV) return HPC_RLL_EUNSUPPORTED;
+    if (empty) return HPC_RLL_OK;
+    return token_grad_any(logits, elem, action, lse, g_logp, nullptr, grad_logits, (long)rows, V, (hipStream_t)stream);
+}
+
+// ws (floats), R = B*S: lse (R) | coef (R) | logp of logit_new (R) | logp of old (R) | logp of ref (R) | the five sums (8) |
+// partial sums, five per workgroup of the token launch
+extern "C" int64_t hpc_rll_grpo_workspace_floats(int B, int S) {
+    if (B < 0 || S < 0) return HPC_RLL_EINVAL;
+    return 5 * (int64_t)B * S + 8 + 8 * (kFoldMaxGrid + 1);
+}
+
+extern "C" int hpc_rll_grpo_forward(const void* logit_new, int elem_new, const void* old, int old_kind, const void* ref,
+                                    int ref_kind, const int64_t* action, const float* adv, const float* weight, float* out4,
+                                    float* ws, int B, int S, int V, float clip_ratio, float beta, float scale, void* stream) {
+    const bool empty = B == 0 || S == 0 || V == 0;
+    auto kind_ok = [](int k) { return elem_ok(k) || k == HPC_RLL_GRPO_LOGP; };
+    if (!out4) return HPC_RLL_EINVAL;
+    if (!empty && (!logit_new || !old || !action || !adv || !ws)) return HPC_RLL_EINVAL;
+    if (B < 0 || S < 0 || V < 0 || !elem_ok(elem_new) || !kind_ok(old_kind) || (ref && !kind_ok(ref_kind))) return HPC_RLL_EINVAL;
+    if (!aligned(logit_new, elem_size(elem_new)) || !aligned(old, elem_size(old_kind)) || !aligned(ref, elem_size(ref_kind)) ||
+        !aligned(action, 8) || !aligned(adv, 4) || !aligned(weight, 4) || !aligned(out4, 4) || !aligned(ws, 4))
+        return HPC_RLL_EALIGN;
+    if (V > kGrpoMaxV) return HPC_RLL_EUNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    if (empty) return (int)hipMemsetAsync(out4, 0, 4 * sizeof(float), st);
+    const long R = (long)B * S;
+    float *lse = ws, *coef = ws + R, *pn = ws + 2 * R, *po_ws = ws + 3 * R, *pr_ws = ws + 4 * R, *sums = ws + 5 * R,
+          *partials = ws + 5 * R + 8;
+    int rc = token_logp_any(logit_new, elem_new, action, weight, pn, lse, R, V, st);
+    if (rc) return rc;
+    const float* po = static_cast<const float*>(old);
+    if (old_kind != HPC_RLL_GRPO_LOGP) {
+        rc = token_logp_any(old, old_kind, action, weight, po_ws, nullptr, R, V, st);
+        if (rc) return rc;
+        po = po_ws;
+    }
+    const float* pr = nullptr;
+    if (ref) {
+        pr = static_cast<const float*>(ref);
+        if (ref_kind != HPC_RLL_GRPO_LOGP) {
+            rc = token_logp_any(ref, ref_kind, action, weight, pr_ws, nullptr, R, V, st);
+            if (rc) return rc;
+            pr = pr_ws;
+        }
+    }
+    const float sc = scale > 0.f ? scale : 1.f / (float)B;
+    const GrpoTokenArgs p{pn, po, pr, action, adv, weight, coef, B, S, V, clip_ratio, ref ? beta : 0.f, sc};
+    long grid = ((long)B + 3) / 4;
+    if (grid > kFoldMaxGrid) grid = kFoldMaxGrid;
+    const float scales[kGrpoSums] = {sc, 1.f, 1.f, 1.f, 1.f};
+    const ScanFold fold = make_fold(st, kGrpoSums, scales, sums, grid);
+    hipLaunchKernelGGL(grpo_token_kernel, dim3((unsigned)grid), dim3(256), 0, st, p, partials, fold);
+    rc = last_error();
+    if (rc) return rc;
+    if (!fold.out) {
+        rc = finalize_sums(partials, (int)grid, kGrpoSums, scales, sums, st);
+        if (rc) return rc;
+    }
+    grpo_note(g_grpo_token, {256, (int)grid});
+    hipLaunchKernelGGL(grpo_info_kernel, dim3(1), dim3(64), 0, st, sums, out4);
+    return last_error();
+}
+
+extern "C" int hpc_rll_grpo_backward(const float* g_loss, const void* logit_new, int elem, const int64_t* action,
+                                     const float* ws, void* grad_logit, int B, int S, int V, void* stream) {
+    const bool empty = B == 0 || S == 0 || V == 0;
+    if (!empty && (!logit_new || !action || !ws || !grad_logit)) return HPC_RLL_EINVAL;
+    if (B < 0 || S < 0 || V < 0 || !elem_ok(elem)) return HPC_RLL_EINVAL;
+    if (!aligned(logit_new, elem_size(elem)) || !aligned(grad_logit, elem_size(elem)) || !aligned(action, 8) ||
+        !aligned(g_loss, 4) || !aligned(ws, 4))
+        return HPC_RLL_EALIGN;
+    if (V > kGrpoMaxV) return HPC_RLL_EUNSUPPORTED;
+    if (empty) return HPC_RLL_OK;
+    const long R = (long)B * S;
+    return token_grad_any(logit_new, elem, action, ws, ws + R, g_loss, grad_logit, R, V, (hipStream_t)stream);
+}
+
+extern "C" int hpc_rll_grpo_last_config(int* out) {
+    if (!out) return HPC_RLL_EINVAL;
+    auto put = [&](const int* rec, int n) {
+        out[0] = rec[0];
+        for (int i = 1; i < n; ++i) out[i] = rec[0] ? rec[i] : -1;   // no launch yet
+        out += n;
+    };
+    put(g_grpo_head, kHeadInts);
+    put(g_grpo_token, kTokenInts);
+    put(g_grpo_grad, kGradInts);
+    return HPC_RLL_OK;
+}
+static_assert(HPC_RLL_GRPO_CONFIG_INTS == kHeadInts + kTokenInts + kGradInts, "the layout documented in hpc_rll_hip.h");

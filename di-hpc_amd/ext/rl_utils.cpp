@@ -3,7 +3,7 @@
 // Two layers in one module:
 //   * the reference's L2 functions `XxxForward(inputs, outputs, scalars...)` / `XxxBackward(inputs, outputs)`
 //     (declared in include/hpc/rll/cuda/rl_utils/entry.h:10-165) -- validated, launched on torch's current stream;
-//   * fused autograd ops (`gae`, `td_lambda`, `vtrace`, `upgo`, `upgo_masked`, `ppo`, `ppo_continuous`, `vtrace_continuous`, `retrace_loss`, `acer_policy_loss`, `coma`, `r2d2_td`, `q_nstep_td`, `dist_nstep_td`, `iqn_nstep_td`,
+//   * fused autograd ops (`gae`, `td_lambda`, `vtrace`, `upgo`, `upgo_masked`, `ppo`, `ppo_continuous`, `vtrace_continuous`, `retrace_loss`, `acer_policy_loss`, `coma`, `r2d2_td`, `token_log_prob`, `grpo_policy_loss`, `q_nstep_td`, `dist_nstep_td`, `iqn_nstep_td`,
 //     `qrdqn_nstep_td`) -- torch::autograd::Function nodes that allocate outputs, launch and register backward in ONE
 //     pybind call; these are what hpc_rll.rl_utils.* modules use.
 // Host-only C++: every kernel lives behind the C ABI of libhpc_rll_hip.so (include/hpc_rll_hip.h).
@@ -1174,6 +1174,129 @@ struct R2d2Fn : public ag::Function<R2d2Fn> {
     }
 };
 
+// ========================================================================================================== GRPO
+// The language-model policy losses (hpc_rll_token_logp_*, hpc_rll_grpo_*): logits may be fp32 or bf16.  Shapes and dtypes are
+// checked before the device so that a wrong argument is named even on host tensors.
+at::ScalarType logits_dtype(const Tensor& t, const char* name) {
+    TORCH_CHECK(t.defined(), name, ": expected a tensor, got None");
+    const at::ScalarType st = t.scalar_type();
+    TORCH_CHECK(st == at::kFloat || st == at::kBFloat16, name, ": dtype ", st, ", expected ", at::kFloat, " or ", at::kBFloat16);
+    return st;
+}
+int elem_code(at::ScalarType st) { return st == at::kBFloat16 ? HPC_RLL_ELEM_BF16 : HPC_RLL_ELEM_F32; }
+void grpo_check_v(const char* op, int64_t V) {
+    TORCH_CHECK(V <= 262144, op, ": V = ", V, " is not supported (1 <= V <= 262144)");
+}
+
+// logp = logits[..., a] - logsumexp(logits); saves the logits, action and lse (4 bytes per token)
+struct TokenLogpFn : public ag::Function<TokenLogpFn> {
+    static Tensor forward(ag::AutogradContext* ctx, const Tensor& logits, const Tensor& action) {
+        const at::ScalarType st = logits_dtype(logits, "logits");
+        TORCH_CHECK(logits.dim() >= 1, "logits: expected (..., V), got ", logits.sizes());
+        const int64_t V = logits.size(-1);
+        check_shape(action, "action", logits.sizes().slice(0, logits.dim() - 1), at::kLong);
+        grpo_check_v("token_log_prob", V);
+        const at::Device dev = logits.device();
+        req(logits, "logits", dev, st);
+        req(action, "action", dev, at::kLong);
+        c10::DeviceGuard g(dev);
+        const int64_t rows = action.numel();
+        Tensor logp = new_f32(action.sizes(), dev), lse = new_f32({rows}, dev);
+        check(hpc_rll_token_logp_forward(vptr(logits), elem_code(st), iptr(action), nullptr, fmut(logp), fmut(lse), rows,
+                                         to_int(V, "V"), stream_of(dev)),
+              "hpc_rll_token_logp_forward");
+        ctx->save_for_backward({logits, action, lse});
+        return logp;
+    }
+    static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
+        ag::tensor_list out(2);
+        if (!ctx->needs_input_grad(0)) return out;
+        const auto saved = ctx->get_saved_variables();
+        const Tensor &logits = saved[0], &action = saved[1], &lse = saved[2];
+        const at::Device dev = logits.device();
+        c10::DeviceGuard g(dev);
+        Tensor gl = grads[0].contiguous();
+        req(gl, "grad_logp", dev);
+        Tensor grad = at::empty(logits.sizes(), logits.options());
+        check(hpc_rll_token_logp_backward(fptr(gl), vptr(logits), elem_code(logits.scalar_type()), iptr(action), fptr(lse),
+                                          grad.data_ptr(), action.numel(), (int)logits.size(-1), stream_of(dev)),
+              "hpc_rll_token_logp_backward");
+        out[0] = grad;
+        return out;
+    }
+};
+
+// (loss, mean_kl, mean_ratio, mean_clipped), (1,) each; the gradient flows to logit_new only.  Saves logit_new, action and the
+// workspace (lse and coef are what the backward reads).
+struct GrpoFn : public ag::Function<GrpoFn> {
+    // logits (B,S,V) of either element type, or log-probs (B,S) fp32: the number of dimensions decides
+    static int kind_of(const Tensor& t, const char* name, int64_t B, int64_t S, int64_t V) {
+        TORCH_CHECK(t.defined(), name, ": expected a tensor, got None");
+        TORCH_CHECK(t.dim() == 2 || t.dim() == 3, name, ": expected logits (B,S,V) or log-probs (B,S), got ", t.sizes());
+        if (t.dim() == 2) {
+            check_shape(t, name, {B, S});
+            return HPC_RLL_GRPO_LOGP;
+        }
+        const at::ScalarType st = logits_dtype(t, name);
+        check_shape(t, name, {B, S, V}, st);
+        return elem_code(st);
+    }
+    static ag::tensor_list forward(ag::AutogradContext* ctx, const Tensor& logit_new, const Tensor& old, const OptTensor& ref,
+                                   const Tensor& action, const Tensor& adv, const OptTensor& weight, double clip_ratio,
+                                   double beta, std::optional<double> scale) {
+        const at::ScalarType st = logits_dtype(logit_new, "logit_new");
+        TORCH_CHECK(logit_new.dim() == 3, "logit_new: expected (B,S,V), got ", logit_new.sizes());
+        const int64_t B = logit_new.size(0), S = logit_new.size(1), V = logit_new.size(2);
+        const int old_kind = kind_of(old, "old", B, S, V);
+        const int ref_kind = has(ref) ? kind_of(*ref, "ref", B, S, V) : HPC_RLL_GRPO_LOGP;
+        check_shape(action, "action", {B, S}, at::kLong);
+        check_shape(adv, "adv", {B});
+        if (has(weight)) check_shape(*weight, "weight", {B, S});
+        grpo_check_v("grpo_policy_loss", V);
+        const at::Device dev = logit_new.device();
+        req(logit_new, "logit_new", dev, st);
+        req(old, "old", dev, old.scalar_type());
+        if (has(ref)) req(*ref, "ref", dev, ref->scalar_type());
+        req(action, "action", dev, at::kLong);
+        req(adv, "adv", dev);
+        if (has(weight)) req(*weight, "weight", dev);
+        c10::DeviceGuard g(dev);
+        const bool empty = B == 0 || S == 0 || V == 0;
+        Tensor out4 = new_f32({4}, dev);
+        Tensor ws = new_f32({empty ? 0 : hpc_rll_grpo_workspace_floats(to_int(B, "B"), to_int(S, "S"))}, dev);
+        const float sc = scale.has_value() && *scale > 0.0 ? (float)*scale : 0.f;   // 0: the kernels take 1/B
+        check(hpc_rll_grpo_forward(vptr(logit_new), elem_code(st), vptr(old), old_kind, has(ref) ? vptr(*ref) : nullptr,
+                                   ref_kind, iptr(action), fptr(adv), fptr(weight), fmut(out4), fmut(ws), to_int(B, "B"),
+                                   to_int(S, "S"), to_int(V, "V"), (float)clip_ratio, (float)beta, sc, stream_of(dev)),
+              "hpc_rll_grpo_forward");
+        ctx->save_for_backward({logit_new, action, ws});
+        ctx->saved_data["empty"] = empty;
+        ag::tensor_list out = {alias_of(out4, 0, 1), alias_of(out4, 1, 1), alias_of(out4, 2, 1), alias_of(out4, 3, 1)};
+        ctx->mark_non_differentiable({out[1], out[2], out[3]});
+        return out;
+    }
+    static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
+        ag::tensor_list out(9);
+        if (!ctx->needs_input_grad(0)) return out;
+        const auto saved = ctx->get_saved_variables();
+        const Tensor &logit_new = saved[0], &action = saved[1], &ws = saved[2];
+        const at::Device dev = logit_new.device();
+        c10::DeviceGuard g(dev);
+        if (ctx->saved_data["empty"].toBool()) {
+            out[0] = at::zeros(logit_new.sizes(), logit_new.options());
+            return out;
+        }
+        Tensor gl = grad1(grads[0], dev, "grad_loss");
+        Tensor grad = at::empty(logit_new.sizes(), logit_new.options());
+        check(hpc_rll_grpo_backward(fptr(gl), vptr(logit_new), elem_code(logit_new.scalar_type()), iptr(action), fptr(ws),
+                                    grad.data_ptr(), (int)logit_new.size(0), (int)logit_new.size(1), (int)logit_new.size(2),
+                                    stream_of(dev)),
+              "hpc_rll_grpo_backward");
+        out[0] = grad;
+        return out;
+    }
+};
+
 // ==================================================================================================== q n-step TD
 struct QDims { int64_t B, N, nstep; at::Device dev; };
 int64_t check_nstep_reward(const Tensor& reward, int64_t B, const at::Device& dev) {
@@ -1777,6 +1900,18 @@ PYBIND11_MODULE(hpc_rl_utils, m) {
           py::arg("scale") = py::none(),
           "R2D2 sequence loss over a (T,B,N) unroll: (loss (1,), td_error (L,B), priority (B,)) with L = T - nstep - burnin; "
           "differentiable wrt q; scale = 1/(global count) for a sharded caller");
+    m.def("token_log_prob", [](const Tensor& logits, const Tensor& action) { return TokenLogpFn::apply(logits, action); },
+          py::arg("logits"), py::arg("action"),
+          "logits[..., a] - logsumexp(logits) per token: (..., V) fp32 or bf16 logits, (...) int64 actions -> (...) fp32; "
+          "differentiable wrt logits");
+    m.def("grpo_policy_loss", [](const Tensor& logit_new, const Tensor& old, const OptTensor& ref, const Tensor& action,
+                                 const Tensor& adv, const OptTensor& weight, double clip_ratio, double beta,
+                                 std::optional<double> scale) {
+        return GrpoFn::apply(logit_new, old, ref, action, adv, weight, clip_ratio, beta, scale);
+    }, py::arg("logit_new"), py::arg("old"), py::arg("ref"), py::arg("action"), py::arg("adv"),
+          py::arg("weight") = py::none(), py::arg("clip_ratio") = 0.2, py::arg("beta") = 0.1, py::arg("scale") = py::none(),
+          "GRPO token loss over (B,S,V) logits: (loss, mean_kl, mean_ratio, mean_clipped), (1,) each; old / ref are logits "
+          "(B,S,V) or log-probs (B,S), ref may be None; differentiable wrt logit_new; scale = 1/(global B) for a sharded caller");
     m.def("q_nstep_td", [](const Tensor& q, const Tensor& nq, const Tensor& action, const Tensor& naction,
                            const Tensor& reward, const Tensor& done, const OptTensor& weight, double gamma, bool rescale,
                            std::optional<double> scale) {

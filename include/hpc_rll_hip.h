@@ -449,6 +449,60 @@ int hpc_rll_r2d2_backward(const float* g_loss, const int64_t* action, const floa
                           int nstep, int burnin, void* stream);
 int hpc_rll_r2d2_last_config(int* out);
 
+/* Language-model policy losses: the per-token log-probability over a large vocabulary and GRPO's clipped-ratio + k3-KL token
+ * loss with per-sequence masked means (no reference counterpart; the semantics restate DI-engine's grpo_policy_error /
+ * rloo_policy_error and their log_prob_utils helper).  Logits are (rows, V) of element type HPC_RLL_ELEM_F32 or
+ * HPC_RLL_ELEM_BF16, contiguous, 1 <= V <= 262144; action (rows) int64; lp(x) = x[a] - logsumexp(x).  A row whose action is
+ * outside [0,V), or whose weight is 0, is DROPPED: its logits are not read (they may hold anything), logp = lse = 0, it
+ * adds nothing to any sum and its gradient row is exact zeros.  -inf logits are vocabulary entries of probability 0; a
+ * chosen token whose own logit is -inf is not supported.  NaN in a LIVE row is not propagated: the clamp that maps -inf to
+ * the most negative finite float maps NaN there too, so such an entry counts with probability 0 (as hpc_rll_categorical_*).
+ * hpc_rll_token_logp_forward -- one launch, one read of every live row: logp (rows), lse (rows; may be NULL); weight
+ *   (rows; may be NULL) only selects the rows to drop.
+ * hpc_rll_token_logp_backward -- one streaming launch: grad_logits[r,v] = g_logp[r] ([v = a] - exp(x_v - lse[r])) in the
+ *   logits' element type (bf16: round to nearest even); a row with g_logp[r] == 0 is zero-filled without reading its logits.
+ * hpc_rll_grpo_forward -- logit_new (B,S,V) of elem_new; old and ref are logits (kind = their element type) or per-token
+ *   log-probs (B,S) fp32 (kind HPC_RLL_GRPO_LOGP); ref may be NULL (no KL term, beta ignored: RLOO / token-level PPO);
+ *   adv (B); weight (B,S) or NULL (= ones).  Per token, with pn, po, pr the three log-probs:
+ *     d = pr - pn, kl = exp(d) - d - 1, r = exp(pn - po), rc = clamp(r, 1 - clip, 1 + clip),
+ *     l = -min(r adv_b, rc adv_b) + beta kl,  dl/dpn = -adv_b r [not (rc adv_b < r adv_b)] - beta (exp(d) - 1);
+ *     loss = scale sum_b (sum_s w l / sum_s w)   (scale <= 0: 1/B; a sequence with sum_s w = 0 contributes 0);
+ *   out4 = loss, mean_kl, mean_ratio, mean_clipped, the last three sum w x / sum w over all tokens for x = kl, r,
+ *   [r > 1 + clip or r < 1 - clip].  One head launch per logits tensor, the token launch (a wave per sequence, fixed-order
+ *   sums, no float atomics), a one-workgroup launch that forms the three means.  ws: hpc_rll_grpo_workspace_floats(B,S)
+ *   floats, with R = B*S the layout is
+ *   lse (R) | coef (R): w scale / (sum_s w) dl/dpn | logp of logit_new, old, ref (R each) | the five sums (8) | partial sums.
+ *   B == 0, S == 0 or V == 0 zeroes out4 and launches nothing.
+ * hpc_rll_grpo_backward -- one streaming launch: grad_logit[b,s,v] = g coef ([v = a] - exp(x_v - lse)) in logit_new's
+ *   element type; g_loss is a device scalar (NULL = 1); a row whose g coef is exactly 0 is zero-filled without reading its
+ *   logits (decided on the device).  ws as the forward left it (lse and coef are read).
+ * hpc_rll_grpo_last_config -- out[HPC_RLL_GRPO_CONFIG_INTS] = {
+ *    [0..6]   the head launch last issued: launches so far, element type, bytes per load of the row's body (16), peeled (1:
+ *             the elements outside the row's 16-byte grid are loaded one by one; 0: base and pitch are on 16 bytes),
+ *             threads per row (64: a wave per row; 256: a workgroup per row), rows per workgroup, workgroups,
+ *    [7..9]   the token launch: launches so far, threads per workgroup, workgroups,
+ *    [10..15] the gradient launch: launches so far, element type, bytes per load and store (16, or the element's size when
+ *             a base or the pitch is off 16 bytes), threads per row, rows per workgroup, workgroups };
+ *   each of the three parts is {0, -1 ...} before its first launch; HPC_RLL_EINVAL for out == NULL.
+ * Argument errors of the first four, before any HIP call: HPC_RLL_EINVAL (null operands, then negative sizes or an unknown
+ * element type / kind), HPC_RLL_EALIGN (a float array off 4-byte alignment, action off 8, logits off their element size),
+ * then HPC_RLL_EUNSUPPORTED (V > 262144); then empty shapes return 0. */
+#define HPC_RLL_ELEM_F32 (0)
+#define HPC_RLL_ELEM_BF16 (1)
+#define HPC_RLL_GRPO_LOGP (2)
+#define HPC_RLL_GRPO_CONFIG_INTS (16)
+int hpc_rll_token_logp_forward(const void* logits, int elem, const int64_t* action, const float* weight, float* logp,
+                               float* lse, int64_t rows, int V, void* stream);
+int hpc_rll_token_logp_backward(const float* g_logp, const void* logits, int elem, const int64_t* action, const float* lse,
+                                void* grad_logits, int64_t rows, int V, void* stream);
+int64_t hpc_rll_grpo_workspace_floats(int B, int S);
+int hpc_rll_grpo_forward(const void* logit_new, int elem_new, const void* old, int old_kind, const void* ref, int ref_kind,
+                         const int64_t* action, const float* adv, const float* weight, float* out4, float* ws, int B, int S,
+                         int V, float clip_ratio, float beta, float scale, void* stream);
+int hpc_rll_grpo_backward(const float* g_loss, const void* logit_new, int elem, const int64_t* action, const float* ws,
+                          void* grad_logit, int B, int S, int V, void* stream);
+int hpc_rll_grpo_last_config(int* out);
+
 /* PPO -- replaces PPOForward/Backward (rl_utils/entry.h:158-165, src/rl_utils/ppo.cu:8-111).
  * logits (B,N), action (B,), value_new/old, adv, ret, weight (B,) (weight NULL = ones).
  * out5 = policy_loss, value_loss, entropy_loss, approx_kl, clipfrac.  dual_clip < 1 disables dual clip
