@@ -93,11 +93,17 @@ template <int CTRL, int ROW_MASK> __device__ __forceinline__ float row_fetch(flo
                                                                  CTRL, ROW_MASK, 0xF, false));
 }
 struct RowAcc { float m, s, t, xa; };
+// A part whose columns are ALL masked has m = -FLT_MAX and s = its column count (every exp(0) is 1), so against a part with a
+// real maximum d = -FLT_MAX - m ~ -3.4e38, w = exp(d) = 0 and d * s overflows to -inf as soon as s >= 2: w * (d * s) was
+// 0 * -inf = NaN in the entropy of a row whose 16-lane part holds no valid action ("the first K of N actions are valid").
+// Bounding d below keeps d * s finite (s <= 512 columns per part) where exp(d) is 0 anyway: one v_max_f32 per side, and no
+// bit changes for any d above the bound, i.e. for every pair of parts that each hold a real logit.
+constexpr float kMergeFloor = -1.0e30f;
 // merge the statistics of two disjoint parts of a row (each relative to its own maximum)
 __device__ __forceinline__ RowAcc merge(const RowAcc& a, const RowAcc& b) {
     RowAcc r;
     r.m = MaxOp::f(a.m, b.m);
-    const float da = a.m - r.m, db = b.m - r.m;
+    const float da = fmaxf(a.m - r.m, kMergeFloor), db = fmaxf(b.m - r.m, kMergeFloor);
     const float wa = __expf(da), wb = __expf(db);
     r.s = a.s * wa + b.s * wb;
     r.t = wa * fmaf(da, a.s, a.t) + wb * fmaf(db, b.s, b.t);
@@ -723,6 +729,15 @@ namespace {
 constexpr int kRowPieces = 8;
 constexpr int kMaxE = 8;   // row_cfg(...).e > kMaxE means "use the long-row fallback"
 
+// The dispatch record (hpc_rll_categorical_last_config): plain ints of the host process, like the scan family's; not
+// synchronised.  One row per direction (0 forward, the fused PPO forward included; 1 backward), [0] = launches so far (zero at
+// load), written where the kernel is launched so that it names the instantiation that ran, not a second evaluation of the rule.
+int g_cat_last[2][HPC_RLL_CATEGORICAL_CONFIG_INTS];
+void cat_note(int dir, int family, int g, int vec, int e, int r, bool ent, long grid) {
+    const int vals[HPC_RLL_CATEGORICAL_CONFIG_INTS] = {g_cat_last[dir][0] + 1, family, g, vec, e, r, ent ? 1 : 0, (int)grid};
+    for (int i = 0; i < HPC_RLL_CATEGORICAL_CONFIG_INTS; ++i) g_cat_last[dir][i] = vals[i];
+}
+
 // the (G, VEC, E) of row_cfg(N, ., kRowPieces) below that fallback: N <= 64 lanes x kMaxE pieces x 4 floats
 #define HPC_RLL_CAT_TABLE(CASE, ...)                                                                       \
     CASE(1, 1, 1, __VA_ARGS__) CASE(2, 1, 1, __VA_ARGS__) CASE(4, 1, 1, __VA_ARGS__) CASE(8, 1, 1, __VA_ARGS__)     \
@@ -741,25 +756,26 @@ constexpr bool cat_table_complete() {
 }
 static_assert(cat_table_complete(), "HPC_RLL_CAT_TABLE misses a configuration row_cfg(N, ., kRowPieces) returns with e <= kMaxE");
 
-#define HPC_RLL_ROW_CASE(G_, V_, E_, KERNEL, ...)                                                         \
+#define HPC_RLL_ROW_CASE(G_, V_, E_, KERNEL, DIR, ENT, ...)                                               \
     if (cfg.g == G_ && cfg.vec == V_ && cfg.e == E_) {                                                    \
-        hipLaunchKernelGGL((KERNEL<G_, V_, E_>),                                                           \
-                           dim3(row_grid(rows, (256 / G_) * RowsPerIter<V_, E_>::value, kRowGridCap)), dim3(256), 0, st, \
-                           __VA_ARGS__);                                                                  \
+        constexpr int R_ = RowsPerIter<V_, E_>::value;                                                    \
+        const unsigned grid = row_grid(rows, (256 / G_) * R_, kRowGridCap);                               \
+        hipLaunchKernelGGL((KERNEL<G_, V_, E_>), dim3(grid), dim3(256), 0, st, __VA_ARGS__);              \
+        cat_note(DIR, HPC_RLL_CAT_FAMILY_ROW, G_, V_, E_, R_, ENT, (long)grid);                           \
         return true;                                                                                      \
     }
-#define HPC_RLL_ROW_DISPATCH(KERNEL, ...) HPC_RLL_CAT_TABLE(HPC_RLL_ROW_CASE, KERNEL, __VA_ARGS__) return false;
+#define HPC_RLL_ROW_DISPATCH(KERNEL, DIR, ENT, ...) HPC_RLL_CAT_TABLE(HPC_RLL_ROW_CASE, KERNEL, DIR, ENT, __VA_ARGS__) return false;
 
 bool launch_fwd(const RowCfg& cfg, hipStream_t st, const float* logits, const int64_t* action, float* logp,
                 float* ent, long rows, int N) {
     if (ent) {
-        HPC_RLL_ROW_DISPATCH(categorical_fwd_kernel, logits, action, logp, ent, rows, N)
+        HPC_RLL_ROW_DISPATCH(categorical_fwd_kernel, 0, true, logits, action, logp, ent, rows, N)
     }
-    HPC_RLL_ROW_DISPATCH(categorical_fwd_noent_kernel, logits, action, logp, ent, rows, N)
+    HPC_RLL_ROW_DISPATCH(categorical_fwd_noent_kernel, 0, false, logits, action, logp, ent, rows, N)
 }
 bool launch_bwd(const RowCfg& cfg, hipStream_t st, const float* logits, const int64_t* action, const float* c1,
                 const float* g1, const float* c2, const float* g2, float* grad, long rows, int N) {
-    HPC_RLL_ROW_DISPATCH(categorical_bwd_kernel, logits, action, c1, g1, c2, g2, grad, rows, N)
+    HPC_RLL_ROW_DISPATCH(categorical_bwd_kernel, 1, c2 != nullptr, logits, action, c1, g1, c2, g2, grad, rows, N)
 }
 
 #define HPC_RLL_PPO_CASE(G_, V_, E_)                                                                                      \
@@ -770,6 +786,7 @@ bool launch_bwd(const RowCfg& cfg, hipStream_t st, const float* logits, const in
         const ScanFold fold = make_fold(st, PpoOp::NACC, scales, out5, grid);                                             \
         hipLaunchKernelGGL((ppo_fwd_fused_kernel<G_, V_, E_>), dim3((unsigned)grid), dim3(256), 0, st, logits_new,        \
                            logits_old, action, op, rows, N, partials, fold);                                              \
+        cat_note(0, HPC_RLL_CAT_FAMILY_PPO_FUSED, G_, V_, E_, 4, true, grid);                                             \
         *rc = last_error();                                                                                               \
         if (*rc == HPC_RLL_OK && !fold.out) *rc = finalize_sums(partials, (int)grid, PpoOp::NACC, scales, out5, st);      \
         return true;                                                                                                      \
@@ -801,10 +818,12 @@ int categorical_forward(const float* logits, const int64_t* action, float* logp,
     if (rows == 0) return HPC_RLL_OK;
     if (!logits || !action || !logp) return HPC_RLL_EINVAL;
     if ((N % 4) != 0 && N <= kSmallMaxN && aligned(logits, 16)) {
-        hipLaunchKernelGGL(categorical_small_kernel<false>, dim3(row_grid(rows, kSmallRows, kRowGridCap)), dim3(256),
+        const unsigned grid = row_grid(rows, kSmallRows, kRowGridCap);
+        hipLaunchKernelGGL(categorical_small_kernel<false>, dim3(grid), dim3(256),
                            (size_t)kSmallRows * N * sizeof(float), st, logits,
                            action, logp, ent, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
                            (const float*)nullptr, (float*)nullptr, rows, N);
+        cat_note(0, HPC_RLL_CAT_FAMILY_SMALL, 0, 0, 0, kSmallRows, ent != nullptr, (long)grid);
         return last_error();
     }
     const RowCfg cfg = row_cfg(N, aligned(logits, 16), kRowPieces);
@@ -816,13 +835,18 @@ int categorical_forward(const float* logits, const int64_t* action, float* logp,
                            (float*)nullptr, rows, N)
         if (N <= 4096) HPC_RLL_BLOCKROW(4); else if (N <= 8192) HPC_RLL_BLOCKROW(8); else HPC_RLL_BLOCKROW(16);
 #undef HPC_RLL_BLOCKROW
+        cat_note(0, HPC_RLL_CAT_FAMILY_BLOCKROW, 0, 0, N <= 4096 ? 4 : (N <= 8192 ? 8 : 16), 1, ent != nullptr, (long)grid.x);
     } else if (cfg.e > kMaxE && N <= 16384) {
-        hipLaunchKernelGGL(categorical_ldsrow_kernel<false>, dim3(row_grid(rows, 1, kRowGridCap)), dim3(256), (size_t)N * sizeof(float),
+        const unsigned grid = row_grid(rows, 1, kRowGridCap);
+        hipLaunchKernelGGL(categorical_ldsrow_kernel<false>, dim3(grid), dim3(256), (size_t)N * sizeof(float),
                            st, logits, action, logp, ent, (const float*)nullptr, (const float*)nullptr,
                            (const float*)nullptr, (const float*)nullptr, (float*)nullptr, rows, N);
+        cat_note(0, HPC_RLL_CAT_FAMILY_LDSROW, 0, 0, 0, 1, ent != nullptr, (long)grid);
     } else if (cfg.e > kMaxE || !launch_fwd(cfg, st, logits, action, logp, ent, rows, N)) {
-        hipLaunchKernelGGL(categorical_fwd_long_kernel, dim3(row_grid(rows, 4, kRowGridCap)), dim3(256), 0, st, logits, action,
+        const unsigned grid = row_grid(rows, 4, kRowGridCap);
+        hipLaunchKernelGGL(categorical_fwd_long_kernel, dim3(grid), dim3(256), 0, st, logits, action,
                            logp, ent, rows, N);
+        cat_note(0, HPC_RLL_CAT_FAMILY_LONG, 0, 0, 0, 4, ent != nullptr, (long)grid);
     }
     return last_error();
 }
@@ -833,9 +857,11 @@ int categorical_backward(const float* logits, const int64_t* action, const float
     if (rows == 0) return HPC_RLL_OK;
     if (!logits || !action || !c1 || !grad) return HPC_RLL_EINVAL;
     if ((N % 4) != 0 && N <= kSmallMaxN && aligned(logits, 16) && aligned(grad, 16)) {
-        hipLaunchKernelGGL(categorical_small_kernel<true>, dim3(row_grid(rows, kSmallRows, kRowGridCap)), dim3(256),
+        const unsigned grid = row_grid(rows, kSmallRows, kRowGridCap);
+        hipLaunchKernelGGL(categorical_small_kernel<true>, dim3(grid), dim3(256),
                            (size_t)kSmallRows * N * sizeof(float), st, logits,
                            action, (float*)nullptr, (float*)nullptr, c1, g1, c2, g2, grad, rows, N);
+        cat_note(1, HPC_RLL_CAT_FAMILY_SMALL, 0, 0, 0, kSmallRows, c2 != nullptr, (long)grid);
         return last_error();
     }
     const RowCfg cfg = row_cfg(N, aligned(logits, 16) && aligned(grad, 16), kRowPieces);
@@ -846,12 +872,17 @@ int categorical_backward(const float* logits, const int64_t* action, const float
                            (float*)nullptr, (float*)nullptr, c1, g1, c2, g2, grad, rows, N)
         if (N <= 4096) HPC_RLL_BLOCKROW(4); else if (N <= 8192) HPC_RLL_BLOCKROW(8); else HPC_RLL_BLOCKROW(16);
 #undef HPC_RLL_BLOCKROW
+        cat_note(1, HPC_RLL_CAT_FAMILY_BLOCKROW, 0, 0, N <= 4096 ? 4 : (N <= 8192 ? 8 : 16), 1, c2 != nullptr, (long)grid.x);
     } else if (cfg.e > kMaxE && N <= 16384) {
-        hipLaunchKernelGGL(categorical_ldsrow_kernel<true>, dim3(row_grid(rows, 1, kRowGridCap)), dim3(256), (size_t)N * sizeof(float),
+        const unsigned grid = row_grid(rows, 1, kRowGridCap);
+        hipLaunchKernelGGL(categorical_ldsrow_kernel<true>, dim3(grid), dim3(256), (size_t)N * sizeof(float),
                            st, logits, action, (float*)nullptr, (float*)nullptr, c1, g1, c2, g2, grad, rows, N);
+        cat_note(1, HPC_RLL_CAT_FAMILY_LDSROW, 0, 0, 0, 1, c2 != nullptr, (long)grid);
     } else if (cfg.e > kMaxE || !launch_bwd(cfg, st, logits, action, c1, g1, c2, g2, grad, rows, N)) {
-        hipLaunchKernelGGL(categorical_bwd_long_kernel, dim3(row_grid(rows, 4, kRowGridCap)), dim3(256), 0, st, logits, action,
+        const unsigned grid = row_grid(rows, 4, kRowGridCap);
+        hipLaunchKernelGGL(categorical_bwd_long_kernel, dim3(grid), dim3(256), 0, st, logits, action,
                            c1, g1, c2, g2, grad, rows, N);
+        cat_note(1, HPC_RLL_CAT_FAMILY_LONG, 0, 0, 0, 4, c2 != nullptr, (long)grid);
     }
     return last_error();
 }
@@ -868,4 +899,12 @@ extern "C" int hpc_rll_categorical_backward(const float* logits, const int64_t* 
                                             float* grad_logits, int64_t rows, int N, void* stream) {
     return hpc_rll::categorical_backward(logits, action, coef_logp, g_logp, coef_ent, g_ent, grad_logits, (long)rows,
                                          N, (hipStream_t)stream);
+}
+
+extern "C" int hpc_rll_categorical_last_config(int direction, int* out) {
+    if ((direction != HPC_RLL_CAT_DIR_FORWARD && direction != HPC_RLL_CAT_DIR_BACKWARD) || !out) return HPC_RLL_EINVAL;
+    const int* rec = hpc_rll::g_cat_last[direction];
+    out[0] = rec[0];
+    for (int i = 1; i < HPC_RLL_CATEGORICAL_CONFIG_INTS; ++i) out[i] = rec[0] ? rec[i] : -1;   // no launch yet
+    return HPC_RLL_OK;
 }

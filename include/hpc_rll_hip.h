@@ -162,6 +162,31 @@ int hpc_rll_categorical_forward(const float* logits, const int64_t* action, floa
 int hpc_rll_categorical_backward(const float* logits, const int64_t* action, const float* coef_logp,
                                  const float* g_logp, const float* coef_ent, const float* g_ent,
                                  float* grad_logits, int64_t rows, int N, void* stream);
+/* Diagnostic (no reference counterpart; read-only, modelled on hpc_rll_gae_last_config / hpc_rll_acer_last_config): which
+ * categorical kernel the most recent launch of this process ran, recorded on the host where the kernel is launched.
+ * direction HPC_RLL_CAT_DIR_FORWARD covers hpc_rll_categorical_forward and every op that runs the head's forward (V-trace,
+ * UPGO, PPO -- its one-launch fused forward included); HPC_RLL_CAT_DIR_BACKWARD covers hpc_rll_categorical_backward and
+ * those ops' backward.  out[HPC_RLL_CATEGORICAL_CONFIG_INTS] = {
+ *    [0] launches in this direction so far (0 = no launch yet: every other entry is then -1),
+ *    [1] kernel family, one of HPC_RLL_CAT_FAMILY_*,
+ *    [2] G, [3] VEC, [4] E: lanes per row, floats per load, loads per lane and row (ROW and PPO_FUSED; BLOCKROW reports its
+ *        E = float4 loads per thread, 4 / 8 / 16, with G = VEC = 0; the other families report 0, 0, 0),
+ *    [5] R: rows per lane group and iteration (ROW: 4 / 2 / 1, PPO_FUSED: 4); for the families without lane groups the rows
+ *        per WORKGROUP and iteration (SMALL 256, BLOCKROW 1, LDSROW 1, LONG 4),
+ *    [6] 1 = the entropy half runs (forward: entropy != NULL; backward: coef_ent != NULL; PPO_FUSED: always), 0 = it does not,
+ *    [7] workgroups of the launch }.
+ * Calls that return before launching (rows == 0, argument errors) leave the record as it was.  Plain ints of the host
+ * process, not synchronised.  HPC_RLL_EINVAL for a direction outside the two or out == NULL. */
+#define HPC_RLL_CAT_DIR_FORWARD (0)
+#define HPC_RLL_CAT_DIR_BACKWARD (1)
+#define HPC_RLL_CAT_FAMILY_ROW (0)        /* a row per group of G lanes, in registers: the 20 (G, VEC, E) configurations */
+#define HPC_RLL_CAT_FAMILY_SMALL (1)      /* N % 4 != 0, N <= 32, 16-byte aligned bases: 256 rows per workgroup through LDS */
+#define HPC_RLL_CAT_FAMILY_BLOCKROW (2)   /* 2048 < N <= 16384, 16-byte loads: a row per workgroup, in registers */
+#define HPC_RLL_CAT_FAMILY_LDSROW (3)     /* 512 < N <= 16384 with 4-byte loads: a row per workgroup, in LDS */
+#define HPC_RLL_CAT_FAMILY_LONG (4)       /* N > 16384: a row per wave, three passes */
+#define HPC_RLL_CAT_FAMILY_PPO_FUSED (5)  /* PPO's forward in one launch (both heads and the sample arithmetic) */
+#define HPC_RLL_CATEGORICAL_CONFIG_INTS (8)
+int hpc_rll_categorical_last_config(int direction, int* out);
 
 /* Path switches (a test / measurement hook, not a serving API; csrc/tune.hip holds the table): process-global plain ints,
  * not synchronised -- set them while no other thread is launching work, and never between an LSTM forward and its backward.

@@ -126,7 +126,9 @@ def _mask(rng, logits, action, frac=0.3):
 def test_masked_actions_vtrace_ppo(T, B, N):
     """Masked actions arrive as logits = -inf: probability 0, no entropy contribution, zero gradient -- what
     torch.distributions.Categorical (hpc_rll.origin's softmax/entropy, origin/vtrace.py:76-79, origin/ppo.py:57-61)
-    does by clamping log p to the most negative finite float.  Every row shape of the categorical kernels."""
+    does by clamping log p to the most negative finite float.  Seven action counts and a random 30 % mask at the op level:
+    one N for some of the categorical kernels, and no mask that empties a whole part of a row.  Every kernel of the head,
+    per row, with block masks ("only the first K valid"), is tests/test_categorical_head_gpu.py."""
     from hpc_rll.rl_utils.ppo import PPO
     from hpc_rll.rl_utils.vtrace import VTrace
     rng = np.random.default_rng(N + T)
