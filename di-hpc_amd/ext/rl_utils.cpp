@@ -3,7 +3,7 @@
 // Two layers in one module:
 //   * the reference's L2 functions `XxxForward(inputs, outputs, scalars...)` / `XxxBackward(inputs, outputs)`
 //     (declared in include/hpc/rll/cuda/rl_utils/entry.h:10-165) -- validated, launched on torch's current stream;
-//   * fused autograd ops (`gae`, `td_lambda`, `vtrace`, `upgo`, `upgo_masked`, `ppo`, `ppo_continuous`, `vtrace_continuous`, `retrace_loss`, `acer_policy_loss`, `coma`, `r2d2_td`, `token_log_prob`, `grpo_policy_loss`, `q_nstep_td`, `dist_nstep_td`, `iqn_nstep_td`,
+//   * fused autograd ops (`gae`, `td_lambda`, `vtrace`, `upgo`, `upgo_masked`, `ppo`, `ppo_continuous`, `vtrace_continuous`, `retrace_loss`, `acer_policy_loss`, `coma`, `r2d2_td`, `sac_discrete`, `token_log_prob`, `grpo_policy_loss`, `q_nstep_td`, `dist_nstep_td`, `iqn_nstep_td`,
 //     `qrdqn_nstep_td`) -- torch::autograd::Function nodes that allocate outputs, launch and register backward in ONE
 //     pybind call; these are what hpc_rll.rl_utils.* modules use.
 // Host-only C++: every kernel lives behind the C ABI of libhpc_rll_hip.so (include/hpc_rll_hip.h).
@@ -1174,6 +1174,99 @@ struct R2d2Fn : public ag::Function<R2d2Fn> {
     }
 };
 
+// ========================================================================================================== SAC
+// Soft Actor-Critic for discrete actions (hpc_rll_sac_discrete_*; DI-engine's DiscreteSACPolicy._forward_learn).  logit and its
+// five siblings are (..., N), the per-sample tensors have the leading shape.  Shapes and dtypes are checked before the device
+// so that a wrong argument is named even on host tensors.  The gradient flows to logit, q1 and q2; each is formed only when
+// its input needs it.  Saves the unit gradient of logit (allocated only when it is wanted), action and the workspace.
+struct SacDiscreteFn : public ag::Function<SacDiscreteFn> {
+    static ag::tensor_list forward(ag::AutogradContext* ctx, const Tensor& logit, const Tensor& next_logit, const Tensor& q1,
+                                   const OptTensor& q2, const Tensor& target_q1, const OptTensor& target_q2,
+                                   const Tensor& action, const Tensor& reward, const OptTensor& done, const OptTensor& weight,
+                                   double alpha, const OptTensor& alpha_t, double gamma, std::optional<double> scale,
+                                   bool want_grad) {
+        TORCH_CHECK(logit.defined(), "logit: expected a tensor, got None");
+        TORCH_CHECK(logit.dim() >= 1, "logit: expected (..., N), got ", logit.sizes());
+        TORCH_CHECK(has(q2) == has(target_q2), "sac_discrete: q2 and target_q2 are both given or both None (got ",
+                    has(q2) ? "q2" : "target_q2", " alone)");
+        const at::IntArrayRef full = logit.sizes(), lead = full.slice(0, full.size() - 1);
+        const int64_t N = full.back();
+        check_shape(logit, "logit", full);
+        check_shape(next_logit, "next_logit", full);
+        check_shape(q1, "q1", full);
+        if (has(q2)) check_shape(*q2, "q2", full);
+        check_shape(target_q1, "target_q1", full);
+        if (has(target_q2)) check_shape(*target_q2, "target_q2", full);
+        check_shape(action, "action", lead, at::kLong);
+        check_shape(reward, "reward", lead);
+        int code = HPC_RLL_MASK_U8;
+        if (has(done)) {
+            code = mask_code(*done, "done");
+            TORCH_CHECK(done->sizes() == lead, "done: shape ", done->sizes(), ", expected ", lead);
+        }
+        if (has(weight)) check_shape(*weight, "weight", lead);
+        if (has(alpha_t)) {
+            TORCH_CHECK(alpha_t->scalar_type() == at::kFloat, "alpha: dtype ", alpha_t->scalar_type(), ", expected ", at::kFloat);
+            TORCH_CHECK(alpha_t->numel() == 1, "alpha: expected a float or a 1-element tensor, got shape ", alpha_t->sizes());
+        }
+        retrace_check_n("sac_discrete", N);
+        const at::Device dev = logit.device();
+        req(logit, "logit", dev);
+        req(next_logit, "next_logit", dev);
+        req(q1, "q1", dev);
+        if (has(q2)) req(*q2, "q2", dev);
+        req(target_q1, "target_q1", dev);
+        if (has(target_q2)) req(*target_q2, "target_q2", dev);
+        req(action, "action", dev, at::kLong);
+        req(reward, "reward", dev);
+        if (has(done)) req(*done, "done", dev, done->scalar_type());
+        if (has(weight)) req(*weight, "weight", dev);
+        if (has(alpha_t)) req(*alpha_t, "alpha", dev);
+        c10::DeviceGuard g(dev);
+        const int64_t rows = action.numel();
+        Tensor out4 = new_f32({4}, dev);
+        Tensor td = new_f32(lead, dev), tq = new_f32(lead, dev);
+        Tensor unit = (want_grad && rows > 0) ? new_f32(full, dev) : undef();
+        Tensor ws = new_f32({rows > 0 ? hpc_rll_sac_discrete_workspace_floats(rows) : 0}, dev);
+        check(hpc_rll_sac_discrete_forward(fptr(logit), fptr(next_logit), fptr(q1), fptr(q2), fptr(target_q1), fptr(target_q2),
+                                           iptr(action), fptr(reward), has(done) ? vptr(*done) : nullptr, code, fptr(weight),
+                                           fptr(alpha_t), (float)alpha, fmut(out4), fmut(td), fmut(tq), fmut(unit), fmut(ws),
+                                           rows, to_int(N, "N"), (float)gamma, loss_scale(scale, rows), stream_of(dev)),
+              "hpc_rll_sac_discrete_forward");
+        ctx->save_for_backward({unit, action, ws});
+        ctx->saved_data["N"] = N;
+        Tensor policy = alias_of(out4, 0, 1), critic = alias_of(out4, 1, 1), twin = alias_of(out4, 2, 1),
+               ent = alias_of(out4, 3, 1);
+        ctx->mark_non_differentiable({ent, td, tq});
+        return {policy, critic, twin, ent, td, tq};
+    }
+    static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
+        ag::tensor_list out(15);
+        const bool need_l = ctx->needs_input_grad(0), need_1 = ctx->needs_input_grad(2), need_2 = ctx->needs_input_grad(3);
+        if (!(need_l || need_1 || need_2)) return out;
+        const auto saved = ctx->get_saved_variables();
+        const Tensor &unit = saved[0], &action = saved[1], &ws = saved[2];
+        const at::Device dev = action.device();
+        c10::DeviceGuard g(dev);
+        const int64_t N = ctx->saved_data["N"].toInt(), rows = action.numel();
+        std::vector<int64_t> full(action.sizes().begin(), action.sizes().end());
+        full.push_back(N);
+        TORCH_CHECK(!need_l || rows == 0 || unit.defined(), "sac_discrete: the logit gradient was not stored by the forward");
+        Tensor g_p = grad1(grads[0], dev, "grad_policy_loss"), g_1 = grad1(grads[1], dev, "grad_critic_loss"),
+               g_2 = grad1(grads[2], dev, "grad_twin_critic_loss");
+        Tensor grad_l = need_l ? new_f32(full, dev) : undef();
+        Tensor grad_1 = need_1 ? new_f32(full, dev) : undef();
+        Tensor grad_2 = need_2 ? new_f32(full, dev) : undef();
+        check(hpc_rll_sac_discrete_backward(fptr(g_p), fptr(g_1), fptr(g_2), fptr(unit), iptr(action), fptr(ws), fmut(grad_l),
+                                            fmut(grad_1), fmut(grad_2), rows, (int)N, stream_of(dev)),
+              "hpc_rll_sac_discrete_backward");
+        out[0] = grad_l;
+        out[2] = grad_1;
+        out[3] = grad_2;
+        return out;
+    }
+};
+
 // ========================================================================================================== GRPO
 // The language-model policy losses (hpc_rll_token_logp_*, hpc_rll_grpo_*): logits may be fp32 or bf16.  Shapes and dtypes are
 // checked before the device so that a wrong argument is named even on host tensors.
@@ -1900,6 +1993,22 @@ PYBIND11_MODULE(hpc_rl_utils, m) {
           py::arg("scale") = py::none(),
           "R2D2 sequence loss over a (T,B,N) unroll: (loss (1,), td_error (L,B), priority (B,)) with L = T - nstep - burnin; "
           "differentiable wrt q; scale = 1/(global count) for a sharded caller");
+    m.def("sac_discrete", [](const Tensor& logit, const Tensor& next_logit, const Tensor& q1, const OptTensor& q2,
+                             const Tensor& target_q1, const OptTensor& target_q2, const Tensor& action, const Tensor& reward,
+                             const OptTensor& done, const OptTensor& weight, double alpha, const OptTensor& alpha_tensor,
+                             double gamma, std::optional<double> scale) {
+        // (inside the node grad mode is off: whether the unit gradient is worth storing is decided here)
+        const bool want_grad = at::GradMode::is_enabled() && logit.defined() && logit.requires_grad();
+        return SacDiscreteFn::apply(logit, next_logit, q1, q2, target_q1, target_q2, action, reward, done, weight, alpha,
+                                    alpha_tensor, gamma, scale, want_grad);
+    }, py::arg("logit"), py::arg("next_logit"), py::arg("q1"), py::arg("q2"), py::arg("target_q1"), py::arg("target_q2"),
+          py::arg("action"), py::arg("reward"), py::arg("done") = py::none(), py::arg("weight") = py::none(),
+          py::arg("alpha") = 0.2, py::arg("alpha_tensor") = py::none(), py::arg("gamma") = 0.99,
+          py::arg("scale") = py::none(),
+          "Discrete SAC over (..., N) logits and critics: (policy_loss, critic_loss, twin_critic_loss, entropy; (1,) each, "
+          "td_error, target_q (...)); q2 / target_q2 both tensors or both None (twin_critic_loss is then 0); alpha_tensor, a "
+          "1-element fp32 GPU tensor, replaces alpha and is read on the device; differentiable wrt logit, q1 and q2; "
+          "scale = 1/(global rows) for a sharded caller");
     m.def("token_log_prob", [](const Tensor& logits, const Tensor& action) { return TokenLogpFn::apply(logits, action); },
           py::arg("logits"), py::arg("action"),
           "logits[..., a] - logsumexp(logits) per token: (..., V) fp32 or bf16 logits, (...) int64 actions -> (...) fp32; "

@@ -474,6 +474,49 @@ int hpc_rll_r2d2_backward(const float* g_loss, const int64_t* action, const floa
                           int nstep, int burnin, void* stream);
 int hpc_rll_r2d2_last_config(int* out);
 
+/* Soft Actor-Critic for discrete actions: the soft value of the next state, the TD target, both critic losses, the policy
+ * loss, the entropy and the gradients (no reference counterpart; the semantics restate DI-engine's
+ * DiscreteSACPolicy._forward_learn with q_v_1step_td_error).  logit, next_logit, q1, q2, target_q1, target_q2: `rows` rows
+ * of N floats; action (rows) int64; reward (rows); done (rows) of `mask_dtype` (HPC_RLL_MASK_U8 / HPC_RLL_MASK_F32; NULL =
+ * no episode ends), k = 1 - done; weight (rows) (NULL = ones: an exact 1 is multiplied).  q2 and target_q2 are both given or
+ * both NULL (a single critic: m = q1, m' = target_q1).  The temperature is alpha_dev[0], a device scalar, when alpha_dev is
+ * given, otherwise `alpha`.  Per sample, with x, y the logit and next_logit rows and a the action:
+ *   l' = log_softmax(y), p' = exp l', m' = min(target_q1, target_q2),  V' = sum_n p'_n (m'_n - alpha l'_n)
+ *   G = reward + gamma k V'  (a constant),   d_i = q_i[a] - G,   td_error = mean_i d_i^2 (unweighted),   target_q = G
+ *   l = log_softmax(x), p = exp l, m = min(q1, q2) (a constant),  t_n = alpha l_n - m_n,  f = sum_n p_n t_n,  H = -sum_n p_n l_n
+ *   out4 = { scale sum f,  scale sum w d_1^2,  scale sum w d_2^2 (0 for a single critic),  scale sum H }
+ *   unit_grad[b,n] = scale p_n (t_n - f),   grad_logit = g_policy unit_grad,   grad_q_i[b,n] = g_i 2 scale w d_i [n = a].
+ * A logit of -inf is clamped to the most negative finite float: its column has p_n = 0, adds exactly 0 to V', f and H
+ * whatever the critics hold there and gets gradient 0 (the sums select on p_n > 0).  An action outside [0,N) never addresses
+ * memory: d_i = 0, td_error = 0 and the critic gradient rows are zero; the policy part is unaffected.
+ * hpc_rll_sac_discrete_forward -- one launch.  unit_grad (rows,N) may be NULL: the logit gradient is then not formed.
+ *   ws: hpc_rll_sac_discrete_workspace_floats(rows) floats: delta_1 (rows: 2 scale w d_1) | delta_2 (rows; written for twin
+ *   critics) | the partial sums.  rows == 0 zeroes out4 and launches nothing.
+ * hpc_rll_sac_discrete_backward -- one streaming launch without reductions or atomics: every float of each given output
+ *   (rows,N) is written once.  Any output may be NULL (it is then neither computed nor written; unit_grad may be NULL when
+ *   grad_logit is); with all NULL nothing is launched.  g_policy, g_critic, g_twin are device scalars (NULL = 1).
+ * hpc_rll_sac_discrete_last_config -- out[HPC_RLL_SAC_CONFIG_INTS] = {
+ *    [0..6]  the forward: launches so far, G, VEC, E (lanes per row, floats per load, loads per lane and row), R (rows per
+ *            group and iteration), flags (bit 0 weight given; bits 1-2 done: 0 none, 1 bytes, 2 floats; bit 3 twin critics;
+ *            bit 4 unit_grad stored), workgroups,
+ *    [7..13] the backward: launches so far, G, VEC, E, R, flags (bit 0 grad_logit, bit 1 grad_q1, bit 2 grad_q2 written),
+ *            workgroups };
+ *   each part is {0, -1 ...} before its first launch; HPC_RLL_EINVAL for out == NULL.
+ * 1 <= N <= 1024, beyond that HPC_RLL_EUNSUPPORTED.  Argument errors, before any HIP call: HPC_RLL_EINVAL (null operands,
+ * one of q2 / target_q2 without the other, then negative sizes, N <= 0 or an unknown mask_dtype), HPC_RLL_EALIGN (a pointer
+ * off 4-byte alignment, action off 8; a byte mask has none), then HPC_RLL_EUNSUPPORTED (N > 1024); then empty shapes return 0. */
+#define HPC_RLL_SAC_CONFIG_INTS (14)
+int64_t hpc_rll_sac_discrete_workspace_floats(int64_t rows);
+int hpc_rll_sac_discrete_forward(const float* logit, const float* next_logit, const float* q1, const float* q2,
+                                 const float* target_q1, const float* target_q2, const int64_t* action, const float* reward,
+                                 const void* done, int mask_dtype, const float* weight, const float* alpha_dev, float alpha,
+                                 float* out4, float* td_error, float* target_q, float* unit_grad, float* ws, int64_t rows,
+                                 int N, float gamma, float scale, void* stream);
+int hpc_rll_sac_discrete_backward(const float* g_policy, const float* g_critic, const float* g_twin, const float* unit_grad,
+                                  const int64_t* action, const float* ws, float* grad_logit, float* grad_q1, float* grad_q2,
+                                  int64_t rows, int N, void* stream);
+int hpc_rll_sac_discrete_last_config(int* out);
+
 /* Language-model policy losses: the per-token log-probability over a large vocabulary and GRPO's clipped-ratio + k3-KL token
  * loss with per-sequence masked means (no reference counterpart; the semantics restate DI-engine's grpo_policy_error /
  * rloo_policy_error and their log_prob_utils helper).  Logits are (rows, V) of element type HPC_RLL_ELEM_F32 or
