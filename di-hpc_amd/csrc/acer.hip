@@ -50,24 +50,6 @@ namespace {
 
 constexpr int kAcerMaxN = kRowTableMaxN;   // 64 lanes x 16 floats per lane and input
 constexpr int kAcerSums = 4;               // w (La + Lb + beta H), w La, w Lb, w H
-constexpr float kFltMax = 3.402823466e38f;
-
-struct AddOp { static __device__ __forceinline__ float f(float a, float b) { return a + b; } };
-struct MaxOp { static __device__ __forceinline__ float f(float a, float b) { return fmaxf(a, b); } };
-
-// the maximum of a row in every lane of the group; -inf counts as the most negative finite float, as does padding
-template <int G, int VEC, int E>
-__device__ __forceinline__ float row_max(const RowSlice<G, VEC, E>& r, int N, int gl) {
-    float mx = -kFltMax;
-#pragma unroll
-    for (int e = 0; e < E; ++e)
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-            const int c = (e * G + gl) * VEC + j;
-            mx = fmaxf(mx, c < N ? r.x[e * VEC + j] : -kFltMax);
-        }
-    return group_all<G, MaxOp>(mx);
-}
 
 struct AcerArgs {
     const float* target; const float* behaviour; const float* avg; const float* q; const float* q_ret; const float* v;
@@ -80,7 +62,6 @@ __global__ __launch_bounds__(256) void acer_policy_fwd_kernel(const AcerArgs p, 
                                                               const ScanFold fold) {
     constexpr int GPB = 256 / G;
     constexpr int R = RowsPerIter<VEC, E>::value;
-    __shared__ float red[kAcerSums * 4];
     const int gl = threadIdx.x % G;
     const int gi = threadIdx.x / G;
     const int N = p.N;
@@ -114,11 +95,11 @@ __global__ __launch_bounds__(256) void acer_policy_fwd_kernel(const AcerArgs p, 
             const float* q = qs[k].x;
             const long row = bb + (long)k * GPB + gi;
             const bool live = row < p.rows;
-            const int ai = (a[k] >= 0 && a[k] < (long)N) ? (int)a[k] : -1;
+            const int ai = action_index(a[k], N);
             // ---- 1. maxima; x <- x - mx, y <- y - my (clamped: finite), u <- exp(u - mu)
-            const float mx = row_max<G, VEC, E>(xs[k], N, gl);
-            const float my = row_max<G, VEC, E>(ys[k], N, gl);
-            const float mu = HAVG ? row_max<G, VEC, E>(us[k], N, gl) : 0.f;
+            const float mx = row_max_finite<G, VEC, E>(x, N, gl);
+            const float my = row_max_finite<G, VEC, E>(y, N, gl);
+            const float mu = HAVG ? row_max_finite<G, VEC, E>(u, N, gl) : 0.f;
             float sx = 0.f, sy = 0.f, su = 0.f;
 #pragma unroll
             for (int e = 0; e < E; ++e)
@@ -203,30 +184,11 @@ __global__ __launch_bounds__(256) void acer_policy_fwd_kernel(const AcerArgs p, 
                     const float z = HAVG ? fmaf(-s, u[i], x[i]) : x[i];
                     o[j] = (y[i] > 0.f) ? ws * fmaf(-y[i], sz, z) : 0.f;
                 }
-                if (live && c0 < N) {
-                    if (VEC == 4) {
-                        vfloat4 t;
-                        t.x = o[0]; t.y = o[1]; t.z = o[2]; t.w = o[3];
-                        __builtin_nontemporal_store(t, reinterpret_cast<vfloat4*>(out + c0));
-                    } else {
-                        __builtin_nontemporal_store(o[0], out + c0);
-                    }
-                }
+                if (live && c0 < N) store_piece<VEC>(out + c0, o);
             }
         }
     }
-    // the workgroup's four sums, then the shared epilogue (the only LDS and barriers of the kernel)
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < kAcerSums; ++k) {
-        const float s = wave_sum(acc[k]);
-        if (lane == 0) red[k * 4 + w] = s;
-    }
-    __syncthreads();
-    float sum = 0.f;
-    if (threadIdx.x < kAcerSums)
-        sum = (red[threadIdx.x * 4] + red[threadIdx.x * 4 + 1]) + (red[threadIdx.x * 4 + 2] + red[threadIdx.x * 4 + 3]);
-    publish_sums<kAcerSums, 256>(sum, partials, fold);
+    publish_block_sums<kAcerSums, 256>(acc, partials, fold);   // (the only LDS and barriers of the kernel)
 }
 
 // out = g - max(0, (sum k g - delta) / sum k^2) k,  k = exp(avg_logit): the projection alone
@@ -272,70 +234,46 @@ __global__ __launch_bounds__(256) void acer_trust_region_kernel(const float* __r
             for (int e = 0; e < E; ++e) {
                 const int c0 = (e * G + gl) * VEC;
                 if (c0 >= N) continue;
-                if (VEC == 4) {
-                    vfloat4 t;
-                    t.x = fmaf(-s, ks[k].x[e * 4 + 0], gs[k].x[e * 4 + 0]);
-                    t.y = fmaf(-s, ks[k].x[e * 4 + 1], gs[k].x[e * 4 + 1]);
-                    t.z = fmaf(-s, ks[k].x[e * 4 + 2], gs[k].x[e * 4 + 2]);
-                    t.w = fmaf(-s, ks[k].x[e * 4 + 3], gs[k].x[e * 4 + 3]);
-                    __builtin_nontemporal_store(t, reinterpret_cast<vfloat4*>(o + c0));
-                } else {
-                    __builtin_nontemporal_store(fmaf(-s, ks[k].x[e], gs[k].x[e]), o + c0);
-                }
+                float z[VEC];
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) z[j] = fmaf(-s, ks[k].x[e * VEC + j], gs[k].x[e * VEC + j]);
+                store_piece<VEC>(o + c0, z);
             }
         }
     }
 }
 
-// The dispatch record (hpc_rll_acer_last_config): plain ints of the host process, like the scan family's; not synchronised.
-int g_acer_last[HPC_RLL_ACER_CONFIG_INTS];   // [0] = launches so far; zero at load
-void acer_note(int g, int vec, int e, int r, int flags, long grid, int drop_in) {
-    const int vals[HPC_RLL_ACER_CONFIG_INTS] = {g_acer_last[0] + 1, g, vec, e, r, flags, (int)grid, drop_in};
-    for (int i = 0; i < HPC_RLL_ACER_CONFIG_INTS; ++i) g_acer_last[i] = vals[i];
-}
-
-// row_cfg with 4 pieces, as gaussian.hip and retrace.hip: four slices of 16 floats are 64 VGPRs for ONE row
-constexpr int kRowPieces = 4;
+// The dispatch record (hpc_rll_acer_last_config): {launches so far, G, VEC, E, R, flags, grid, drop-in}
+LaunchRecord<HPC_RLL_ACER_CONFIG_INTS> g_acer_last;
 
 template <bool HW, bool HAVG, bool GRAD>
 int acer_forward(const AcerArgs& p, float* partials, const float* scales, float* out4, hipStream_t st) {
     const bool v4 = aligned(p.target, 16) && aligned(p.behaviour, 16) && aligned(p.avg, 16) && aligned(p.q, 16) &&
                     aligned(p.unit, 16);   // (an absent operand restricts nothing)
-    const RowCfg cfg = row_cfg(p.N, v4, kRowPieces);
-#define HPC_RLL_ACER_FWD_CASE(G_, V_, E_)                                                                             \
-    if (cfg.g == G_ && cfg.vec == V_ && cfg.e == E_) {                                                                \
-        /* at most kFoldMaxGrid workgroups, which loop: the sums are folded inside the launch */                       \
-        constexpr int R_ = RowsPerIter<V_, E_>::value;                                                                \
-        const long grid = row_grid(p.rows, (256 / G_) * R_, kFoldMaxGrid);                                            \
-        const ScanFold fold = make_fold(st, kAcerSums, scales, out4, grid);                                           \
-        hipLaunchKernelGGL((acer_policy_fwd_kernel<G_, V_, E_, HW, HAVG, GRAD>), dim3((unsigned)grid), dim3(256), 0,   \
-                           st, p, partials, fold);                                                                    \
-        const int rc = last_error();                                                                                  \
-        if (rc) return rc;                                                                                            \
-        acer_note(G_, V_, E_, R_, (HW ? 1 : 0) | (HAVG ? 2 : 0) | (GRAD ? 4 : 0), grid, 0);                           \
-        if (fold.out) return rc;                                                                                      \
-        return finalize_sums(partials, (int)grid, kAcerSums, scales, out4, st);                                       \
-    }
-    HPC_RLL_ROW4_TABLE(HPC_RLL_ACER_FWD_CASE)
-#undef HPC_RLL_ACER_FWD_CASE
-    return HPC_RLL_EUNSUPPORTED;
+    return with_row4(row_cfg(p.N, v4, kRow4Pieces), [&](auto G_, auto V_, auto E_) {
+        constexpr int G = G_, V = V_, E = E_, R = RowsPerIter<V, E>::value;
+        long grid = 0;
+        const int rc = launch_rows_folded(p.rows, (256 / G) * R, kAcerSums, scales, out4, partials, st, &grid,
+                                          [&](unsigned blocks, const ScanFold& fold) {
+            hipLaunchKernelGGL((acer_policy_fwd_kernel<G, V, E, HW, HAVG, GRAD>), dim3(blocks), dim3(256), 0, st, p,
+                               partials, fold);
+        });
+        if (grid) g_acer_last.note({G, V, E, R, (HW ? 1 : 0) | (HAVG ? 2 : 0) | (GRAD ? 4 : 0), (int)grid, 0});
+        return rc;
+    });
 }
 
 int acer_trust_region(const float* grad, const float* avg_logit, float* out, long rows, int N, float delta, hipStream_t st) {
-    const RowCfg cfg = row_cfg(N, aligned(grad, 16) && aligned(avg_logit, 16) && aligned(out, 16), kRowPieces);
-#define HPC_RLL_ACER_TR_CASE(G_, V_, E_)                                                                              \
-    if (cfg.g == G_ && cfg.vec == V_ && cfg.e == E_) {                                                                \
-        constexpr int R_ = RowsPerIter<V_, E_>::value;                                                                \
-        const unsigned grid = row_grid(rows, (256 / G_) * R_, 256L * 1024);   /* short-lived workgroups; above it they loop */ \
-        hipLaunchKernelGGL((acer_trust_region_kernel<G_, V_, E_>), dim3(grid), dim3(256), 0, st, grad, avg_logit, out, \
-                           rows, N, delta);                                                                           \
-        const int rc = last_error();                                                                                  \
-        if (!rc) acer_note(G_, V_, E_, R_, 0, (long)grid, 1);                                                         \
-        return rc;                                                                                                    \
-    }
-    HPC_RLL_ROW4_TABLE(HPC_RLL_ACER_TR_CASE)
-#undef HPC_RLL_ACER_TR_CASE
-    return HPC_RLL_EUNSUPPORTED;
+    const RowCfg cfg = row_cfg(N, aligned(grad, 16) && aligned(avg_logit, 16) && aligned(out, 16), kRow4Pieces);
+    return with_row4(cfg, [&](auto G_, auto V_, auto E_) {
+        constexpr int G = G_, V = V_, E = E_, R = RowsPerIter<V, E>::value;
+        const unsigned grid = row_grid(rows, (256 / G) * R, kUnfoldedGridCap);
+        hipLaunchKernelGGL((acer_trust_region_kernel<G, V, E>), dim3(grid), dim3(256), 0, st, grad, avg_logit, out, rows, N,
+                           delta);
+        const int rc = last_error();
+        if (!rc) g_acer_last.note({G, V, E, R, 0, (int)grid, 1});
+        return rc;
+    });
 }
 
 }  // namespace
@@ -410,7 +348,6 @@ extern "C" int hpc_rll_acer_trust_region(const float* actor_gradient, const floa
 
 extern "C" int hpc_rll_acer_last_config(int* out) {
     if (!out) return HPC_RLL_EINVAL;
-    out[0] = g_acer_last[0];
-    for (int i = 1; i < HPC_RLL_ACER_CONFIG_INTS; ++i) out[i] = g_acer_last[0] ? g_acer_last[i] : -1;   // no launch yet
+    g_acer_last.read(out);
     return HPC_RLL_OK;
 }

@@ -36,7 +36,6 @@ namespace hpc_rll {
 namespace {
 
 constexpr float kNegInf = -3.0e38f;
-constexpr float kFltMax = 3.402823466e38f;
 
 // Masked actions arrive as logits = -inf.  torch.distributions.Categorical (what hpc_rll.origin uses) clamps
 // the normalised logits to the most negative finite float so that p*log p is 0 instead of 0*(-inf) = NaN; clamping
@@ -44,7 +43,6 @@ constexpr float kFltMax = 3.402823466e38f;
 __device__ __forceinline__ float clamp_logit(float x) { return fmaxf(x, -kFltMax); }   // -inf (masked) -> finite
 
 // ---- the ops of the group all-reduces (group_all, rowgroup.hpp)
-struct SumOp { static __device__ __forceinline__ float f(float a, float b) { return a + b; } };
 // max of two values that are never NaN here (finish() removed NaNs): med3(a, b, +inf) is ONE v_med3_f32, whereas fmaxf
 // first canonicalises an operand the compiler cannot prove quiet (every DPP move): 3 instructions per butterfly step -> 2
 // (+inf comes out of an asm so that the compiler cannot fold med3(a, b, inf) back into maxnum(a, b) + canonicalise)
@@ -183,9 +181,9 @@ __device__ __forceinline__ void row_stats_fwd(const RowSlice<G, VEC, E>& r, int 
     m = row_all<G, MaxOp>(m);
     float ex[E * VEC];
     RowAcc a = lane_stats<G, VEC, E, true>(r, N, gl, ai, full, ex, m);
-    a.s = row_all<G, SumOp>(a.s);
-    a.t = row_all<G, SumOp>(a.t);
-    a.xa = row_all<G, SumOp>(a.xa);
+    a.s = row_all<G, AddOp>(a.s);
+    a.t = row_all<G, AddOp>(a.t);
+    a.xa = row_all<G, AddOp>(a.xa);
     if (G >= 32) {   // rows 1 and 3 merge the row before them
         RowAcc b;
         b.m = row_fetch<0x142, 0xA>(a.m); b.s = row_fetch<0x142, 0xA>(a.s);
@@ -216,8 +214,8 @@ __device__ __forceinline__ void row_stats(const RowSlice<G, VEC, E>& r, int N, i
     for (int i = 1; i < E * VEC; ++i) m = fmaxf(m, r.x[i]);
     m = group_all<G, MaxOp>(m);
     const RowAcc a = lane_stats<G, VEC, E, false>(r, N, gl, ai, full, ex, m);
-    const float s = group_all<G, SumOp>(a.s);
-    const float t = group_all<G, SumOp>(a.t);
+    const float s = group_all<G, AddOp>(a.s);
+    const float t = group_all<G, AddOp>(a.t);
     const float ls = log_sum(s);
     inv_sum = __builtin_amdgcn_rcpf(s);
     lse = m + ls;
@@ -257,7 +255,7 @@ __device__ __forceinline__ void categorical_fwd_body(const float* __restrict__ l
         float lp[R], h[R];
 #pragma unroll
         for (int k = 0; k < R; ++k) {
-            const int ai = (a[k] >= 0 && a[k] < (long)N) ? (int)a[k] : -1;
+            const int ai = action_index(a[k], N);
             finish(r[k], N, gl);
             row_stats_fwd<G, VEC, E>(r[k], N, gl, ai, full, lp[k], h[k]);
         }
@@ -300,7 +298,6 @@ __global__ __launch_bounds__(256) void ppo_fwd_fused_kernel(const float* __restr
                                                             int N, float* __restrict__ partials, const ScanFold fold) {
     constexpr int GPB = 256 / G;
     constexpr int R = 4;   // rows per group and iteration: 4 rows x 2 heads x E loads in flight per lane (the grid is at most 512 workgroups)
-    __shared__ float red[PpoOp::NACC * 4];
     const int gl = threadIdx.x % G;
     const int gi = threadIdx.x / G;
     const bool full = N == G * VEC * E;
@@ -323,7 +320,7 @@ __global__ __launch_bounds__(256) void ppo_fwd_fused_kernel(const float* __restr
         }
 #pragma unroll
         for (int k = 0; k < R; ++k) {
-            const int ai = (a[k] >= 0 && a[k] < (long)N) ? (int)a[k] : -1;
+            const int ai = action_index(a[k], N);
             float lpn, h, lpo, h_unused;
             finish(rn[k], N, gl);
             finish(ro[k], N, gl);
@@ -333,17 +330,7 @@ __global__ __launch_bounds__(256) void ppo_fwd_fused_kernel(const float* __restr
             if (gl == G - 1 && row < rows) op.apply(row, in[k], lpn, h, lpo, acc);
         }
     }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < PpoOp::NACC; ++k) {
-        const float s = wave_sum(acc[k]);
-        if (lane == 0) red[k * 4 + w] = s;
-    }
-    __syncthreads();
-    float sum = 0.f;
-    if (threadIdx.x < PpoOp::NACC)
-        sum = (red[threadIdx.x * 4] + red[threadIdx.x * 4 + 1]) + (red[threadIdx.x * 4 + 2] + red[threadIdx.x * 4 + 3]);
-    publish_sums<PpoOp::NACC, 256>(sum, partials, fold);
+    publish_block_sums<PpoOp::NACC, 256>(acc, partials, fold);
 }
 
 // grad[row,i] = g1*c1[row]*(1[i==a] - p_i) + g2*c2[row]*(-p_i*(log p_i + H))
@@ -382,7 +369,7 @@ __global__ __launch_bounds__(256) void categorical_bwd_kernel(const float* __res
 #pragma unroll
         for (int k = 0; k < R; ++k) {
             float ex[E * VEC], lse, inv, h;
-            const int ai = (a[k] >= 0 && a[k] < (long)N) ? (int)a[k] : -1;
+            const int ai = action_index(a[k], N);
             finish(r[k], N, gl);
             row_stats<G, VEC, E>(r[k], N, gl, ai, full, ex, lse, inv, h);
             if (w0 + (long)k * GPB >= rows) continue;
@@ -402,14 +389,7 @@ __global__ __launch_bounds__(256) void categorical_bwd_kernel(const float* __res
                     const float hot = (c0 + q == ai) ? kk1 : 0.f;
                     o[q] = fmaf(qq * kk2, r[k].x[i] - cc, fmaf(qq, kk1, hot));
                 }
-                if (c0 < N) {
-                    if (VEC == 4) {
-                        vfloat4 t; t.x = o[0]; t.y = o[1]; t.z = o[2]; t.w = o[3];
-                        __builtin_nontemporal_store(t, reinterpret_cast<vfloat4*>(out + c0));
-                    } else {
-                        __builtin_nontemporal_store(o[0], out + c0);
-                    }
-                }
+                if (c0 < N) store_piece<VEC>(out + c0, o);
             }
         }
     }
@@ -543,8 +523,8 @@ __global__ __launch_bounds__(256) void categorical_blockrow_kernel(const float* 
             t = fmaf(ex, d, t);
             if (BWD) v[i] = d;          // keep d; exp(d) is recomputed below only when registers are short (E = 16)
         }
-        s = group_all<64, SumOp>(s);
-        t = group_all<64, SumOp>(t);
+        s = group_all<64, AddOp>(s);
+        t = group_all<64, AddOp>(t);
         if (lane == 0) { red_s[buf][w] = s; red_t[buf][w] = t; }
         __syncthreads();
         s = (red_s[buf][0] + red_s[buf][1]) + (red_s[buf][2] + red_s[buf][3]);
@@ -729,13 +709,12 @@ namespace {
 constexpr int kRowPieces = 8;
 constexpr int kMaxE = 8;   // row_cfg(...).e > kMaxE means "use the long-row fallback"
 
-// The dispatch record (hpc_rll_categorical_last_config): plain ints of the host process, like the scan family's; not
-// synchronised.  One row per direction (0 forward, the fused PPO forward included; 1 backward), [0] = launches so far (zero at
-// load), written where the kernel is launched so that it names the instantiation that ran, not a second evaluation of the rule.
-int g_cat_last[2][HPC_RLL_CATEGORICAL_CONFIG_INTS];
+// The dispatch record (hpc_rll_categorical_last_config): one per direction (0 forward, the fused PPO forward included;
+// 1 backward), noted where the kernel is launched so that it names the instantiation that ran, not a second evaluation of the
+// rule.
+LaunchRecord<HPC_RLL_CATEGORICAL_CONFIG_INTS> g_cat_last[2];
 void cat_note(int dir, int family, int g, int vec, int e, int r, bool ent, long grid) {
-    const int vals[HPC_RLL_CATEGORICAL_CONFIG_INTS] = {g_cat_last[dir][0] + 1, family, g, vec, e, r, ent ? 1 : 0, (int)grid};
-    for (int i = 0; i < HPC_RLL_CATEGORICAL_CONFIG_INTS; ++i) g_cat_last[dir][i] = vals[i];
+    g_cat_last[dir].note({family, g, vec, e, r, ent ? 1 : 0, (int)grid});
 }
 
 // the (G, VEC, E) of row_cfg(N, ., kRowPieces) below that fallback: N <= 64 lanes x kMaxE pieces x 4 floats
@@ -903,8 +882,6 @@ extern "C" int hpc_rll_categorical_backward(const float* logits, const int64_t* 
 
 extern "C" int hpc_rll_categorical_last_config(int direction, int* out) {
     if ((direction != HPC_RLL_CAT_DIR_FORWARD && direction != HPC_RLL_CAT_DIR_BACKWARD) || !out) return HPC_RLL_EINVAL;
-    const int* rec = hpc_rll::g_cat_last[direction];
-    out[0] = rec[0];
-    for (int i = 1; i < HPC_RLL_CATEGORICAL_CONFIG_INTS; ++i) out[i] = rec[0] ? rec[i] : -1;   // no launch yet
+    hpc_rll::g_cat_last[direction].read(out);
     return HPC_RLL_OK;
 }

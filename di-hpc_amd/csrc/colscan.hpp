@@ -23,6 +23,7 @@
 
 #include <type_traits>
 
+#include "hostutil.hpp"
 #include "hpc_rll_hip.h"
 #include "wave.hpp"
 
@@ -129,6 +130,31 @@ __device__ __forceinline__ void publish_sums(float sum, float* __restrict__ part
         fold.out[threadIdx.x] = (float)(tot * (double)fold.scale[threadIdx.x]);
     }
     if (threadIdx.x == 0) __hip_atomic_store(fold.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The same epilogue from per-THREAD sums: wave butterflies, one LDS slot per sum and wave, one barrier, the waves' sums added
+// in a fixed order -- (r0 + r1) + (r2 + r3) for four waves, in wave order otherwise -- then publish_sums.  The only LDS and
+// barriers of the row and sample kernels that end with it.  Called by ALL NT threads.
+template <int NACC, int NT>
+__device__ __forceinline__ void publish_block_sums(const float (&acc)[NACC], float* __restrict__ partials,
+                                                   const ScanFold& fold) {
+    constexpr int NWV = NT / 64;
+    __shared__ float red[NACC * NWV];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) {
+        const float s = wave_sum(acc[k]);
+        if (lane == 0) red[k * NWV + w] = s;
+    }
+    __syncthreads();
+    float sum = 0.f;
+    if (threadIdx.x < NACC) {
+        const int k = threadIdx.x;
+        if (NWV == 4) sum = (red[k * 4] + red[k * 4 + 1]) + (red[k * 4 + 2] + red[k * 4 + 3]);
+        else
+            for (int i = 0; i < NWV; ++i) sum += red[k * NWV + i];
+    }
+    publish_sums<NACC, NT>(sum, partials, fold);
 }
 
 template <class Op, int V, int LC, int NW, int SUB = 1>
@@ -369,6 +395,24 @@ inline int scan_and_finalize(const Op& op, const ScanCfg& c, int T, int B, float
     scan_note_final(Op::DIAG_OP, fold.out ? 1 : 2);
     if (fold.out) return 0;
     return finalize_sums(partials, (int)scan_grid(c, B), nacc, scale, out, st);
+}
+
+// The forward of a head that ends in `nacc` loss sums: at most kFoldMaxGrid workgroups, which loop, so that the sums are
+// folded inside the launch (publish_sums above); finalize_sums where no fold is available.  launch(grid, fold) issues the kernel.
+// *grid is set once the launch has succeeded (the caller's dispatch record).
+template <class L>
+int launch_rows_folded(long rows, long rows_per_block, int nacc, const float* scales, float* out, float* partials,
+                       hipStream_t st, long* grid, L&& launch) {
+    long g = (rows + rows_per_block - 1) / rows_per_block;
+    if (g > kFoldMaxGrid) g = kFoldMaxGrid;
+    if (g < 1) g = 1;
+    const ScanFold fold = make_fold(st, nacc, scales, out, g);
+    launch((unsigned)g, fold);
+    const int rc = last_error();
+    if (rc) return rc;
+    *grid = g;
+    if (fold.out) return rc;
+    return finalize_sums(partials, (int)g, nacc, scales, out, st);
 }
 
 }  // namespace hpc_rll

@@ -49,10 +49,6 @@ namespace {
 
 constexpr int kComaMaxN = kRowTableMaxN;   // 64 lanes x 16 floats per lane and input
 constexpr int kComaSums = 3;               // the order of loss[3]: policy, q (zero here: the scan's), entropy
-constexpr float kFltMax = 3.402823466e38f;
-
-struct AddOp { static __device__ __forceinline__ float f(float a, float b) { return a + b; } };
-struct MaxOp { static __device__ __forceinline__ float f(float a, float b) { return fmaxf(a, b); } };
 
 // ================================================================================================
 // the heads
@@ -68,12 +64,11 @@ __global__ __launch_bounds__(256) void coma_heads_fwd_kernel(const ComaHeadArgs 
                                                              const ScanFold fold) {
     constexpr int GPB = 256 / G;
     constexpr int R = RowsPerIter<VEC, E>::value;
-    __shared__ float red[2 * 4];
     const int gl = threadIdx.x % G;
     const int gi = threadIdx.x / G;
     const int N = p.N;
     const long stride = (long)gridDim.x * GPB * R;
-    float acc_p = 0.f, acc_e = 0.f;
+    float acc[kComaSums] = {0.f, 0.f, 0.f};   // policy, q (zero here: the scan's), entropy
     for (long bb = (long)blockIdx.x * GPB * R; bb < p.rows; bb += stride) {
         RowSlice<G, VEC, E> xs[R], qs[R], ts[R];
         long a[R];
@@ -94,17 +89,8 @@ __global__ __launch_bounds__(256) void coma_heads_fwd_kernel(const ComaHeadArgs 
             const float* x = xs[k].x;
             const float* q = qs[k].x;
             const float* tq = ts[k].x;
-            const int ai = (a[k] >= 0 && a[k] < (long)N) ? (int)a[k] : -1;
-            // ---- maximum; -inf counts as the most negative finite float, as does padding
-            float mx = -kFltMax;
-#pragma unroll
-            for (int e = 0; e < E; ++e)
-#pragma unroll
-                for (int j = 0; j < VEC; ++j) {
-                    const int c = (e * G + gl) * VEC + j;
-                    mx = fmaxf(mx, c < N ? fmaxf(x[e * VEC + j], -kFltMax) : -kFltMax);
-                }
-            const float m = group_all<G, MaxOp>(mx);
+            const int ai = action_index(a[k], N);
+            const float m = row_max_finite<G, VEC, E>(x, N, gl);
             // ---- partition sum, baseline, sum e (x - m) and the three selected entries
             float s = 0.f, bq = 0.f, sxm = 0.f, xa = 0.f, qsel = 0.f, tsel = 0.f;
 #pragma unroll
@@ -136,8 +122,8 @@ __global__ __launch_bounds__(256) void coma_heads_fwd_kernel(const ComaHeadArgs 
             const float pterm = ai >= 0 ? la * adv : 0.f;
             const long row = bb + (long)k * GPB + gi;
             if (row < p.rows) {
-                acc_p = HW ? fmaf(wt[k], pterm, acc_p) : acc_p + pterm;
-                acc_e = HW ? fmaf(wt[k], h, acc_e) : acc_e + h;
+                acc[0] = HW ? fmaf(wt[k], pterm, acc[0]) : acc[0] + pterm;
+                acc[2] = HW ? fmaf(wt[k], h, acc[2]) : acc[2] + h;
                 if (gl == 0) {
                     p.qa[row] = qsel;
                     p.tqa[row] = tsel;
@@ -149,50 +135,28 @@ __global__ __launch_bounds__(256) void coma_heads_fwd_kernel(const ComaHeadArgs 
         }
     }
     // every lane of a group holds the same row terms: lane 0 of each group counts
-    if (gl != 0) { acc_p = 0.f; acc_e = 0.f; }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const float sp = wave_sum(acc_p), se = wave_sum(acc_e);
-    if (lane == 0) { red[w] = sp; red[4 + w] = se; }
-    __syncthreads();
-    float sum = 0.f;   // thread 1: the q sum is the scan's
-    if (threadIdx.x == 0) sum = (red[0] + red[1]) + (red[2] + red[3]);
-    if (threadIdx.x == 2) sum = (red[4] + red[5]) + (red[6] + red[7]);
-    publish_sums<kComaSums, 256>(sum, partials, fold);
+    if (gl != 0) { acc[0] = 0.f; acc[2] = 0.f; }
+    publish_block_sums<kComaSums, 256>(acc, partials, fold);
 }
 
-// The dispatch records of the heads and the backward (hpc_rll_coma_last_config): plain ints of the host process, like the
-// scan family's; not synchronised.  {launches so far, G, VEC, E, R, flags, grid}
+// The dispatch records of the heads and the backward (hpc_rll_coma_last_config): {launches so far, G, VEC, E, R, flags, grid}
 constexpr int kLaunchInts = 7;
-int g_coma_heads[kLaunchInts], g_coma_bwd[kLaunchInts];   // zero at load
-void coma_note(int* rec, int g, int vec, int e, int r, int flags, long grid) {
-    const int vals[kLaunchInts] = {rec[0] + 1, g, vec, e, r, flags, (int)grid};
-    for (int i = 0; i < kLaunchInts; ++i) rec[i] = vals[i];
-}
-
-// row_cfg with 4 pieces, as Retrace's heads: three slices of 16 floats are 48 VGPRs for ONE row
-constexpr int kRowPieces = 4;
+LaunchRecord<kLaunchInts> g_coma_heads, g_coma_bwd;
 
 template <bool HW>
 int coma_heads(const ComaHeadArgs& p, float* partials, float* loss, hipStream_t st) {
-    const RowCfg cfg = row_cfg(p.N, aligned(p.logit, 16) && aligned(p.q, 16) && aligned(p.tq, 16), kRowPieces);
+    const RowCfg cfg = row_cfg(p.N, aligned(p.logit, 16) && aligned(p.q, 16) && aligned(p.tq, 16), kRow4Pieces);
     const float sc[kComaSums] = {-p.scale_pe, 0.f, p.scale_pe};
-#define HPC_RLL_COMA_HEADS_CASE(G_, V_, E_)                                                                           \
-    if (cfg.g == G_ && cfg.vec == V_ && cfg.e == E_) {                                                                \
-        /* at most kFoldMaxGrid workgroups, which loop: the sums are folded inside the launch */                       \
-        constexpr int R_ = RowsPerIter<V_, E_>::value;                                                                \
-        const long grid = row_grid(p.rows, (256 / G_) * R_, kFoldMaxGrid);                                            \
-        const ScanFold fold = make_fold(st, kComaSums, sc, loss, grid);                                               \
-        hipLaunchKernelGGL((coma_heads_fwd_kernel<G_, V_, E_, HW>), dim3((unsigned)grid), dim3(256), 0, st, p,         \
-                           partials, fold);                                                                           \
-        const int rc = last_error();                                                                                  \
-        if (rc) return rc;                                                                                            \
-        coma_note(g_coma_heads, G_, V_, E_, R_, HW ? 1 : 0, grid);                                                    \
-        if (fold.out) return rc;                                                                                      \
-        return finalize_sums(partials, (int)grid, kComaSums, sc, loss, st);                                           \
-    }
-    HPC_RLL_ROW4_TABLE(HPC_RLL_COMA_HEADS_CASE)
-#undef HPC_RLL_COMA_HEADS_CASE
-    return HPC_RLL_EUNSUPPORTED;
+    return with_row4(cfg, [&](auto G_, auto V_, auto E_) {
+        constexpr int G = G_, V = V_, E = E_, R = RowsPerIter<V, E>::value;
+        long grid = 0;
+        const int rc = launch_rows_folded(p.rows, (256 / G) * R, kComaSums, sc, loss, partials, st, &grid,
+                                          [&](unsigned blocks, const ScanFold& fold) {
+            hipLaunchKernelGGL((coma_heads_fwd_kernel<G, V, E, HW>), dim3(blocks), dim3(256), 0, st, p, partials, fold);
+        });
+        if (grid) g_coma_heads.note({G, V, E, R, HW ? 1 : 0, (int)grid});
+        return rc;
+    });
 }
 
 // ================================================================================================
@@ -316,7 +280,7 @@ __global__ __launch_bounds__(256) void coma_bwd_kernel(const ComaBwdArgs p) {
         for (int k = 0; k < R; ++k) {
             const long row = bb + (long)k * GPB + gi;
             const bool live = row < p.rows;
-            const int ai = (a[k] >= 0 && a[k] < (long)N) ? (int)a[k] : -1;
+            const int ai = action_index(a[k], N);
             const float cpk = GL ? gp * cp[k] : 0.f, cek = GL ? ge * ce[k] : 0.f;
 #pragma unroll
             for (int e = 0; e < E; ++e) {
@@ -336,20 +300,8 @@ __global__ __launch_bounds__(256) void coma_bwd_kernel(const ComaBwdArgs p) {
                 }
                 if (live && c0 < N) {
                     const long o = row * (long)N + c0;
-                    if (VEC == 4) {
-                        vfloat4 t;
-                        if (GL) {
-                            t.x = ol[0]; t.y = ol[1]; t.z = ol[2]; t.w = ol[3];
-                            __builtin_nontemporal_store(t, reinterpret_cast<vfloat4*>(p.grad_logit + o));
-                        }
-                        if (GQ) {
-                            t.x = oq[0]; t.y = oq[1]; t.z = oq[2]; t.w = oq[3];
-                            __builtin_nontemporal_store(t, reinterpret_cast<vfloat4*>(p.grad_q + o));
-                        }
-                    } else {
-                        if (GL) __builtin_nontemporal_store(ol[0], p.grad_logit + o);
-                        if (GQ) __builtin_nontemporal_store(oq[0], p.grad_q + o);
-                    }
+                    if (GL) store_piece<VEC>(p.grad_logit + o, ol);
+                    if (GQ) store_piece<VEC>(p.grad_q + o, oq);
                 }
             }
         }
@@ -360,20 +312,15 @@ template <bool GL, bool GQ, bool HW>
 int coma_backward(const ComaBwdArgs& p, hipStream_t st) {
     // an absent operand restricts nothing; logit counts only when it is read
     const RowCfg cfg = row_cfg(p.N, aligned(GL ? p.logit : nullptr, 16) && aligned(p.grad_logit, 16) && aligned(p.grad_q, 16),
-                               kRowPieces);
-#define HPC_RLL_COMA_BWD_CASE(G_, V_, E_)                                                                             \
-    if (cfg.g == G_ && cfg.vec == V_ && cfg.e == E_) {                                                                \
-        constexpr int R_ = RowsPerIter<V_, E_>::value;                                                                \
-        /* short-lived workgroups, as Retrace's backward; above the cap they loop */                                  \
-        const unsigned grid = row_grid(p.rows, (256 / G_) * R_, 256L * 1024);                                         \
-        hipLaunchKernelGGL((coma_bwd_kernel<G_, V_, E_, GL, GQ, HW>), dim3(grid), dim3(256), 0, st, p);                \
-        const int rc = last_error();                                                                                  \
-        if (!rc) coma_note(g_coma_bwd, G_, V_, E_, R_, (GL ? 1 : 0) | (GQ ? 2 : 0) | (HW ? 4 : 0), (long)grid);       \
-        return rc;                                                                                                    \
-    }
-    HPC_RLL_ROW4_TABLE(HPC_RLL_COMA_BWD_CASE)
-#undef HPC_RLL_COMA_BWD_CASE
-    return HPC_RLL_EUNSUPPORTED;
+                               kRow4Pieces);
+    return with_row4(cfg, [&](auto G_, auto V_, auto E_) {
+        constexpr int G = G_, V = V_, E = E_, R = RowsPerIter<V, E>::value;
+        const unsigned grid = row_grid(p.rows, (256 / G) * R, kUnfoldedGridCap);
+        hipLaunchKernelGGL((coma_bwd_kernel<G, V, E, GL, GQ, HW>), dim3(grid), dim3(256), 0, st, p);
+        const int rc = last_error();
+        if (!rc) g_coma_bwd.note({G, V, E, R, (GL ? 1 : 0) | (GQ ? 2 : 0) | (HW ? 4 : 0), (int)grid});
+        return rc;
+    });
 }
 
 // B*A columns must fit an int
@@ -445,12 +392,8 @@ extern "C" int hpc_rll_coma_last_config(int* out) {
     if (!out) return HPC_RLL_EINVAL;
     const int rc = scan_read_record(kScanOpComa, out);
     if (rc) return rc;
-    int* o = out + HPC_RLL_SCAN_CONFIG_INTS;
-    for (const int* rec : {g_coma_heads, g_coma_bwd}) {
-        o[0] = rec[0];
-        for (int i = 1; i < kLaunchInts; ++i) o[i] = rec[0] ? rec[i] : -1;   // no launch yet
-        o += kLaunchInts;
-    }
+    g_coma_heads.read(out + HPC_RLL_SCAN_CONFIG_INTS);
+    g_coma_bwd.read(out + HPC_RLL_SCAN_CONFIG_INTS + kLaunchInts);
     return HPC_RLL_OK;
 }
 static_assert(HPC_RLL_COMA_CONFIG_INTS == HPC_RLL_SCAN_CONFIG_INTS + 2 * 7, "the layout documented in hpc_rll_hip.h");

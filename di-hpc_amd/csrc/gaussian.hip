@@ -62,7 +62,6 @@ __global__ __launch_bounds__(256) void ppo_gauss_fwd_kernel(const float* __restr
                                                             int A, float* __restrict__ partials, const ScanFold fold) {
     constexpr int GPB = 256 / G;
     constexpr int R = RowsPerIter<VEC, E>::value;
-    __shared__ float red[PpoOp::NACC * 4];
     const int gl = threadIdx.x % G;
     const int gi = threadIdx.x / G;
     const bool full = A == G * VEC * E;   // uniform: no padding lanes
@@ -109,17 +108,7 @@ __global__ __launch_bounds__(256) void ppo_gauss_fwd_kernel(const float* __restr
             if (gl == G - 1 && row < rows) op.apply(row, in[k], d, fmaf(h, kLn2, hconst), 0.f, acc);
         }
     }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < PpoOp::NACC; ++k) {
-        const float s = wave_sum(acc[k]);
-        if (lane == 0) red[k * 4 + w] = s;
-    }
-    __syncthreads();
-    float sum = 0.f;
-    if (threadIdx.x < PpoOp::NACC)
-        sum = (red[threadIdx.x * 4] + red[threadIdx.x * 4 + 1]) + (red[threadIdx.x * 4 + 2] + red[threadIdx.x * 4 + 3]);
-    publish_sums<PpoOp::NACC, 256>(sum, partials, fold);
+    publish_block_sums<PpoOp::NACC, 256>(acc, partials, fold);
 }
 
 // c1 / c2 / c3 = the forward's coef_logp / coef_ent / gv_unit; g_* device scalars (NULL = 1); any of the three outputs may be NULL
@@ -173,20 +162,8 @@ __global__ __launch_bounds__(256) void ppo_gauss_bwd_kernel(const float* __restr
                     os[q] = fmaf(k1[k], fmaf(z, z, -1.f), k2[k]) * inv;
                 }
                 if (c0 < A) {
-                    if (VEC == 4) {
-                        vfloat4 t;
-                        if (grad_mu) {
-                            t.x = om[0]; t.y = om[1]; t.z = om[2]; t.w = om[3];
-                            __builtin_nontemporal_store(t, reinterpret_cast<vfloat4*>(grad_mu + off + c0));
-                        }
-                        if (grad_sigma) {
-                            t.x = os[0]; t.y = os[1]; t.z = os[2]; t.w = os[3];
-                            __builtin_nontemporal_store(t, reinterpret_cast<vfloat4*>(grad_sigma + off + c0));
-                        }
-                    } else {
-                        if (grad_mu) __builtin_nontemporal_store(om[0], grad_mu + off + c0);
-                        if (grad_sigma) __builtin_nontemporal_store(os[0], grad_sigma + off + c0);
-                    }
+                    if (grad_mu) store_piece<VEC>(grad_mu + off + c0, om);
+                    if (grad_sigma) store_piece<VEC>(grad_sigma + off + c0, os);
                 }
             }
             if (grad_value && gl == G - 1) grad_value[row] = k3[k];
@@ -265,32 +242,20 @@ __global__ __launch_bounds__(256) void gauss_heads_fwd_kernel(const float* __res
     }
 }
 
-// row_cfg with 4 pieces: the group is one DPP row (16 lanes) or less while 4 pieces per lane suffice (A <= 256 with 16-byte
-// loads, A <= 64 without); longer rows take the whole wave with up to 4 (16-byte) or 16 (4-byte) pieces per lane: A <= 1024
-// either way.  4, not categorical.hip's 8: eight 16-byte pieces of five inputs would be 160 VGPRs for one row.
-constexpr int kRowPieces = 4;
-constexpr long kRowGridCap = 256L * 1024;   // short-lived workgroups, as the categorical row kernels; above it they loop
-
 int gauss_forward(const float* mu_new, const float* sigma_new, const float* mu_old, const float* sigma_old,
                   const float* action, const PpoOp& op, long rows, int A, float* partials, const float* scales, float* out5,
                   hipStream_t st) {
     const bool v4 = aligned(mu_new, 16) && aligned(sigma_new, 16) && aligned(mu_old, 16) && aligned(sigma_old, 16) &&
                     aligned(action, 16);
-    const RowCfg cfg = row_cfg(A, v4, kRowPieces);
-#define HPC_RLL_GAUSS_FWD_CASE(G_, V_, E_)                                                                            \
-    if (cfg.g == G_ && cfg.vec == V_ && cfg.e == E_) {                                                                \
-        /* at most kFoldMaxGrid workgroups, which loop: the sums are folded inside the launch */                       \
-        const long grid = row_grid(rows, (256 / G_) * RowsPerIter<V_, E_>::value, kFoldMaxGrid);                      \
-        const ScanFold fold = make_fold(st, PpoOp::NACC, scales, out5, grid);                                         \
-        hipLaunchKernelGGL((ppo_gauss_fwd_kernel<G_, V_, E_>), dim3((unsigned)grid), dim3(256), 0, st, mu_new,         \
-                           sigma_new, mu_old, sigma_old, action, op, rows, A, partials, fold);                        \
-        const int rc = last_error();                                                                                  \
-        if (rc || fold.out) return rc;                                                                                \
-        return finalize_sums(partials, (int)grid, PpoOp::NACC, scales, out5, st);                                     \
-    }
-    HPC_RLL_ROW4_TABLE(HPC_RLL_GAUSS_FWD_CASE)
-#undef HPC_RLL_GAUSS_FWD_CASE
-    return HPC_RLL_EUNSUPPORTED;
+    return with_row4(row_cfg(A, v4, kRow4Pieces), [&](auto G_, auto V_, auto E_) {
+        constexpr int G = G_, V = V_, E = E_;
+        long grid = 0;
+        return launch_rows_folded(rows, (256 / G) * RowsPerIter<V, E>::value, PpoOp::NACC, scales, out5, partials, st, &grid,
+                                  [&](unsigned blocks, const ScanFold& fold) {
+            hipLaunchKernelGGL((ppo_gauss_fwd_kernel<G, V, E>), dim3(blocks), dim3(256), 0, st, mu_new, sigma_new, mu_old,
+                               sigma_old, action, op, rows, A, partials, fold);
+        });
+    });
 }
 
 int gauss_backward(const float* mu_new, const float* sigma_new, const float* action, const float* c1, const float* c2,
@@ -298,17 +263,13 @@ int gauss_backward(const float* mu_new, const float* sigma_new, const float* act
                    float* grad_value, long rows, int A, hipStream_t st) {
     const bool v4 = aligned(mu_new, 16) && aligned(sigma_new, 16) && aligned(action, 16) && aligned(grad_mu, 16) &&
                     aligned(grad_sigma, 16);   // (a gradient that is not asked for restricts nothing)
-    const RowCfg cfg = row_cfg(A, v4, kRowPieces);
-#define HPC_RLL_GAUSS_BWD_CASE(G_, V_, E_)                                                                            \
-    if (cfg.g == G_ && cfg.vec == V_ && cfg.e == E_) {                                                                \
-        const unsigned grid = row_grid(rows, (256 / G_) * RowsPerIter<V_, E_>::value, kRowGridCap);                   \
-        hipLaunchKernelGGL((ppo_gauss_bwd_kernel<G_, V_, E_>), dim3(grid), dim3(256), 0, st, mu_new,                   \
-                           sigma_new, action, c1, c2, c3, g_p, g_e, g_v, grad_mu, grad_sigma, grad_value, rows, A);   \
-        return last_error();                                                                                          \
-    }
-    HPC_RLL_ROW4_TABLE(HPC_RLL_GAUSS_BWD_CASE)
-#undef HPC_RLL_GAUSS_BWD_CASE
-    return HPC_RLL_EUNSUPPORTED;
+    return with_row4(row_cfg(A, v4, kRow4Pieces), [&](auto G_, auto V_, auto E_) {
+        constexpr int G = G_, V = V_, E = E_;
+        const unsigned grid = row_grid(rows, (256 / G) * RowsPerIter<V, E>::value, kUnfoldedGridCap);
+        hipLaunchKernelGGL((ppo_gauss_bwd_kernel<G, V, E>), dim3(grid), dim3(256), 0, st, mu_new, sigma_new, action, c1, c2,
+                           c3, g_p, g_e, g_v, grad_mu, grad_sigma, grad_value, rows, A);
+        return last_error();
+    });
 }
 
 }  // namespace
@@ -325,17 +286,13 @@ int gaussian_heads_forward(const float* mu_t, const float* sigma_t, const float*
     if (A > kGaussMaxA) return HPC_RLL_EUNSUPPORTED;
     if (rows == 0) return HPC_RLL_OK;
     const bool v4 = aligned(mu_t, 16) && aligned(sigma_t, 16) && aligned(mu_b, 16) && aligned(sigma_b, 16) && aligned(action, 16);
-    const RowCfg cfg = row_cfg(A, v4, kRowPieces);
-#define HPC_RLL_GAUSS_HEADS_CASE(G_, V_, E_)                                                                          \
-    if (cfg.g == G_ && cfg.vec == V_ && cfg.e == E_) {                                                                \
-        const unsigned grid = row_grid(rows, (256 / G_) * RowsPerIter<V_, E_>::value, kRowGridCap);                   \
-        hipLaunchKernelGGL((gauss_heads_fwd_kernel<G_, V_, E_>), dim3(grid), dim3(256), 0, st, mu_t,                   \
-                           sigma_t, mu_b, sigma_b, action, logp_t, ent, logp_b, log_ratio, rows, A);                  \
-        return last_error();                                                                                          \
-    }
-    HPC_RLL_ROW4_TABLE(HPC_RLL_GAUSS_HEADS_CASE)
-#undef HPC_RLL_GAUSS_HEADS_CASE
-    return HPC_RLL_EUNSUPPORTED;
+    return with_row4(row_cfg(A, v4, kRow4Pieces), [&](auto G_, auto V_, auto E_) {
+        constexpr int G = G_, V = V_, E = E_;
+        const unsigned grid = row_grid(rows, (256 / G) * RowsPerIter<V, E>::value, kUnfoldedGridCap);
+        hipLaunchKernelGGL((gauss_heads_fwd_kernel<G, V, E>), dim3(grid), dim3(256), 0, st, mu_t, sigma_t, mu_b, sigma_b,
+                           action, logp_t, ent, logp_b, log_ratio, rows, A);
+        return last_error();
+    });
 }
 
 }  // namespace hpc_rll

@@ -234,13 +234,11 @@ __global__ __launch_bounds__(256) void token_logp_kernel(const Elem* __restrict_
     }
 }
 
-// The dispatch records (hpc_rll_grpo_last_config): plain ints of the host process, not synchronised.  [0] = launches so far.
+// The dispatch records (hpc_rll_grpo_last_config)
 constexpr int kHeadInts = 7, kTokenInts = 3, kGradInts = 6;
-int g_grpo_head[kHeadInts], g_grpo_token[kTokenInts], g_grpo_grad[kGradInts];
-template <int K> void grpo_note(int (&rec)[K], const int (&vals)[K - 1]) {
-    ++rec[0];
-    for (int i = 1; i < K; ++i) rec[i] = vals[i - 1];
-}
+LaunchRecord<kHeadInts> g_grpo_head;
+LaunchRecord<kTokenInts> g_grpo_token;
+LaunchRecord<kGradInts> g_grpo_grad;
 
 long row_grid_of(long rows, int rpw) {
     long grid = (rows + rpw - 1) / rpw;
@@ -264,7 +262,7 @@ int token_logp_launch(const void* xv, const int64_t* action, const float* weight
     else HPC_RLL_GRPO_HEAD(false, 64);
 #undef HPC_RLL_GRPO_HEAD
     const int rc = last_error();
-    if (!rc) grpo_note(g_grpo_head, {ElemIO<Elem>::kCode, 16, al ? 0 : 1, wide_row ? 256 : 64, rpw, (int)grid});
+    if (!rc) g_grpo_head.note({ElemIO<Elem>::kCode, 16, al ? 0 : 1, wide_row ? 256 : 64, rpw, (int)grid});
     return rc;
 }
 int token_logp_any(const void* x, int elem, const int64_t* action, const float* weight, float* logp, float* lse, long rows,
@@ -448,7 +446,7 @@ int token_grad_launch(const void* xv, const int64_t* action, const float* lse, c
 #undef HPC_RLL_GRPO_GRAD
     const int rc = last_error();
     if (!rc)
-        grpo_note(g_grpo_grad, {ElemIO<Elem>::kCode, wide ? 16 : (int)sizeof(Elem), wide_row ? 256 : 64, rpw, (int)grid});
+        g_grpo_grad.note({ElemIO<Elem>::kCode, wide ? 16 : (int)sizeof(Elem), wide_row ? 256 : 64, rpw, (int)grid});
     return rc;
 }
 int token_grad_any(const void* x, int elem, const int64_t* action, const float* lse, const float* coef, const float* g,
@@ -552,7 +550,7 @@ extern "C" int hpc_rll_grpo_forward(const void* logit_new, int elem_new, const v
         rc = finalize_sums(partials, (int)grid, kGrpoSums, scales, sums, st);
         if (rc) return rc;
     }
-    grpo_note(g_grpo_token, {256, (int)grid});
+    g_grpo_token.note({256, (int)grid});
     hipLaunchKernelGGL(grpo_info_kernel, dim3(1), dim3(64), 0, st, sums, out4);
     return last_error();
 }
@@ -573,14 +571,9 @@ extern "C" int hpc_rll_grpo_backward(const float* g_loss, const void* logit_new,
 
 extern "C" int hpc_rll_grpo_last_config(int* out) {
     if (!out) return HPC_RLL_EINVAL;
-    auto put = [&](const int* rec, int n) {
-        out[0] = rec[0];
-        for (int i = 1; i < n; ++i) out[i] = rec[0] ? rec[i] : -1;   // no launch yet
-        out += n;
-    };
-    put(g_grpo_head, kHeadInts);
-    put(g_grpo_token, kTokenInts);
-    put(g_grpo_grad, kGradInts);
+    g_grpo_head.read(out);
+    g_grpo_token.read(out + kHeadInts);
+    g_grpo_grad.read(out + kHeadInts + kTokenInts);
     return HPC_RLL_OK;
 }
 static_assert(HPC_RLL_GRPO_CONFIG_INTS == kHeadInts + kTokenInts + kGradInts, "the layout documented in hpc_rll_hip.h");

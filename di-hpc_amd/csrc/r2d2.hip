@@ -42,10 +42,6 @@ namespace {
 constexpr int kR2d2MaxN = kRowTableMaxN;   // 64 lanes x 16 floats per lane and input
 constexpr float kRescaleEps = 1e-2f;       // as QNStepTDRescale
 
-struct AddOp { static __device__ __forceinline__ float f(float a, float b) { return a + b; } };
-struct MaxOp { static __device__ __forceinline__ float f(float a, float b) { return fmaxf(a, b); } };
-struct MinOp { static __device__ __forceinline__ float f(float a, float b) { return fminf(a, b); } };
-
 // ================================================================================================
 // the heads: rows [row0, rows) of q, target_q and action, row = t*B + b
 // ================================================================================================
@@ -72,7 +68,7 @@ __global__ __launch_bounds__(256) void r2d2_heads_kernel(const float* __restrict
         }
 #pragma unroll
         for (int k = 0; k < R; ++k) {
-            const int ai = (a[k] >= 0 && a[k] < (long)N) ? (int)a[k] : -1;
+            const int ai = action_index(a[k], N);
             // ---- the maximum of the selecting row; padding counts as -inf
             float mx = -INFINITY;
 #pragma unroll
@@ -119,33 +115,24 @@ __global__ __launch_bounds__(256) void r2d2_heads_kernel(const float* __restrict
     }
 }
 
-// The dispatch records (hpc_rll_r2d2_last_config): plain ints of the host process, like the scan family's; not synchronised.
-// [0] = launches so far; zero at load
+// The dispatch records (hpc_rll_r2d2_last_config)
 constexpr int kHeadInts = 7, kWindowInts = 5, kPrioInts = 2, kBwdInts = 3;
-int g_r2d2_heads[kHeadInts], g_r2d2_window[kWindowInts], g_r2d2_prio[kPrioInts], g_r2d2_bwd[kBwdInts];
-template <int K> void r2d2_note(int (&rec)[K], const int (&vals)[K - 1]) {
-    ++rec[0];
-    for (int i = 1; i < K; ++i) rec[i] = vals[i - 1];
-}
+LaunchRecord<kHeadInts> g_r2d2_heads;
+LaunchRecord<kWindowInts> g_r2d2_window;
+LaunchRecord<kPrioInts> g_r2d2_prio;
+LaunchRecord<kBwdInts> g_r2d2_bwd;
 
 int r2d2_heads(const float* q, const float* tq, const int64_t* action, float* qa, float* v, long row0, long rows, int N,
                int double_q, int rescale, hipStream_t st) {
-    // row_cfg with 4 pieces, as Retrace's heads
-    const RowCfg cfg = row_cfg(N, aligned(q, 16) && aligned(tq, 16), 4);
-#define HPC_RLL_R2D2_HEADS_CASE(G_, V_, E_)                                                                           \
-    if (cfg.g == G_ && cfg.vec == V_ && cfg.e == E_) {                                                                \
-        /* short-lived workgroups, as Retrace's heads; above the cap they loop */                                     \
-        constexpr int R_ = RowsPerIter<V_, E_>::value;                                                                \
-        const unsigned grid = row_grid(rows - row0, (256 / G_) * R_, 256L * 1024);                                    \
-        hipLaunchKernelGGL((r2d2_heads_kernel<G_, V_, E_>), dim3(grid), dim3(256), 0, st, q, tq, action, qa, v, row0,  \
-                           rows, N, double_q, rescale);                                                               \
-        const int rc = last_error();                                                                                  \
-        if (!rc) r2d2_note(g_r2d2_heads, {G_, V_, E_, R_, (double_q ? 1 : 0) | (rescale ? 2 : 0), (int)grid});         \
-        return rc;                                                                                                    \
-    }
-    HPC_RLL_ROW4_TABLE(HPC_RLL_R2D2_HEADS_CASE)
-#undef HPC_RLL_R2D2_HEADS_CASE
-    return HPC_RLL_EUNSUPPORTED;
+    return with_row4(row_cfg(N, aligned(q, 16) && aligned(tq, 16), kRow4Pieces), [&](auto G_, auto V_, auto E_) {
+        constexpr int G = G_, V = V_, E = E_, R = RowsPerIter<V, E>::value;
+        const unsigned grid = row_grid(rows - row0, (256 / G) * R, kUnfoldedGridCap);
+        hipLaunchKernelGGL((r2d2_heads_kernel<G, V, E>), dim3(grid), dim3(256), 0, st, q, tq, action, qa, v, row0, rows, N,
+                           double_q, rescale);
+        const int rc = last_error();
+        if (!rc) g_r2d2_heads.note({G, V, E, R, (double_q ? 1 : 0) | (rescale ? 2 : 0), (int)grid});
+        return rc;
+    });
 }
 
 // ================================================================================================
@@ -160,9 +147,7 @@ struct R2d2WindowArgs {
 template <int MT, bool HD, int WM, int NT>
 __global__ __launch_bounds__(NT) void r2d2_window_kernel(const R2d2WindowArgs p, float* __restrict__ partials,
                                                          const ScanFold fold) {
-    constexpr int NWV = NT / 64;
-    __shared__ float red[NWV];
-    float acc = 0.f;
+    float acc[1] = {0.f};
     for (long i = (long)blockIdx.x * NT + threadIdx.x; i < p.n; i += (long)gridDim.x * NT) {
         const size_t o = p.first + (size_t)i;
         const long a = p.action[o];
@@ -177,21 +162,11 @@ __global__ __launch_bounds__(NT) void r2d2_window_kernel(const R2d2WindowArgs p,
         if (p.rescale) G = h_transform(G, kRescaleEps);
         const float d = (a >= 0 && a < (long)p.N) ? qa - G : 0.f;   // an action outside: the step is dropped
         const float wd = WM ? w * d : d;
-        acc = fmaf(wd, d, acc);
+        acc[0] = fmaf(wd, d, acc[0]);
         __builtin_nontemporal_store(d * d, p.td + i);
         __builtin_nontemporal_store((2.f * wd) * p.scale, p.delta + o);
     }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const float s = wave_sum(acc);
-    if (lane == 0) red[wv] = s;
-    __syncthreads();
-    float sum = 0.f;
-    if (threadIdx.x == 0) {
-        if (NWV == 4) sum = (red[0] + red[1]) + (red[2] + red[3]);
-        else
-            for (int i = 0; i < NWV; ++i) sum += red[i];
-    }
-    publish_sums<1, NT>(sum, partials, fold);
+    publish_block_sums<1, NT>(acc, partials, fold);
 }
 
 template <int MT, bool HD, int WM>
@@ -209,7 +184,7 @@ int r2d2_window_launch(const R2d2WindowArgs& p, float* partials, float* loss, hi
     if (!fold.out) rc = finalize_sums(partials, (int)grid, 1, &p.scale, loss, st);
     if (!rc) {
         const int flags = (HD ? 1 + MT : 0) | (WM << 2) | (p.rescale ? 16 : 0);
-        r2d2_note(g_r2d2_window, {(int)nt, flags, (int)grid, fold.out ? 1 : 2});
+        g_r2d2_window.note({(int)nt, flags, (int)grid, fold.out ? 1 : 2});
     }
     return rc;
 }
@@ -322,7 +297,7 @@ extern "C" int hpc_rll_r2d2_forward(const float* q, const float* target_q, const
     const unsigned grid = (unsigned)(((long)B + 63) / 64);
     hipLaunchKernelGGL(r2d2_priority_kernel, dim3(grid), dim3(256), 0, st, td_error, priority, (int)L, B, priority_eta);
     rc = last_error();
-    if (!rc) r2d2_note(g_r2d2_prio, {(int)grid});
+    if (!rc) g_r2d2_prio.note({(int)grid});
     return rc;
 }
 
@@ -340,21 +315,16 @@ extern "C" int hpc_rll_r2d2_backward(const float* g_loss, const int64_t* action,
     long grid = 0;
     const int rc = launch_onehot_stream(value, g_loss, grad_q, (size_t)T * B * N, N, (hipStream_t)stream, &vec, &grid);
     if (rc != (int)hipSuccess) return rc;
-    r2d2_note(g_r2d2_bwd, {vec, (int)grid});
+    g_r2d2_bwd.note({vec, (int)grid});
     return HPC_RLL_OK;
 }
 
 extern "C" int hpc_rll_r2d2_last_config(int* out) {
     if (!out) return HPC_RLL_EINVAL;
-    auto put = [&](const int* rec, int n) {
-        out[0] = rec[0];
-        for (int i = 1; i < n; ++i) out[i] = rec[0] ? rec[i] : -1;   // no launch yet
-        out += n;
-    };
-    put(g_r2d2_heads, kHeadInts);
-    put(g_r2d2_window, kWindowInts);
-    put(g_r2d2_prio, kPrioInts);
-    put(g_r2d2_bwd, kBwdInts);
+    g_r2d2_heads.read(out);
+    g_r2d2_window.read(out + kHeadInts);
+    g_r2d2_prio.read(out + kHeadInts + kWindowInts);
+    g_r2d2_bwd.read(out + kHeadInts + kWindowInts + kPrioInts);
     return HPC_RLL_OK;
 }
 static_assert(HPC_RLL_R2D2_CONFIG_INTS == kHeadInts + kWindowInts + kPrioInts + kBwdInts, "the layout documented in hpc_rll_hip.h");

@@ -44,7 +44,6 @@ namespace hpc_rll {
 namespace {
 
 constexpr int kRetraceMaxN = kRowTableMaxN;   // 64 lanes x 16 floats per lane and input
-constexpr float kFltMax = 3.402823466e38f;
 
 // ================================================================================================
 // drop-in form: qa = q_values[t,b,a], c = lambda*min(1, ratio[t,b,a]) as coalesced (T,B) streams
@@ -63,25 +62,14 @@ __global__ __launch_bounds__(256) void retrace_gather_kernel(const float* __rest
 }
 
 // ================================================================================================
-// fused form: the heads, with the ops of their group all-reduces (group_all, rowgroup.hpp)
+// fused form: the heads
 // ================================================================================================
-struct AddOp { static __device__ __forceinline__ float f(float a, float b) { return a + b; } };
-struct MaxOp { static __device__ __forceinline__ float f(float a, float b) { return fmaxf(a, b); } };
-
 // maximum, partition sum (relative to the maximum) and the selected logit of a row, in every lane of the group; -inf logits
 // (masked actions) are clamped to the most negative finite float as categorical.hip does, padding counts as that value
 template <int G, int VEC, int E>
 __device__ __forceinline__ void softmax_stats(const RowSlice<G, VEC, E>& r, int N, int gl, int ai, float (&ex)[E * VEC],
                                               float& m, float& s, float& xa) {
-    float mx = -kFltMax;
-#pragma unroll
-    for (int e = 0; e < E; ++e)
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) {
-            const int c = (e * G + gl) * VEC + k;
-            mx = fmaxf(mx, c < N ? fmaxf(r.x[e * VEC + k], -kFltMax) : -kFltMax);
-        }
-    m = group_all<G, MaxOp>(mx);
+    m = row_max_finite<G, VEC, E>(r.x, N, gl);
     float sum = 0.f, sel = 0.f;
 #pragma unroll
     for (int e = 0; e < E; ++e)
@@ -125,7 +113,7 @@ __global__ __launch_bounds__(256) void retrace_heads_fwd_kernel(const float* __r
         }
 #pragma unroll
         for (int k = 0; k < R; ++k) {
-            const int ai = (a[k] >= 0 && a[k] < (long)N) ? (int)a[k] : -1;
+            const int ai = action_index(a[k], N);
             float ex[E * VEC], eb[E * VEC];
             float mt, st, xa, mb, sb, ya;
             softmax_stats<G, VEC, E>(ts[k], N, gl, ai, ex, mt, st, xa);
@@ -159,20 +147,13 @@ __global__ __launch_bounds__(256) void retrace_heads_fwd_kernel(const float* __r
 int retrace_heads(const float* q, const float* tgt, const float* beh, const int64_t* action, float* v_out, float* qa_out,
                   float* c_out, int T, int B, int N, float lambda, hipStream_t st) {
     const long rows = ((long)T + 1) * B, TB = (long)T * B;
-    // row_cfg with 4 pieces, as gaussian.hip (at 8, the three slices and two sets of exponentials of ONE row would be 160
-    // VGPRs): one DPP row (16 lanes) or less while 4 pieces per lane suffice (N <= 256 with 16-byte loads, N <= 64 without)
-    const RowCfg cfg = row_cfg(N, aligned(q, 16) && aligned(tgt, 16) && aligned(beh, 16), 4);
-#define HPC_RLL_RETRACE_HEADS_CASE(G_, V_, E_)                                                                        \
-    if (cfg.g == G_ && cfg.vec == V_ && cfg.e == E_) {                                                                \
-        /* short-lived workgroups, as gaussian.hip's heads; above the cap they loop */                                \
-        const unsigned grid = row_grid(rows, (256 / G_) * RowsPerIter<V_, E_>::value, 256L * 1024);                   \
-        hipLaunchKernelGGL((retrace_heads_fwd_kernel<G_, V_, E_>), dim3(grid), dim3(256), 0, st, q, tgt, beh,          \
-                           action, v_out, qa_out, c_out, rows, TB, (long)B, N, lambda);                               \
-        return last_error();                                                                                          \
-    }
-    HPC_RLL_ROW4_TABLE(HPC_RLL_RETRACE_HEADS_CASE)
-#undef HPC_RLL_RETRACE_HEADS_CASE
-    return HPC_RLL_EUNSUPPORTED;
+    return with_row4(row_cfg(N, aligned(q, 16) && aligned(tgt, 16) && aligned(beh, 16), kRow4Pieces), [&](auto G_, auto V_, auto E_) {
+        constexpr int G = G_, V = V_, E = E_;
+        const unsigned grid = row_grid(rows, (256 / G) * RowsPerIter<V, E>::value, kUnfoldedGridCap);
+        hipLaunchKernelGGL((retrace_heads_fwd_kernel<G, V, E>), dim3(grid), dim3(256), 0, st, q, tgt, beh, action, v_out,
+                           qa_out, c_out, rows, TB, (long)B, N, lambda);
+        return last_error();
+    });
 }
 
 // ================================================================================================

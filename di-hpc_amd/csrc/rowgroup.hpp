@@ -1,4 +1,5 @@
-// rowgroup.hpp -- the row-per-lane-group mapping of the policy-head kernels (categorical.hip, gaussian.hip, retrace.hip).
+// rowgroup.hpp -- the row-per-lane-group mapping of the head kernels: categorical.hip, gaussian.hip, retrace.hip, acer.hip,
+// coma.hip, r2d2.hip and sac.hip (grpo.hip uses group_all alone).
 //
 // A row of N floats is owned by an aligned GROUP of G lanes (G = 1..64, a power of two), 256 / G groups per workgroup.  Lane
 // gl of the group holds E pieces of VEC consecutive floats, piece e at column (e*G + gl)*VEC, of every (rows,N) input, in
@@ -8,11 +9,18 @@
 // bb + k*(256/G) + gi, so for a fixed k the groups of a workgroup read consecutive rows: one contiguous span per load
 // instruction whatever G is.
 //
-// Device side: RowSlice, RowsPerIter, dpp_mov, group_all.  Host side: row_cfg (which G, VEC, E for an N), row_grid, and the
-// table of configurations the rule gives the Gaussian and Retrace heads, checked against the rule at compile time.
+// Device side: RowSlice, RowsPerIter, dpp_mov, group_all with its ops (AddOp, MaxOp, MinOp); for the softmax heads
+// row_max_finite (the clamped maximum), action_index (the column an action selects) and store_piece (a lane's piece of an
+// output row).
+// Host side: row_cfg (which G, VEC, E for an N), row_grid, the table of configurations the rule gives at kRow4Pieces pieces
+// per lane, checked against the rule at compile time and its dispatcher with_row4 (launch_rows_folded, for the
+// forwards that end in loss sums, is in colscan.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
+#include "hpc_rll_hip.h"
 #include "wave.hpp"
 
 namespace hpc_rll {
@@ -21,7 +29,7 @@ namespace hpc_rll {
 template <int CTRL> __device__ __forceinline__ float dpp_mov(float x) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xF, 0xF, true));
 }
-// Op::f(a, b) is the unit's own (a sum, or its form of max: what a max may assume about NaNs differs between the units)
+// Op::f(a, b): AddOp, MaxOp or MinOp below, or the unit's own (categorical.hip's max assumes other things about NaNs)
 template <int G, class Op> __device__ __forceinline__ float group_all(float x) {
     if (G >= 2) x = Op::f(x, dpp_mov<0xB1>(x));    // quad_perm [1,0,3,2]
     if (G >= 4) x = Op::f(x, dpp_mov<0x4E>(x));    // quad_perm [2,3,0,1]
@@ -31,6 +39,10 @@ template <int G, class Op> __device__ __forceinline__ float group_all(float x) {
     if (G >= 64) x = Op::f(x, __shfl_xor(x, 32, 64));
     return x;
 }
+
+struct AddOp { static __device__ __forceinline__ float f(float a, float b) { return a + b; } };
+struct MaxOp { static __device__ __forceinline__ float f(float a, float b) { return fmaxf(a, b); } };
+struct MinOp { static __device__ __forceinline__ float f(float a, float b) { return fminf(a, b); } };
 
 // Per-lane slice of one row: E pieces of VEC consecutive floats, piece e at column (e*G + gl)*VEC.
 // load() only ISSUES the (nontemporal: a row is read exactly once) loads: every lane loads unconditionally -- padding
@@ -63,6 +75,37 @@ struct RowSlice {
 // lane within the register budget of 256-thread workgroups.
 template <int VEC, int E> struct RowsPerIter { static constexpr int value = (E * VEC <= 4) ? 4 : ((E * VEC <= 8) ? 2 : 1); };
 
+// ---- what the softmax heads share beyond the slice
+constexpr float kFltMax = 3.402823466e38f;
+
+// the maximum of a row of logits in every lane of the group; -inf (a masked action) counts as the most negative finite
+// float, as does padding
+template <int G, int VEC, int E> __device__ __forceinline__ float row_max_finite(const float* x, int N, int gl) {
+    float mx = -kFltMax;
+#pragma unroll
+    for (int e = 0; e < E; ++e)
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+            const int c = (e * G + gl) * VEC + j;
+            mx = fmaxf(mx, c < N ? fmaxf(x[e * VEC + j], -kFltMax) : -kFltMax);
+        }
+    return group_all<G, MaxOp>(mx);
+}
+
+// the column an action selects, -1 outside [0, N): it then matches no column
+__device__ __forceinline__ int action_index(long a, int N) { return (a >= 0 && a < (long)N) ? (int)a : -1; }
+
+// a lane's piece of an output row (written exactly once: nontemporal), 16 bytes when VEC == 4
+template <int VEC> __device__ __forceinline__ void store_piece(float* dst, const float (&o)[VEC]) {
+    if constexpr (VEC == 4) {
+        vfloat4 t;
+        t.x = o[0]; t.y = o[1]; t.z = o[2]; t.w = o[3];
+        __builtin_nontemporal_store(t, reinterpret_cast<vfloat4*>(dst));
+    } else {
+        __builtin_nontemporal_store(o[0], dst);
+    }
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------------
 struct RowCfg { int g, vec, e; };
 
@@ -86,8 +129,13 @@ inline unsigned row_grid(long rows, long rows_per_block, long cap) {
     return (unsigned)g;
 }
 
-// The (G, VEC, E) of row_cfg(N, ., 4) for 1 <= N <= kRowTableMaxN (64 lanes x 16 floats per lane and input): the kernels
-// the Gaussian and Retrace heads instantiate.
+// Pieces per lane of every head but the categorical one: a unit holds three to five slices of a row at once, and at 16
+// floats per slice that is 48 to 80 VGPRs for ONE row (categorical.hip's 8 pieces would be twice that).
+constexpr int kRow4Pieces = 4;
+// The grid cap of a row kernel that ends in no sums: short-lived workgroups; above it they loop.
+constexpr long kUnfoldedGridCap = 256L * 1024;
+// The (G, VEC, E) of row_cfg(N, ., kRow4Pieces) for 1 <= N <= kRowTableMaxN (64 lanes x 16 floats per lane and input): the
+// kernels these heads instantiate.
 constexpr int kRowTableMaxN = 1024;
 #define HPC_RLL_ROW4_TABLE(CASE)                                                                                      \
     CASE(1, 4, 1) CASE(2, 4, 1) CASE(4, 4, 1) CASE(8, 4, 1) CASE(16, 4, 1) CASE(16, 4, 2) CASE(16, 4, 4)             \
@@ -101,11 +149,21 @@ constexpr int kRowTableMaxN = 1024;
 constexpr bool row4_table_complete() {
     for (int n = 1; n <= kRowTableMaxN; ++n)
         for (int v4 = 0; v4 < 2; ++v4) {
-            const RowCfg c = row_cfg(n, v4 != 0, 4);
+            const RowCfg c = row_cfg(n, v4 != 0, kRow4Pieces);
             if (!(false HPC_RLL_ROW4_TABLE(HPC_RLL_ROW_MATCH))) return false;
         }
     return true;
 }
-static_assert(row4_table_complete(), "HPC_RLL_ROW4_TABLE misses a configuration row_cfg(N, ., 4) returns for N <= kRowTableMaxN");
+static_assert(row4_table_complete(), "HPC_RLL_ROW4_TABLE misses a configuration row_cfg(N, ., kRow4Pieces) returns for N <= kRowTableMaxN");
+
+// f(G, V, E) as std::integral_constants for the table entry that equals cfg; its status, or HPC_RLL_EUNSUPPORTED
+template <int N> using RowInt = std::integral_constant<int, N>;
+template <class F> int with_row4(const RowCfg& cfg, F&& f) {
+#define HPC_RLL_ROW4_CASE(G_, V_, E_) \
+    if (cfg.g == G_ && cfg.vec == V_ && cfg.e == E_) return f(RowInt<G_>{}, RowInt<V_>{}, RowInt<E_>{});
+    HPC_RLL_ROW4_TABLE(HPC_RLL_ROW4_CASE)
+#undef HPC_RLL_ROW4_CASE
+    return HPC_RLL_EUNSUPPORTED;
+}
 
 }  // namespace hpc_rll

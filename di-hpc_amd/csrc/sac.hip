@@ -54,10 +54,6 @@ namespace {
 
 constexpr int kSacMaxN = kRowTableMaxN;   // 64 lanes x 16 floats per lane and input
 constexpr int kSacSums = 4;               // the order of out4: policy, critic, twin critic, entropy
-constexpr float kFltMax = 3.402823466e38f;
-
-struct AddOp { static __device__ __forceinline__ float f(float a, float b) { return a + b; } };
-struct MaxOp { static __device__ __forceinline__ float f(float a, float b) { return fmaxf(a, b); } };
 
 struct SacArgs {
     const float* logit; const float* next_logit; const float* q1; const float* q2; const float* tq1; const float* tq2;
@@ -72,16 +68,7 @@ struct SacArgs {
 template <int G, int VEC, int E, bool TWIN, bool KEEP>
 __device__ __forceinline__ void softmax_pass(float* z, float* c1, const float* c2, int N, int gl, float alpha, float& part,
                                              float& pl) {
-    // ---- maximum; -inf counts as the most negative finite float, as does padding
-    float mx = -kFltMax;
-#pragma unroll
-    for (int e = 0; e < E; ++e)
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-            const int c = (e * G + gl) * VEC + j;
-            mx = fmaxf(mx, c < N ? fmaxf(z[e * VEC + j], -kFltMax) : -kFltMax);
-        }
-    mx = group_all<G, MaxOp>(mx);
+    const float mx = row_max_finite<G, VEC, E>(z, N, gl);
     // ---- partition sum; z <- z - max (clamped: finite)
     float s = 0.f;
 #pragma unroll
@@ -123,7 +110,6 @@ __global__ __launch_bounds__(256) void sac_discrete_fwd_kernel(const SacArgs p, 
                                                                const ScanFold fold) {
     constexpr int GPB = 256 / G;
     constexpr int R = RowsPerIter<VEC, E>::value;
-    __shared__ float red[kSacSums * 4];
     const int gl = threadIdx.x % G;
     const int gi = threadIdx.x / G;
     const float alpha = p.alpha_dev ? p.alpha_dev[0] : p.alpha;
@@ -182,7 +168,7 @@ __global__ __launch_bounds__(256) void sac_discrete_fwd_kernel(const SacArgs p, 
         for (int k = 0; k < R; ++k) {
             const long row = bb + (long)k * GPB + gi;
             const bool live = row < p.rows;
-            const int ai = (a[k] >= 0 && a[k] < (long)N) ? (int)a[k] : -1;
+            const int ai = action_index(a[k], N);
             // the selected critic values, before the slices are overwritten; at most one lane holds a nonzero value
             float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -227,30 +213,11 @@ __global__ __launch_bounds__(256) void sac_discrete_fwd_kernel(const SacArgs p, 
                     const float pn = q1[k].x[i];
                     o[j] = (pn > 0.f) ? (p.scale * pn) * (xs[k].x[i] - f) : 0.f;
                 }
-                if (live && c0 < N) {
-                    if (VEC == 4) {
-                        vfloat4 t;
-                        t.x = o[0]; t.y = o[1]; t.z = o[2]; t.w = o[3];
-                        __builtin_nontemporal_store(t, reinterpret_cast<vfloat4*>(out + c0));
-                    } else {
-                        __builtin_nontemporal_store(o[0], out + c0);
-                    }
-                }
+                if (live && c0 < N) store_piece<VEC>(out + c0, o);
             }
         }
     }
-    // the workgroup's four sums, then the shared epilogue (the only LDS and barriers of the kernel)
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < kSacSums; ++k) {
-        const float s = wave_sum(acc[k]);
-        if (lane == 0) red[k * 4 + w] = s;
-    }
-    __syncthreads();
-    float sum = 0.f;
-    if (threadIdx.x < kSacSums)
-        sum = (red[threadIdx.x * 4] + red[threadIdx.x * 4 + 1]) + (red[threadIdx.x * 4 + 2] + red[threadIdx.x * 4 + 3]);
-    publish_sums<kSacSums, 256>(sum, partials, fold);
+    publish_block_sums<kSacSums, 256>(acc, partials, fold);   // (the only LDS and barriers of the kernel)
 }
 
 // ================================================================================================
@@ -291,12 +258,13 @@ __global__ __launch_bounds__(256) void sac_discrete_bwd_kernel(const SacBwdArgs 
         for (int k = 0; k < R; ++k) {
             const long row = bb + (long)k * GPB + gi;
             if (row >= p.rows) continue;
-            const int ai = (a[k] >= 0 && a[k] < (long)N) ? (int)a[k] : -1;
+            const int ai = action_index(a[k], N);
 #pragma unroll
             for (int e = 0; e < E; ++e) {
                 const int c0 = (e * G + gl) * VEC;
                 if (c0 >= N) continue;
                 const long o = row * (long)N + c0;
+                // (not store_piece: with three outputs behind run-time branches that form measured slower, r18_rowgroup_share.txt)
                 if (VEC == 4) {
                     vfloat4 t;
                     if (GL) {
@@ -324,63 +292,44 @@ __global__ __launch_bounds__(256) void sac_discrete_bwd_kernel(const SacBwdArgs 
     }
 }
 
-// The dispatch records of the forward and the backward (hpc_rll_sac_discrete_last_config): plain ints of the host process,
-// like the scan family's; not synchronised.  {launches so far, G, VEC, E, R, flags, grid}
+// The dispatch records of the forward and the backward (hpc_rll_sac_discrete_last_config):
+// {launches so far, G, VEC, E, R, flags, grid}
 constexpr int kLaunchInts = 7;
-int g_sac_fwd[kLaunchInts], g_sac_bwd[kLaunchInts];   // zero at load
-void sac_note(int* rec, int g, int vec, int e, int r, int flags, long grid) {
-    const int vals[kLaunchInts] = {rec[0] + 1, g, vec, e, r, flags, (int)grid};
-    for (int i = 0; i < kLaunchInts; ++i) rec[i] = vals[i];
-}
-
-// row_cfg with 4 pieces, as acer.hip and coma.hip: three slices of 16 floats are 48 VGPRs for ONE row
-constexpr int kRowPieces = 4;
+LaunchRecord<kLaunchInts> g_sac_fwd, g_sac_bwd;
 
 template <bool TWIN, bool GRAD>
 int sac_forward(const SacArgs& p, float* partials, float* out4, hipStream_t st) {
     const bool v4 = aligned(p.logit, 16) && aligned(p.next_logit, 16) && aligned(p.q1, 16) && aligned(p.q2, 16) &&
                     aligned(p.tq1, 16) && aligned(p.tq2, 16) && aligned(p.unit, 16);   // (an absent operand restricts nothing)
-    const RowCfg cfg = row_cfg(p.N, v4, kRowPieces);
     const float sc[kSacSums] = {p.scale, p.scale, p.scale, p.scale};
     const int flags = (p.weight ? 1 : 0) | (p.done ? (p.done_f32 ? 4 : 2) : 0) | (TWIN ? 8 : 0) | (GRAD ? 16 : 0);
-#define HPC_RLL_SAC_FWD_CASE(G_, V_, E_)                                                                              \
-    if (cfg.g == G_ && cfg.vec == V_ && cfg.e == E_) {                                                                \
-        /* at most kFoldMaxGrid workgroups, which loop: the sums are folded inside the launch */                       \
-        constexpr int R_ = RowsPerIter<V_, E_>::value;                                                                \
-        const long grid = row_grid(p.rows, (256 / G_) * R_, kFoldMaxGrid);                                            \
-        const ScanFold fold = make_fold(st, kSacSums, sc, out4, grid);                                                \
-        hipLaunchKernelGGL((sac_discrete_fwd_kernel<G_, V_, E_, TWIN, GRAD>), dim3((unsigned)grid), dim3(256), 0, st, \
-                           p, partials, fold);                                                                        \
-        const int rc = last_error();                                                                                  \
-        if (rc) return rc;                                                                                            \
-        sac_note(g_sac_fwd, G_, V_, E_, R_, flags, grid);                                                             \
-        if (fold.out) return rc;                                                                                      \
-        return finalize_sums(partials, (int)grid, kSacSums, sc, out4, st);                                            \
-    }
-    HPC_RLL_ROW4_TABLE(HPC_RLL_SAC_FWD_CASE)
-#undef HPC_RLL_SAC_FWD_CASE
-    return HPC_RLL_EUNSUPPORTED;
+    return with_row4(row_cfg(p.N, v4, kRow4Pieces), [&](auto G_, auto V_, auto E_) {
+        constexpr int G = G_, V = V_, E = E_, R = RowsPerIter<V, E>::value;
+        long grid = 0;
+        const int rc = launch_rows_folded(p.rows, (256 / G) * R, kSacSums, sc, out4, partials, st, &grid,
+                                          [&](unsigned blocks, const ScanFold& fold) {
+            hipLaunchKernelGGL((sac_discrete_fwd_kernel<G, V, E, TWIN, GRAD>), dim3(blocks), dim3(256), 0, st, p, partials,
+                               fold);
+        });
+        if (grid) g_sac_fwd.note({G, V, E, R, flags, (int)grid});
+        return rc;
+    });
 }
 
 template <bool GL>
 int sac_backward(const SacBwdArgs& p, hipStream_t st) {
     // an absent operand restricts nothing; the unit gradient counts only when it is read
     const RowCfg cfg = row_cfg(p.N, aligned(GL ? p.unit : nullptr, 16) && aligned(p.grad_logit, 16) &&
-                                        aligned(p.grad_q1, 16) && aligned(p.grad_q2, 16), kRowPieces);
+                                        aligned(p.grad_q1, 16) && aligned(p.grad_q2, 16), kRow4Pieces);
     const int flags = (GL ? 1 : 0) | (p.grad_q1 ? 2 : 0) | (p.grad_q2 ? 4 : 0);
-#define HPC_RLL_SAC_BWD_CASE(G_, V_, E_)                                                                              \
-    if (cfg.g == G_ && cfg.vec == V_ && cfg.e == E_) {                                                                \
-        constexpr int R_ = RowsPerIter<V_, E_>::value;                                                                \
-        /* short-lived workgroups, as COMA's backward; above the cap they loop */                                     \
-        const unsigned grid = row_grid(p.rows, (256 / G_) * R_, 256L * 1024);                                         \
-        hipLaunchKernelGGL((sac_discrete_bwd_kernel<G_, V_, E_, GL>), dim3(grid), dim3(256), 0, st, p);                \
-        const int rc = last_error();                                                                                  \
-        if (!rc) sac_note(g_sac_bwd, G_, V_, E_, R_, flags, (long)grid);                                              \
-        return rc;                                                                                                    \
-    }
-    HPC_RLL_ROW4_TABLE(HPC_RLL_SAC_BWD_CASE)
-#undef HPC_RLL_SAC_BWD_CASE
-    return HPC_RLL_EUNSUPPORTED;
+    return with_row4(cfg, [&](auto G_, auto V_, auto E_) {
+        constexpr int G = G_, V = V_, E = E_, R = RowsPerIter<V, E>::value;
+        const unsigned grid = row_grid(p.rows, (256 / G) * R, kUnfoldedGridCap);
+        hipLaunchKernelGGL((sac_discrete_bwd_kernel<G, V, E, GL>), dim3(grid), dim3(256), 0, st, p);
+        const int rc = last_error();
+        if (!rc) g_sac_bwd.note({G, V, E, R, flags, (int)grid});
+        return rc;
+    });
 }
 
 // floats of the partial-sum region: kSacSums per workgroup of at most kFoldMaxGrid
@@ -446,12 +395,8 @@ extern "C" int hpc_rll_sac_discrete_backward(const float* g_policy, const float*
 
 extern "C" int hpc_rll_sac_discrete_last_config(int* out) {
     if (!out) return HPC_RLL_EINVAL;
-    int* o = out;
-    for (const int* rec : {g_sac_fwd, g_sac_bwd}) {
-        o[0] = rec[0];
-        for (int i = 1; i < kLaunchInts; ++i) o[i] = rec[0] ? rec[i] : -1;   // no launch yet
-        o += kLaunchInts;
-    }
+    g_sac_fwd.read(out);
+    g_sac_bwd.read(out + kLaunchInts);
     return HPC_RLL_OK;
 }
 static_assert(HPC_RLL_SAC_CONFIG_INTS == 2 * 7, "the layout documented in hpc_rll_hip.h");

@@ -31,26 +31,12 @@ namespace {
 template <class Op, int NT>
 __global__ __launch_bounds__(NT) void sample_kernel(const Op op, long n, float* __restrict__ partials,
                                                     const ScanFold fold) {
-    constexpr int NACC = Op::NACC, NWV = NT / 64;
-    __shared__ float red[NACC * NWV];
+    constexpr int NACC = Op::NACC;
     float acc[NACC];
 #pragma unroll
     for (int k = 0; k < NACC; ++k) acc[k] = 0.f;
     for (long i = (long)blockIdx.x * NT + threadIdx.x; i < n; i += (long)gridDim.x * NT) op(i, acc);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NACC; ++k) {
-        const float s = wave_sum(acc[k]);
-        if (lane == 0) red[k * NWV + w] = s;
-    }
-    __syncthreads();
-    float sum = 0.f;
-    if (threadIdx.x < NACC) {
-        if (NWV == 4) sum = (red[threadIdx.x * 4] + red[threadIdx.x * 4 + 1]) + (red[threadIdx.x * 4 + 2] + red[threadIdx.x * 4 + 3]);
-        else
-            for (int i = 0; i < NWV; ++i) sum += red[threadIdx.x * NWV + i];
-    }
-    publish_sums<NACC, NT>(sum, partials, fold);   // with a fold: the last workgroup also finalises the sums (colscan.hpp)
+    publish_block_sums<NACC, NT>(acc, partials, fold);   // with a fold: the last workgroup also finalises the sums (colscan.hpp)
 }
 // launch + finalisation of the NACC sums into `out` (x scale[k])
 template <class Op>
