@@ -32,65 +32,13 @@
 #include "colscan.hpp"
 #include "hostutil.hpp"
 #include "hpc_rll_hip.h"
+#include "lm_head.hpp"
 #include "wave.hpp"
 
 namespace hpc_rll {
 namespace {
 
-constexpr int kGrpoMaxV = 262144;
-constexpr int kWaveRowMaxV = 2048;   // up to here a wave per row, above a workgroup per row
-constexpr int kInFlight = 4;         // 16-byte loads a lane issues before it uses the first
-constexpr float kFltMaxG = 3.402823466e+38f;
-constexpr float kLog2eG = 1.44269504088896340736f, kLn2G = 0.69314718055994530942f;
 constexpr int kGrpoSums = 5;         // loss, sum w kl, sum w r, sum w clipped, sum w
-constexpr long kRowGridMax = 1L << 16;   // workgroups of a row launch; above it they loop (far more than the device holds at once)
-
-typedef unsigned int vuint4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float clampf(float x) { return fmaxf(x, -kFltMaxG); }   // -inf (masked) and NaN -> finite
-__device__ __forceinline__ float ex2(float y) { return __builtin_amdgcn_exp2f(y); }
-__device__ __forceinline__ float as_f(unsigned u) { return __builtin_bit_cast(float, u); }
-__device__ __forceinline__ unsigned as_u(float f) { return __builtin_bit_cast(unsigned, f); }
-
-// ---- the two element types: P elements per 16 bytes
-template <class Elem> struct ElemIO;
-template <> struct ElemIO<float> {
-    static constexpr int P = 4;
-    static constexpr int kCode = 0;
-    static __device__ __forceinline__ float get(const float* p) { return *p; }
-    static __device__ __forceinline__ void put(float* p, float v) { __builtin_nontemporal_store(v, p); }
-    static __device__ __forceinline__ void unpack(const vuint4& v, float* x) {
-        x[0] = as_f(v.x); x[1] = as_f(v.y); x[2] = as_f(v.z); x[3] = as_f(v.w);
-    }
-    static __device__ __forceinline__ vuint4 pack(const float* x) {
-        vuint4 v = {as_u(x[0]), as_u(x[1]), as_u(x[2]), as_u(x[3])};
-        return v;
-    }
-};
-__device__ __forceinline__ unsigned bf16_bits(float f) {   // round to nearest even
-    return (unsigned)__builtin_bit_cast(unsigned short, static_cast<__bf16>(f));
-}
-template <> struct ElemIO<uint16_t> {
-    static constexpr int P = 8;
-    static constexpr int kCode = 1;
-    static __device__ __forceinline__ float get(const uint16_t* p) { return as_f((unsigned)*p << 16); }
-    static __device__ __forceinline__ void put(uint16_t* p, float v) { __builtin_nontemporal_store((uint16_t)bf16_bits(v), p); }
-    static __device__ __forceinline__ void unpack(const vuint4& v, float* x) {
-        const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            x[2 * i] = as_f(w[i] << 16);
-            x[2 * i + 1] = as_f(w[i] & 0xffff0000u);
-        }
-    }
-    static __device__ __forceinline__ vuint4 pack(const float* x) {
-        unsigned w[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) w[i] = bf16_bits(x[2 * i]) | (bf16_bits(x[2 * i + 1]) << 16);
-        vuint4 v = {w[0], w[1], w[2], w[3]};
-        return v;
-    }
-};
 
 // ---- online softmax statistics: s = sum exp(x - m) over what has been seen, m its maximum (never below -FLT_MAX)
 struct MS { float m, s; };
@@ -239,11 +187,6 @@ constexpr int kHeadInts = 7, kTokenInts = 3, kGradInts = 6;
 LaunchRecord<kHeadInts> g_grpo_head;
 LaunchRecord<kTokenInts> g_grpo_token;
 LaunchRecord<kGradInts> g_grpo_grad;
-
-long row_grid_of(long rows, int rpw) {
-    long grid = (rows + rpw - 1) / rpw;
-    return grid < 1 ? 1 : (grid > kRowGridMax ? kRowGridMax : grid);
-}
 
 template <class Elem>
 int token_logp_launch(const void* xv, const int64_t* action, const float* weight, float* logp, float* lse, long rows, int V,
@@ -454,9 +397,6 @@ int token_grad_any(const void* x, int elem, const int64_t* action, const float* 
     return elem == 1 ? token_grad_launch<uint16_t>(x, action, lse, coef, g, grad, rows, V, st)
                      : token_grad_launch<float>(x, action, lse, coef, g, grad, rows, V, st);
 }
-
-bool elem_ok(int e) { return e == HPC_RLL_ELEM_F32 || e == HPC_RLL_ELEM_BF16; }
-size_t elem_size(int e) { return e == HPC_RLL_ELEM_BF16 ? 2 : 4; }
 
 }  // namespace
 }  // namespace hpc_rll

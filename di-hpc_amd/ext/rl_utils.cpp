@@ -3,7 +3,7 @@
 // Two layers in one module:
 //   * the reference's L2 functions `XxxForward(inputs, outputs, scalars...)` / `XxxBackward(inputs, outputs)`
 //     (declared in include/hpc/rll/cuda/rl_utils/entry.h:10-165) -- validated, launched on torch's current stream;
-//   * fused autograd ops (`gae`, `td_lambda`, `vtrace`, `upgo`, `upgo_masked`, `ppo`, `ppo_continuous`, `vtrace_continuous`, `retrace_loss`, `acer_policy_loss`, `coma`, `r2d2_td`, `sac_discrete`, `token_log_prob`, `grpo_policy_loss`, `q_nstep_td`, `dist_nstep_td`, `iqn_nstep_td`,
+//   * fused autograd ops (`gae`, `td_lambda`, `vtrace`, `upgo`, `upgo_masked`, `ppo`, `ppo_continuous`, `vtrace_continuous`, `retrace_loss`, `acer_policy_loss`, `coma`, `r2d2_td`, `sac_discrete`, `token_log_prob`, `grpo_policy_loss`, `token_log_prob_entropy`, `lm_ppo_loss`, `q_nstep_td`, `dist_nstep_td`, `iqn_nstep_td`,
 //     `qrdqn_nstep_td`) -- torch::autograd::Function nodes that allocate outputs, launch and register backward in ONE
 //     pybind call; these are what hpc_rll.rl_utils.* modules use.
 // Host-only C++: every kernel lives behind the C ABI of libhpc_rll_hip.so (include/hpc_rll_hip.h).
@@ -1390,6 +1390,173 @@ struct GrpoFn : public ag::Function<GrpoFn> {
     }
 };
 
+// ======================================================================================================== LM PPO
+// Token-level PPO for language models (hpc_rll_lm_*): the head with entropy, GAE over (B,S), the token loss.
+// (logp, entropy) per token; saves the logits, action, weight, lse and the entropy (8 bytes per token)
+struct TokenLpeFn : public ag::Function<TokenLpeFn> {
+    static ag::tensor_list forward(ag::AutogradContext* ctx, const Tensor& logits, const Tensor& action,
+                                   const OptTensor& weight) {
+        const at::ScalarType st = logits_dtype(logits, "logits");
+        TORCH_CHECK(logits.dim() >= 1, "logits: expected (..., V), got ", logits.sizes());
+        const int64_t V = logits.size(-1);
+        const at::IntArrayRef lead = logits.sizes().slice(0, logits.dim() - 1);
+        check_shape(action, "action", lead, at::kLong);
+        if (has(weight)) check_shape(*weight, "weight", lead);
+        grpo_check_v("token_log_prob_entropy", V);
+        const at::Device dev = logits.device();
+        req(logits, "logits", dev, st);
+        req(action, "action", dev, at::kLong);
+        if (has(weight)) req(*weight, "weight", dev);
+        c10::DeviceGuard g(dev);
+        const int64_t rows = action.numel();
+        Tensor logp = new_f32(action.sizes(), dev), ent = new_f32(action.sizes(), dev), lse = new_f32({rows}, dev);
+        check(hpc_rll_lm_head_forward(vptr(logits), elem_code(st), iptr(action), fptr(weight), fmut(logp), fmut(lse), fmut(ent),
+                                      rows, to_int(V, "V"), stream_of(dev)),
+              "hpc_rll_lm_head_forward");
+        ctx->save_for_backward({logits, action, has(weight) ? *weight : undef(), lse, ent});
+        return {logp, ent};
+    }
+    static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
+        ag::tensor_list out(3);
+        if (!ctx->needs_input_grad(0)) return out;
+        const auto saved = ctx->get_saved_variables();
+        const Tensor &logits = saved[0], &action = saved[1], &weight = saved[2], &lse = saved[3], &ent = saved[4];
+        const at::Device dev = logits.device();
+        c10::DeviceGuard g(dev);
+        Tensor g_lp = grads[0].defined() ? grads[0].contiguous() : undef();
+        Tensor g_h = grads[1].defined() ? grads[1].contiguous() : undef();
+        if (g_lp.defined()) req(g_lp, "grad_logp", dev);
+        if (g_h.defined()) req(g_h, "grad_entropy", dev);
+        Tensor grad = at::empty(logits.sizes(), logits.options());
+        check(hpc_rll_lm_head_backward(fptr(g_lp), fptr(g_h), vptr(logits), elem_code(logits.scalar_type()), iptr(action),
+                                       fptr(weight), fptr(lse), fptr(ent), grad.data_ptr(), action.numel(),
+                                       (int)logits.size(-1), stream_of(dev)),
+              "hpc_rll_lm_head_backward");
+        out[0] = grad;
+        return out;
+    }
+};
+
+// (adv, ret) over (B,S); no gradient
+std::tuple<Tensor, Tensor> lm_gae(const Tensor& value, const OptTensor& weight, const Tensor& reward, const OptTensor& kl,
+                                  double beta, double gamma, double lam, bool whiten) {
+    TORCH_CHECK(value.defined(), "value: expected a tensor, got None");
+    TORCH_CHECK(value.dim() == 2, "value: expected (B,S), got ", value.sizes());
+    const int64_t B = value.size(0), S = value.size(1);
+    check_shape(value, "value", {B, S});
+    if (has(weight)) check_shape(*weight, "weight", {B, S});
+    TORCH_CHECK(reward.defined(), "reward: expected a tensor, got None");
+    TORCH_CHECK(reward.dim() == 1 || reward.dim() == 2, "reward: expected per-token (B,S) or per-sequence (B,), got ",
+                reward.sizes());
+    const bool per_seq = reward.dim() == 1;
+    if (per_seq) check_shape(reward, "reward", {B});
+    else check_shape(reward, "reward", {B, S});
+    if (has(kl)) check_shape(*kl, "kl", {B, S});
+    const at::Device dev = value.device();
+    req(value, "value", dev);
+    if (has(weight)) req(*weight, "weight", dev);
+    req(reward, "reward", dev);
+    if (has(kl)) req(*kl, "kl", dev);
+    c10::DeviceGuard g(dev);
+    Tensor adv = new_f32({B, S}, dev), ret = new_f32({B, S}, dev);
+    const bool empty = B == 0 || S == 0;
+    Tensor ws = new_f32({empty ? 0 : hpc_rll_lm_gae_workspace_floats()}, dev);
+    check(hpc_rll_lm_gae(fptr(value), fptr(weight), fptr(reward), per_seq ? 1 : 0, fptr(kl), fmut(adv), fmut(ret), fmut(ws),
+                         to_int(B, "B"), to_int(S, "S"), (float)beta, (float)gamma, (float)lam, whiten ? 1 : 0, stream_of(dev)),
+          "hpc_rll_lm_gae");
+    return {adv, ret};
+}
+
+// (policy_loss, value_loss, entropy, approx_kl, mean_ratio, clipfrac, den), (1,) each; the first three are differentiable, the
+// gradient flows to logit_new and value_new.  Saves logit_new, action, weight and the workspace.
+struct LmPpoFn : public ag::Function<LmPpoFn> {
+    static ag::tensor_list forward(ag::AutogradContext* ctx, const Tensor& logit_new, const Tensor& old_logp,
+                                   const Tensor& action, const Tensor& adv, const OptTensor& weight, const OptTensor& value_new,
+                                   const OptTensor& value_old, const OptTensor& ret, double clip_ratio,
+                                   std::optional<double> dual_clip, std::optional<double> value_clip, bool seq_mean, bool raw,
+                                   std::optional<double> scale) {
+        const at::ScalarType st = logits_dtype(logit_new, "logit_new");
+        TORCH_CHECK(logit_new.dim() == 3, "logit_new: expected (B,S,V), got ", logit_new.sizes());
+        const int64_t B = logit_new.size(0), S = logit_new.size(1), V = logit_new.size(2);
+        TORCH_CHECK(old_logp.defined(), "old_logp: expected a tensor, got None");
+        check_shape(old_logp, "old_logp", {B, S});
+        check_shape(action, "action", {B, S}, at::kLong);
+        check_shape(adv, "adv", {B, S});
+        if (has(weight)) check_shape(*weight, "weight", {B, S});
+        const int nval = (int)has(value_new) + (int)has(value_old) + (int)has(ret);
+        TORCH_CHECK(nval == 0 || nval == 3, "lm_ppo_loss: value_new, value_old and ret are given all three or none (got ", nval,
+                    " of them)");
+        if (nval) {
+            check_shape(*value_new, "value_new", {B, S});
+            check_shape(*value_old, "value_old", {B, S});
+            check_shape(*ret, "ret", {B, S});
+        }
+        TORCH_CHECK(!dual_clip.has_value() || *dual_clip > 1.0, "dual_clip: expected None or a value above 1, got ", *dual_clip);
+        grpo_check_v("lm_ppo_loss", V);
+        const at::Device dev = logit_new.device();
+        req(logit_new, "logit_new", dev, st);
+        req(old_logp, "old_logp", dev);
+        req(action, "action", dev, at::kLong);
+        req(adv, "adv", dev);
+        if (has(weight)) req(*weight, "weight", dev);
+        if (nval) {
+            req(*value_new, "value_new", dev);
+            req(*value_old, "value_old", dev);
+            req(*ret, "ret", dev);
+        }
+        c10::DeviceGuard g(dev);
+        const bool empty = B == 0 || S == 0 || V == 0;
+        Tensor out8 = new_f32({8}, dev);
+        Tensor ws = new_f32({empty ? 0 : hpc_rll_lm_ppo_workspace_floats(to_int(B, "B"), to_int(S, "S"))}, dev);
+        const float sc = scale.has_value() && *scale > 0.0 ? (float)*scale : 0.f;   // 0: the kernels take 1/B
+        check(hpc_rll_lm_ppo_forward(vptr(logit_new), elem_code(st), fptr(old_logp), iptr(action), fptr(adv), fptr(weight),
+                                     fptr(value_new), fptr(value_old), fptr(ret), fmut(out8), fmut(ws), to_int(B, "B"),
+                                     to_int(S, "S"), to_int(V, "V"), (float)clip_ratio, dual_clip.has_value() ? (float)*dual_clip : 0.f,
+                                     value_clip.has_value() ? 1 : 0, value_clip.has_value() ? (float)*value_clip : 0.f,
+                                     seq_mean ? 1 : 0, raw ? 1 : 0, sc, stream_of(dev)),
+              "hpc_rll_lm_ppo_forward");
+        ctx->save_for_backward({logit_new, action, has(weight) ? *weight : undef(), ws});
+        ctx->saved_data["empty"] = empty;
+        ctx->saved_data["has_value"] = nval == 3;
+        ctx->saved_data["use_den"] = !seq_mean && !raw;
+        // needs_input_grad counts the tensor inputs that are present: value_new follows the four required ones and weight
+        ctx->saved_data["value_edge"] = (int64_t)(has(weight) ? 5 : 4);
+        ag::tensor_list out;
+        for (int k = 0; k < 7; ++k) out.push_back(alias_of(out8, k, 1));
+        ctx->mark_non_differentiable({out[3], out[4], out[5], out[6]});
+        return out;
+    }
+    static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
+        ag::tensor_list out(14);
+        const auto saved = ctx->get_saved_variables();
+        const Tensor &logit_new = saved[0], &action = saved[1], &weight = saved[2], &ws = saved[3];
+        const bool need_l = ctx->needs_input_grad(0);
+        const bool need_v = ctx->saved_data["has_value"].toBool() && ctx->needs_input_grad((size_t)ctx->saved_data["value_edge"].toInt());
+        if (!(need_l || need_v)) return out;
+        const at::Device dev = logit_new.device();
+        c10::DeviceGuard g(dev);
+        if (ctx->saved_data["empty"].toBool()) {
+            if (need_l) out[0] = at::zeros(logit_new.sizes(), logit_new.options());
+            if (need_v) out[5] = at::zeros(action.sizes(), logit_new.options().dtype(at::kFloat));
+            return out;
+        }
+        // an output that did not enter the caller's loss arrives undefined: the kernels take NULL for a zero gradient
+        Tensor g_p = grads[0].defined() ? grad1(grads[0], dev, "grad_policy_loss") : undef();
+        Tensor g_v = grads[1].defined() ? grad1(grads[1], dev, "grad_value_loss") : undef();
+        Tensor g_e = grads[2].defined() ? grad1(grads[2], dev, "grad_entropy") : undef();
+        Tensor grad_l = need_l ? at::empty(logit_new.sizes(), logit_new.options()) : undef();
+        Tensor grad_v = need_v ? new_f32(action.sizes(), dev) : undef();
+        check(hpc_rll_lm_ppo_backward(fptr(g_p), fptr(g_e), fptr(g_v), vptr(logit_new), elem_code(logit_new.scalar_type()),
+                                      iptr(action), fptr(weight), fptr(ws), grad_l.defined() ? grad_l.data_ptr() : nullptr,
+                                      fmut(grad_v), (int)logit_new.size(0), (int)logit_new.size(1), (int)logit_new.size(2),
+                                      ctx->saved_data["use_den"].toBool() ? 1 : 0, stream_of(dev)),
+              "hpc_rll_lm_ppo_backward");
+        out[0] = grad_l;
+        out[5] = grad_v;
+        return out;
+    }
+};
+
 // ==================================================================================================== q n-step TD
 struct QDims { int64_t B, N, nstep; at::Device dev; };
 int64_t check_nstep_reward(const Tensor& reward, int64_t B, const at::Device& dev) {
@@ -2021,6 +2188,26 @@ PYBIND11_MODULE(hpc_rl_utils, m) {
           py::arg("weight") = py::none(), py::arg("clip_ratio") = 0.2, py::arg("beta") = 0.1, py::arg("scale") = py::none(),
           "GRPO token loss over (B,S,V) logits: (loss, mean_kl, mean_ratio, mean_clipped), (1,) each; old / ref are logits "
           "(B,S,V) or log-probs (B,S), ref may be None; differentiable wrt logit_new; scale = 1/(global B) for a sharded caller");
+    m.def("token_log_prob_entropy", [](const Tensor& logits, const Tensor& action, const OptTensor& weight) {
+        return TokenLpeFn::apply(logits, action, weight);
+    }, py::arg("logits"), py::arg("action"), py::arg("weight") = py::none(),
+          "(logp, entropy) per token from one read of (..., V) fp32 or bf16 logits; both differentiable wrt logits");
+    m.def("lm_gae", &lm_gae, py::arg("value"), py::arg("weight"), py::arg("reward"), py::arg("kl") = py::none(),
+          py::arg("beta") = 0.0, py::arg("gamma") = 1.0, py::arg("lam") = 0.95, py::arg("whiten") = true,
+          "Token-level GAE over (B,S) under a response mask: (adv, ret); reward is (B,S) or a terminal score (B,)");
+    m.def("lm_ppo_loss", [](const Tensor& logit_new, const Tensor& old_logp, const Tensor& action, const Tensor& adv,
+                            const OptTensor& weight, const OptTensor& value_new, const OptTensor& value_old,
+                            const OptTensor& ret, double clip_ratio, std::optional<double> dual_clip,
+                            std::optional<double> value_clip, bool seq_mean, bool raw, std::optional<double> scale) {
+        return LmPpoFn::apply(logit_new, old_logp, action, adv, weight, value_new, value_old, ret, clip_ratio, dual_clip,
+                              value_clip, seq_mean, raw, scale);
+    }, py::arg("logit_new"), py::arg("old_logp"), py::arg("action"), py::arg("adv"), py::arg("weight") = py::none(),
+          py::arg("value_new") = py::none(), py::arg("value_old") = py::none(), py::arg("ret") = py::none(),
+          py::arg("clip_ratio") = 0.2, py::arg("dual_clip") = py::none(), py::arg("value_clip") = 0.2,
+          py::arg("seq_mean") = false, py::arg("raw") = false, py::arg("scale") = py::none(),
+          "Token-level PPO over (B,S,V) logits: (policy_loss, value_loss, entropy, approx_kl, mean_ratio, clipfrac, den), (1,) "
+          "each; the first three are differentiable wrt logit_new and value_new; raw leaves the six as numerators over den "
+          "for a sharded caller; scale = 1/(global B) for a sharded caller in sequence mode");
     m.def("q_nstep_td", [](const Tensor& q, const Tensor& nq, const Tensor& action, const Tensor& naction,
                            const Tensor& reward, const Tensor& done, const OptTensor& weight, double gamma, bool rescale,
                            std::optional<double> scale) {

@@ -34,8 +34,9 @@ Conventions:
 * ``B``, ``S`` or ``V`` of size 0 gives a zero loss and launches nothing;
 * contiguous GPU tensors.
 
-Out of scope: fusing the LM head's matrix product, in-place gradients, the entropy over the vocabulary, float16, and
-vocabularies split over ranks (tensor parallelism)."""
+Out of scope: fusing the LM head's matrix product, in-place gradients, float16, and vocabularies split over ranks (tensor
+parallelism).  The entropy over the vocabulary is not formed here: ``hpc_rll.rl_utils.lm_ppo.token_log_prob_entropy`` gives it
+with the log-probability from the same single read of the logits, and ``lm_ppo_loss`` is the token-level PPO loss on top."""
 from collections import namedtuple
 
 import torch

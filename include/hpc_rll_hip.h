@@ -571,6 +571,82 @@ int hpc_rll_grpo_backward(const float* g_loss, const void* logit_new, int elem, 
                           void* grad_logit, int B, int S, int V, void* stream);
 int hpc_rll_grpo_last_config(int* out);
 
+/* Token-level PPO for language models (no reference counterpart; the semantics are those of TRL's / OpenRLHF's PPO trainers):
+ * the head of hpc_rll_token_logp_forward with the entropy over the vocabulary, GAE on the (B,S) layout under a response mask,
+ * and the clipped token loss with value loss and entropy.  Logits, element types, the limit 1 <= V <= 262144, dropped rows
+ * (action outside [0,V) or weight 0: not read, every output 0, gradient row exact zeros) and the -inf / NaN clamp are those of
+ * the GRPO entry points above.
+ * hpc_rll_lm_head_forward -- one launch, one read of every live row.  Every lane keeps an online triple (m, s = sum e^(x-m),
+ *   u = sum e^(x-m) (x-m)); lse = m + ln s, logp = x[a] - lse, entropy H = ln s - u/s.  An entry of probability 0 adds exactly 0
+ *   to u.  logp, lse, entropy (rows), all required; weight (rows; may be NULL) only selects the rows to drop.
+ * hpc_rll_lm_head_backward -- one streaming launch:
+ *     grad_logits[r,v] = g_logp[r] ([v = a] - p_v) - g_entropy[r] p_v (x_v - lse[r] + H[r]),   p_v = exp(x_v - lse[r])
+ *   in the logits' element type (bf16: round to nearest even), nontemporal stores.  g_logp, g_entropy (rows) may each be NULL
+ *   (= zeros).  A row whose two coefficients are exactly 0 is zero-filled without reading its logits (decided on the device).
+ * hpc_rll_lm_gae -- value, weight (NULL = ones), kl (NULL = none), adv, ret (B,S); reward (B,S), or (B) with
+ *   reward_per_sequence != 0: a terminal score credited to the last live token of the sequence.  A token is live iff w != 0; the
+ *   live tokens j_1 < ... < j_L of a sequence are its trajectory, dropped ones are skipped (they may hold NaN; adv = ret = 0):
+ *     r_i = reward_i - beta kl_i,  delta_i = r_i + gamma V_(i+1) - V_i,  A_i = delta_i + gamma lam A_(i+1),  V_(L+1) = A_(L+1) = 0,
+ *     ret_i = A_i + V_i;   whiten != 0: adv = (A - mu) / sqrt(var + 1e-8), mu and the biased var over the n live tokens of the
+ *   batch (Chan's merge of centred sums in a fixed order; n = 0 gives zeros, n = 1 gives adv = 0), else adv = A.
+ *   One launch (a wave per sequence, 64 tokens per step), plus one for the whitening, whatever B and S are; no atomics, no host
+ *   synchronisation, the same bits on every run.  ws: hpc_rll_lm_gae_workspace_floats() floats; (n, mean, M2) per workgroup of
+ *   the first launch are written, nothing else.  B == 0 or S == 0 launches nothing.
+ * hpc_rll_lm_ppo_forward -- logit_new (B,S,V) of elem; old_logp, adv, weight (NULL = ones) (B,S) fp32; action (B,S) int64;
+ *   value_new, value_old, ret (B,S): all three or all NULL.  Per live token, with pn and H from the head:
+ *     r = exp(pn - po), rc = clamp(r, 1 - clip, 1 + clip), l = max(-A r, -A rc); dual_clip = c > 1 and A < 0: l = min(l, -c A);
+ *     dl/dpn = -A r where the unclipped term is the maximum (a tie counts as unclipped) and the dual clip is not active, else 0;
+ *     lv = max((v - ret)^2, (vc - ret)^2) / 2, vc = v_old + clamp(v - v_old, -value_clip, value_clip)  (use_value_clip == 0:
+ *     lv = (v - ret)^2 / 2);  the clipped branch has no gradient.
+ *   Aggregation of a per-token x: seq_mean == 0 ('token'): sum w x / sum w over the batch; seq_mean != 0 ('sequence'):
+ *     scale sum_b (sum_s w x / sum_s w), scale <= 0: 1/B, a sequence without weight contributes 0.  sum w == 0 gives zeros.
+ *   out8 = policy_loss, value_loss, entropy, approx_kl ((r - 1) - log r), mean_ratio, clipfrac ([r outside 1 +- clip]),
+ *     den (sum w in 'token' mode, 1 in 'sequence' mode), 0.  raw != 0: the six are left as numerators (not divided by den): a
+ *     sharded caller sums numerators and den over the ranks and divides then.
+ *   Three launches: the head, the token launch (a wave per sequence, fixed-order sums), a one-workgroup launch for out8.
+ *   ws: hpc_rll_lm_ppo_workspace_floats(B,S) floats, with R = B*S the layout is
+ *   lse (R) | entropy (R) | cp (R) | ce (R) | cv (R) | logp (R) | the seven sums (8; 7 written) | partial sums (7 per workgroup);
+ *   cp, ce, cv are the unit gradients of the three numerators towards logp, entropy and value_new (cv is written only with value
+ *   operands).  B == 0, S == 0 or V == 0 zeroes out8 and launches nothing.
+ * hpc_rll_lm_ppo_backward -- g_policy, g_entropy, g_value: device scalars, the upstream gradients of the three outputs; NULL
+ *   means the output was not differentiated (gradient 0).  use_den != 0 ('token' mode, raw == 0): they are divided by the
+ *   sum w the forward left in ws, read on the device.  grad_logit (may be NULL): one streaming launch of the head's gradient
+ *   kernel with the per-row coefficients g_policy cp / den and g_entropy ce / den; weight as given to the forward.
+ *   grad_value (B,S) (may be NULL) = g_value cv / den, one small launch.
+ * hpc_rll_lm_ppo_last_config -- out[HPC_RLL_LM_PPO_CONFIG_INTS] = {
+ *    [0..6]   the head launch last issued: launches so far, element type, bytes per load of the row's body (16), peeled (1:
+ *             the elements outside the row's 16-byte grid are loaded one by one; 0: base and pitch are on 16 bytes),
+ *             threads per row (64: a wave per row; 256: a workgroup per row), rows per workgroup, workgroups,
+ *    [7..11]  the GAE launch: launches so far, threads per sequence (64), sequences per workgroup (4), tokens per step (64),
+ *             workgroups,
+ *    [12..14] the whitening launch: launches so far, threads per workgroup, workgroups,
+ *    [15..17] the token launch: launches so far, threads per workgroup, workgroups,
+ *    [18..23] the gradient launch: launches so far, element type, bytes per load and store (16, or the element's size when
+ *             a base or the pitch is off 16 bytes), threads per row, rows per workgroup, workgroups };
+ *   each of the five parts is {0, -1 ...} before its first launch; HPC_RLL_EINVAL for out == NULL.
+ * Argument errors, before any HIP call: HPC_RLL_EINVAL (null operands, value operands given in part, then negative sizes or an
+ * unknown element type), HPC_RLL_EALIGN (a float array off 4-byte alignment, action off 8, logits off their element size),
+ * then HPC_RLL_EUNSUPPORTED (V > 262144); then empty shapes return 0. */
+#define HPC_RLL_LM_PPO_CONFIG_INTS (24)
+int hpc_rll_lm_head_forward(const void* logits, int elem, const int64_t* action, const float* weight, float* logp, float* lse,
+                            float* entropy, int64_t rows, int V, void* stream);
+int hpc_rll_lm_head_backward(const float* g_logp, const float* g_entropy, const void* logits, int elem, const int64_t* action,
+                             const float* weight, const float* lse, const float* entropy, void* grad_logits, int64_t rows,
+                             int V, void* stream);
+int64_t hpc_rll_lm_gae_workspace_floats(void);
+int hpc_rll_lm_gae(const float* value, const float* weight, const float* reward, int reward_per_sequence, const float* kl,
+                   float* adv, float* ret, float* ws, int B, int S, float beta, float gamma, float lam, int whiten,
+                   void* stream);
+int64_t hpc_rll_lm_ppo_workspace_floats(int B, int S);
+int hpc_rll_lm_ppo_forward(const void* logit_new, int elem, const float* old_logp, const int64_t* action, const float* adv,
+                           const float* weight, const float* value_new, const float* value_old, const float* ret, float* out8,
+                           float* ws, int B, int S, int V, float clip_ratio, float dual_clip, int use_value_clip,
+                           float value_clip, int seq_mean, int raw, float scale, void* stream);
+int hpc_rll_lm_ppo_backward(const float* g_policy, const float* g_entropy, const float* g_value, const void* logit_new,
+                            int elem, const int64_t* action, const float* weight, const float* ws, void* grad_logit,
+                            float* grad_value, int B, int S, int V, int use_den, void* stream);
+int hpc_rll_lm_ppo_last_config(int* out);
+
 /* PPO -- replaces PPOForward/Backward (rl_utils/entry.h:158-165, src/rl_utils/ppo.cu:8-111).
  * logits (B,N), action (B,), value_new/old, adv, ret, weight (B,) (weight NULL = ones).
  * out5 = policy_loss, value_loss, entropy_loss, approx_kl, clipfrac.  dual_clip < 1 disables dual clip
