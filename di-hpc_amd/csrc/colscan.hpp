@@ -157,6 +157,24 @@ __device__ __forceinline__ void publish_block_sums(const float (&acc)[NACC], flo
     publish_sums<NACC, NT>(sum, partials, fold);
 }
 
+// The same epilogue of a 256-thread workgroup whose sums are already WAVE-UNIFORM (a wave per sequence: every lane of a wave
+// holds the wave's acc): no butterfly, lane 0 of each wave stores, one barrier, (r0 + r1) + (r2 + r3), then publish_sums.
+template <int NACC>
+__device__ __forceinline__ void publish_wave_sums(const float (&acc)[NACC], float* __restrict__ partials, const ScanFold& fold) {
+    __shared__ float red[4][NACC];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0)
+#pragma unroll
+        for (int k = 0; k < NACC; ++k) red[wv][k] = acc[k];
+    __syncthreads();
+    float sum = 0.f;
+    if (threadIdx.x < NACC) {
+        const int k = threadIdx.x;
+        sum = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+    }
+    publish_sums<NACC, 256>(sum, partials, fold);
+}
+
 template <class Op, int V, int LC, int NW, int SUB = 1>
 __global__ __launch_bounds__(NW * 64) void colscan_rev_kernel(const Op op, int T, int B,
                                                               float* __restrict__ partials, const ScanFold fold) {

@@ -12,19 +12,16 @@
 //   dl/dpn = -adv_b r [not (rc adv_b < r adv_b)] - beta (exp(d) - 1)
 //   grad[b,s,v] = g w scale / (sum_s w) dl/dpn ([v = a] - exp(x_v - lse))
 //
-// Three kernels:
-//   * token_logp_kernel<Elem, ALIGNED, NT>: ONE read of the row.  Every lane keeps an online (max, sum exp) pair over the
-//     16-byte vectors it visits, kInFlight loads in flight, the running sum rescaled once per batch of loads; the pairs of a
-//     wave meet in a butterfly, the four waves of a workgroup through 8 LDS words.  NT = 256: a workgroup per row (V above
-//     kWaveRowMaxV); NT = 64: a wave per row, four rows per workgroup.  ALIGNED = false peels the elements in front of the
-//     first and behind the last 16-byte boundary of the row (at most 2 (P - 1), one lane each), so no wide load is
-//     misaligned or leaves the row.  A dropped row (action outside [0,V), or weight 0) is not read: logp = lse = 0.
-//   * grpo_token_kernel: a wave per sequence walks s twice (the weight sum, then everything); wave butterflies in a fixed
-//     order, the batch sums leave through publish_sums (colscan.hpp).  No float atomics.
-//   * token_grad_kernel<Elem, WIDE, NT>: reads the row once, writes c ([v = a] - exp(x - lse)) with nontemporal stores in the
-//     logits' dtype (bf16: round to nearest even).  A row whose coefficient is exactly 0 is zero-filled WITHOUT reading its
-//     logits; the decision is the device's.  WIDE needs both bases and the row pitch on 16 bytes; otherwise one element per
-//     access (input and output rows do not share an alignment, so peeling cannot serve both).
+// Three kernels; what they have in common with lm_ppo.hip's (the statistic and the row walk of the head, the head kernel and
+// its launcher, the row loops of the gradient, the first pass of the token loss, the dispatch) is in lm_head.hpp:
+//   * lm_head_kernel<Elem, ALIGNED, NT, false> (lm_head.hpp): ONE read of the row, an online (max, sum exp) pair per lane and
+//     no entropy moment.  NT = 256: a workgroup per row (V above kWaveRowMaxV); NT = 64: a wave per row, four rows per
+//     workgroup.  A dropped row (action outside [0,V), or weight 0) is not read: logp = lse = 0.
+//   * grpo_token_kernel: a wave per sequence walks s twice (seq_weight_sum, then everything); wave butterflies in a fixed
+//     order, the batch sums leave through publish_wave_sums (colscan.hpp).  No float atomics.
+//   * token_grad_kernel<Elem, WIDE, NT>: reads the row once, writes c ([v = a] - exp(x - lse)) through stream_row.  A row
+//     whose coefficient is exactly 0 is zero-filled WITHOUT reading its logits (zero_row); the decision is the device's.  A
+//     row is live on `action` alone: a zero weight arrives as coef == 0.
 // -inf logits are clamped to the most negative finite float on load (probability exactly 0), as categorical.hip does; the same
 // clamp turns a NaN logit of a LIVE row into an entry of probability 0: NaN there is not propagated to the loss or the gradient.
 #include <hip/hip_runtime.h>
@@ -40,178 +37,16 @@ namespace {
 
 constexpr int kGrpoSums = 5;         // loss, sum w kl, sum w r, sum w clipped, sum w
 
-// ---- online softmax statistics: s = sum exp(x - m) over what has been seen, m its maximum (never below -FLT_MAX)
-struct MS { float m, s; };
-__device__ __forceinline__ MS ms_merge(const MS& a, const MS& b) {
-    MS r;
-    r.m = fmaxf(a.m, b.m);
-    r.s = a.s * ex2((a.m - r.m) * kLog2eG) + b.s * ex2((b.m - r.m) * kLog2eG);
-    return r;
-}
-__device__ __forceinline__ MS ms_wave(MS a) {   // all 64 lanes end with the wave's pair
-#pragma unroll
-    for (int k = 32; k >= 1; k >>= 1) {
-        MS o;
-        o.m = __shfl_xor(a.m, k, 64);
-        o.s = __shfl_xor(a.s, k, 64);
-        a = ms_merge(a, o);
-    }
-    return a;
-}
-
-// One batch of kInFlight vectors: a single rescale of the running sum.  GUARD: vector k counts only when ok[k].
-template <class Elem, bool GUARD>
-__device__ __forceinline__ void ms_batch(MS& a, const vuint4 (&r)[kInFlight], const bool (&ok)[kInFlight]) {
-    constexpr int P = ElemIO<Elem>::P;
-    float x[kInFlight * P];
-    float bm = -kFltMaxG;
-#pragma unroll
-    for (int k = 0; k < kInFlight; ++k) {
-        ElemIO<Elem>::unpack(r[k], x + k * P);
-#pragma unroll
-        for (int j = 0; j < P; ++j) {
-            float v = clampf(x[k * P + j]);
-            if (GUARD) v = ok[k] ? v : -kFltMaxG;
-            x[k * P + j] = v;
-            bm = fmaxf(bm, v);
-        }
-    }
-    const float m2 = fmaxf(a.m, bm);
-    float s = a.s * ex2((a.m - m2) * kLog2eG);
-#pragma unroll
-    for (int i = 0; i < kInFlight * P; ++i) s += ex2((x[i] - m2) * kLog2eG);
-    a.m = m2;
-    a.s = s;
-}
-
-// The pair of lane `tid` of the NT that share the row p[0, V).
-template <class Elem, bool ALIGNED, int NT>
-__device__ __forceinline__ MS row_stats(const Elem* __restrict__ p, int V, int tid) {
-    using IO = ElemIO<Elem>;
-    constexpr int P = IO::P;
-    int h = 0;
-    if (!ALIGNED) {
-        h = (int)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u) / sizeof(Elem));
-        h = h < V ? h : V;
-    }
-    const int nvec = (V - h) / P;
-    MS a{-kFltMaxG, 0.f};
-    if (!ALIGNED) {   // the elements outside the 16-byte grid of the row: fewer than 2 P, one lane each
-        const int tail = V - h - nvec * P;
-        if (tid < h + tail) {
-            const int i = tid < h ? tid : h + nvec * P + (tid - h);
-            a.m = clampf(IO::get(p + i));
-            a.s = 1.f;
-        }
-    }
-    const vuint4* __restrict__ pv = reinterpret_cast<const vuint4*>(p + h);
-    const bool all[kInFlight] = {true, true, true, true};
-    int v = tid;
-    for (; v + (kInFlight - 1) * NT < nvec; v += kInFlight * NT) {
-        vuint4 r[kInFlight];
-#pragma unroll
-        for (int k = 0; k < kInFlight; ++k) r[k] = __builtin_nontemporal_load(pv + v + k * NT);
-        ms_batch<Elem, false>(a, r, all);
-    }
-    if (v < nvec) {
-        vuint4 r[kInFlight];
-        bool ok[kInFlight];
-#pragma unroll
-        for (int k = 0; k < kInFlight; ++k) {
-            ok[k] = v + k * NT < nvec;
-            const vuint4 z = {0u, 0u, 0u, 0u};
-            r[k] = z;
-            if (ok[k]) r[k] = __builtin_nontemporal_load(pv + v + k * NT);
-        }
-        ms_batch<Elem, true>(a, r, ok);
-    }
-    return a;
-}
-
-// ================================================================================================
-// the head: logp[row] = x[a] - lse, lse[row] (lse may be NULL)
-// ================================================================================================
-template <class Elem, bool ALIGNED, int NT>
-__global__ __launch_bounds__(256) void token_logp_kernel(const Elem* __restrict__ x, const int64_t* __restrict__ action,
-                                                         const float* __restrict__ weight, float* __restrict__ logp,
-                                                         float* __restrict__ lse, long rows, int V) {
-    constexpr int RPW = 256 / NT;
-    __shared__ float red[2][4][2];
-    const int tid = threadIdx.x % NT, sub = threadIdx.x / NT;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int par = 0;
-    for (long r0 = (long)blockIdx.x * RPW; r0 < rows; r0 += (long)gridDim.x * RPW) {
-        const long row = r0 + sub;
-        const bool have = row < rows;
-        long a = -1;
-        float w = 1.f;
-        if (have) {
-            a = action[row];
-            if (weight) w = weight[row];
-        }
-        const bool live = have && a >= 0 && a < (long)V && w != 0.f;   // the same for all NT threads of the row
-        MS st{-kFltMaxG, 0.f};
-        float xa = 0.f;
-        if (live) {
-            const Elem* p = x + (size_t)row * (size_t)V;
-            if (tid == 0) xa = clampf(ElemIO<Elem>::get(p + a));
-            st = ms_wave(row_stats<Elem, ALIGNED, NT>(p, V, tid));
-            if (NT == 256) {   // a workgroup per row: `live` is uniform over it
-                if (lane == 0) {
-                    red[par][wv][0] = st.m;
-                    red[par][wv][1] = st.s;
-                }
-                __syncthreads();
-                if (threadIdx.x == 0) {
-                    MS w0{red[par][0][0], red[par][0][1]}, w1{red[par][1][0], red[par][1][1]};
-                    MS w2{red[par][2][0], red[par][2][1]}, w3{red[par][3][0], red[par][3][1]};
-                    st = ms_merge(ms_merge(w0, w1), ms_merge(w2, w3));
-                }
-                par ^= 1;   // the next row writes the other half: one barrier per row
-            }
-        }
-        if (tid == 0 && have) {
-            float l = 0.f, lp = 0.f;
-            if (live) {
-                l = st.m + __builtin_amdgcn_logf(st.s) * kLn2G;   // s is in [1, V]: the bare log2
-                lp = xa - l;
-            }
-            logp[row] = lp;
-            if (lse) lse[row] = l;
-        }
-    }
-}
-
 // The dispatch records (hpc_rll_grpo_last_config)
 constexpr int kHeadInts = 7, kTokenInts = 3, kGradInts = 6;
 LaunchRecord<kHeadInts> g_grpo_head;
 LaunchRecord<kTokenInts> g_grpo_token;
 LaunchRecord<kGradInts> g_grpo_grad;
 
-template <class Elem>
-int token_logp_launch(const void* xv, const int64_t* action, const float* weight, float* logp, float* lse, long rows, int V,
-                      hipStream_t st) {
-    const Elem* x = static_cast<const Elem*>(xv);
-    const bool al = aligned(x, 16) && ((size_t)V * sizeof(Elem)) % 16 == 0;
-    const bool wide_row = V > kWaveRowMaxV;
-    const int rpw = wide_row ? 1 : 4;
-    const long grid = row_grid_of(rows, rpw);
-#define HPC_RLL_GRPO_HEAD(AL_, NT_)                                                                                  \
-    hipLaunchKernelGGL((token_logp_kernel<Elem, AL_, NT_>), dim3((unsigned)grid), dim3(256), 0, st, x, action, weight, \
-                       logp, lse, rows, V)
-    if (al && wide_row) HPC_RLL_GRPO_HEAD(true, 256);
-    else if (al) HPC_RLL_GRPO_HEAD(true, 64);
-    else if (wide_row) HPC_RLL_GRPO_HEAD(false, 256);
-    else HPC_RLL_GRPO_HEAD(false, 64);
-#undef HPC_RLL_GRPO_HEAD
-    const int rc = last_error();
-    if (!rc) g_grpo_head.note({ElemIO<Elem>::kCode, 16, al ? 0 : 1, wide_row ? 256 : 64, rpw, (int)grid});
-    return rc;
-}
+// the head without the entropy: logp[row] = x[a] - lse, lse[row] (lse may be NULL)
 int token_logp_any(const void* x, int elem, const int64_t* action, const float* weight, float* logp, float* lse, long rows,
                    int V, hipStream_t st) {
-    return elem == 1 ? token_logp_launch<uint16_t>(x, action, weight, logp, lse, rows, V, st)
-                     : token_logp_launch<float>(x, action, weight, logp, lse, rows, V, st);
+    return lm_head_launch<false>(x, elem, action, weight, logp, lse, nullptr, rows, V, st, g_grpo_head);
 }
 
 // ================================================================================================
@@ -224,19 +59,12 @@ struct GrpoTokenArgs {
 
 __global__ __launch_bounds__(256) void grpo_token_kernel(const GrpoTokenArgs p, float* __restrict__ partials,
                                                          const ScanFold fold) {
-    __shared__ float red[4][kGrpoSums];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const float lo = 1.f - p.clip, hi = 1.f + p.clip;
     float acc[kGrpoSums] = {0.f, 0.f, 0.f, 0.f, 0.f};
     for (long b = (long)blockIdx.x * 4 + wv; b < (long)p.B; b += (long)gridDim.x * 4) {
         const size_t base = (size_t)b * (size_t)p.S;
-        float sw = 0.f;
-        for (int s = lane; s < p.S; s += 64) {
-            const long a = p.action[base + s];
-            const float w = p.weight ? p.weight[base + s] : 1.f;
-            sw += (a >= 0 && a < (long)p.V && w != 0.f) ? w : 0.f;
-        }
-        sw = wave_sum(sw);
+        const float sw = seq_weight_sum(p.action, p.weight, base, p.S, p.V, lane);
         const float adv = p.adv[b];
         const float inv = sw != 0.f ? 1.f / sw : 0.f;   // a sequence without weight contributes 0 and still counts in B
         const float cs = p.scale * inv;
@@ -277,16 +105,7 @@ __global__ __launch_bounds__(256) void grpo_token_kernel(const GrpoTokenArgs p, 
         acc[3] += sc;
         acc[4] += sw;
     }
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < kGrpoSums; ++k) red[wv][k] = acc[k];
-    __syncthreads();
-    float sum = 0.f;
-    if (threadIdx.x < kGrpoSums) {
-        const int k = threadIdx.x;
-        sum = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
-    }
-    publish_sums<kGrpoSums, 256>(sum, partials, fold);
+    publish_wave_sums<kGrpoSums>(acc, partials, fold);
 }
 
 // sums = scale * loss sum, sum w kl, sum w r, sum w clipped, sum w  ->  out4 = loss, mean_kl, mean_ratio, mean_clipped
@@ -305,8 +124,6 @@ __global__ __launch_bounds__(256) void token_grad_kernel(const Elem* __restrict_
                                                          const float* __restrict__ lse, const float* __restrict__ coef,
                                                          const float* __restrict__ g, Elem* __restrict__ grad, long rows,
                                                          int V) {
-    using IO = ElemIO<Elem>;
-    constexpr int P = IO::P;
     constexpr int RPW = 256 / NT;
     const int tid = threadIdx.x % NT, sub = threadIdx.x / NT;
     const float u = g ? g[0] : 1.f;
@@ -319,83 +136,33 @@ __global__ __launch_bounds__(256) void token_grad_kernel(const Elem* __restrict_
         const int ai = inr ? (int)a : -1;
         const Elem* p = x + (size_t)row * (size_t)V;
         Elem* o = grad + (size_t)row * (size_t)V;
-        if (c == 0.f) {   // nothing of the row is read
-            if (WIDE) {
-                const vuint4 z = {0u, 0u, 0u, 0u};
-                vuint4* ov = reinterpret_cast<vuint4*>(o);
-                for (int v = tid; v < V / P; v += NT) __builtin_nontemporal_store(z, ov + v);
-            } else {
-                for (int i = tid; i < V; i += NT) IO::put(o + i, 0.f);
-            }
+        if (c == 0.f) {
+            zero_row<Elem, WIDE, NT>(o, V, tid);
             continue;
         }
         const float l = lse[row];
-        if (WIDE) {
-            const int nvec = V / P;
-            const vuint4* __restrict__ pv = reinterpret_cast<const vuint4*>(p);
-            vuint4* ov = reinterpret_cast<vuint4*>(o);
-            for (int v = tid; v < nvec; v += kInFlight * NT) {
-                vuint4 r[kInFlight];
-#pragma unroll
-                for (int k = 0; k < kInFlight; ++k)
-                    if (v + k * NT < nvec) r[k] = __builtin_nontemporal_load(pv + v + k * NT);
-#pragma unroll
-                for (int k = 0; k < kInFlight; ++k)
-                    if (v + k * NT < nvec) {
-                        float xx[P];
-                        IO::unpack(r[k], xx);
-                        const int da = ai - (v + k * NT) * P;
-#pragma unroll
-                        for (int j = 0; j < P; ++j) {
-                            const float e = ex2((clampf(xx[j]) - l) * kLog2eG);
-                            xx[j] = fmaf(-c, e, da == j ? c : 0.f);
-                        }
-                        __builtin_nontemporal_store(IO::pack(xx), ov + v + k * NT);
-                    }
-            }
-        } else {
-            for (int i = tid; i < V; i += kInFlight * NT) {
-                float xx[kInFlight];
-#pragma unroll
-                for (int k = 0; k < kInFlight; ++k)
-                    if (i + k * NT < V) xx[k] = IO::get(p + i + k * NT);
-#pragma unroll
-                for (int k = 0; k < kInFlight; ++k)
-                    if (i + k * NT < V) {
-                        const float e = ex2((clampf(xx[k]) - l) * kLog2eG);
-                        IO::put(o + i + k * NT, fmaf(-c, e, ai == i + k * NT ? c : 0.f));
-                    }
-            }
-        }
+        stream_row<Elem, WIDE, NT>(p, o, V, tid, ai, [&](float xv, bool chosen) {
+            const float e = ex2((clampf(xv) - l) * kLog2eG);
+            return fmaf(-c, e, chosen ? c : 0.f);
+        });
     }
 }
 
-template <class Elem>
-int token_grad_launch(const void* xv, const int64_t* action, const float* lse, const float* coef, const float* g, void* gradv,
-                      long rows, int V, hipStream_t st) {
-    const Elem* x = static_cast<const Elem*>(xv);
-    Elem* grad = static_cast<Elem*>(gradv);
-    const bool wide = aligned(x, 16) && aligned(grad, 16) && ((size_t)V * sizeof(Elem)) % 16 == 0;
-    const bool wide_row = V > kWaveRowMaxV;
-    const int rpw = wide_row ? 1 : 4;
-    const long grid = row_grid_of(rows, rpw);
-#define HPC_RLL_GRPO_GRAD(W_, NT_)                                                                                    \
-    hipLaunchKernelGGL((token_grad_kernel<Elem, W_, NT_>), dim3((unsigned)grid), dim3(256), 0, st, x, action, lse, coef, g, \
-                       grad, rows, V)
-    if (wide && wide_row) HPC_RLL_GRPO_GRAD(true, 256);
-    else if (wide) HPC_RLL_GRPO_GRAD(true, 64);
-    else if (wide_row) HPC_RLL_GRPO_GRAD(false, 256);
-    else HPC_RLL_GRPO_GRAD(false, 64);
-#undef HPC_RLL_GRPO_GRAD
-    const int rc = last_error();
-    if (!rc)
-        g_grpo_grad.note({ElemIO<Elem>::kCode, wide ? 16 : (int)sizeof(Elem), wide_row ? 256 : 64, rpw, (int)grid});
-    return rc;
-}
-int token_grad_any(const void* x, int elem, const int64_t* action, const float* lse, const float* coef, const float* g,
-                   void* grad, long rows, int V, hipStream_t st) {
-    return elem == 1 ? token_grad_launch<uint16_t>(x, action, lse, coef, g, grad, rows, V, st)
-                     : token_grad_launch<float>(x, action, lse, coef, g, grad, rows, V, st);
+int token_grad_any(const void* xv, int elem, const int64_t* action, const float* lse, const float* coef, const float* g,
+                   void* gradv, long rows, int V, hipStream_t st) {
+    return with_elem(elem, [&](auto e) {
+        using Elem = decltype(e);
+        const Elem* x = static_cast<const Elem*>(xv);
+        Elem* grad = static_cast<Elem*>(gradv);
+        const RowLaunch L = row_launch<Elem>(x, grad, rows, V);
+        with_row_kernel(L, [&](auto W, auto NT) {
+            hipLaunchKernelGGL((token_grad_kernel<Elem, decltype(W)::value, decltype(NT)::value>), dim3((unsigned)L.grid),
+                               dim3(256), 0, st, x, action, lse, coef, g, grad, rows, V);
+        });
+        const int rc = last_error();
+        if (!rc) g_grpo_grad.note({ElemIO<Elem>::kCode, L.wide ? 16 : (int)sizeof(Elem), L.nt, L.rpw, (int)L.grid});
+        return rc;
+    });
 }
 
 }  // namespace
@@ -407,11 +174,9 @@ extern "C" int hpc_rll_token_logp_forward(const void* logits, int elem, const in
                                           float* logp, float* lse, int64_t rows, int V, void* stream) {
     const bool empty = rows == 0 || V == 0;
     if (!empty && (!logits || !action || !logp)) return HPC_RLL_EINVAL;
-    if (rows < 0 || V < 0 || !elem_ok(elem)) return HPC_RLL_EINVAL;
-    if (!aligned(logits, elem_size(elem)) || !aligned(action, 8) || !aligned(weight, 4) || !aligned(logp, 4) ||
-        !aligned(lse, 4))
-        return HPC_RLL_EALIGN;
-    if (V > kGrpoMaxV) return HPC_RLL_EUNSUPPORTED;
+    if (const int bad = lm_shape_status(rows, 1, V, elem, aligned(logits, elem_size(elem)) && aligned(action, 8) &&
+                                        aligned(weight, 4) && aligned(logp, 4) && aligned(lse, 4)))
+        return bad;
     if (empty) {   // V == 0 with rows: no token has a probability; zeros
         if (rows > 0 && logp) {
             int rc = (int)hipMemsetAsync(logp, 0, (size_t)rows * sizeof(float), (hipStream_t)stream);
@@ -427,11 +192,9 @@ extern "C" int hpc_rll_token_logp_backward(const float* g_logp, const void* logi
                                            const float* lse, void* grad_logits, int64_t rows, int V, void* stream) {
     const bool empty = rows == 0 || V == 0;
     if (!empty && (!g_logp || !logits || !action || !lse || !grad_logits)) return HPC_RLL_EINVAL;
-    if (rows < 0 || V < 0 || !elem_ok(elem)) return HPC_RLL_EINVAL;
-    if (!aligned(logits, elem_size(elem)) || !aligned(grad_logits, elem_size(elem)) || !aligned(action, 8) ||
-        !aligned(g_logp, 4) || !aligned(lse, 4))
-        return HPC_RLL_EALIGN;
-    if (V > kGrpoMaxV) return HPC_RLL_EUNSUPPORTED;
+    if (const int bad = lm_shape_status(rows, 1, V, elem, aligned(logits, elem_size(elem)) && aligned(grad_logits, elem_size(elem)) &&
+                                        aligned(action, 8) && aligned(g_logp, 4) && aligned(lse, 4)))
+        return bad;
     if (empty) return HPC_RLL_OK;
     return token_grad_any(logits, elem, action, lse, g_logp, nullptr, grad_logits, (long)rows, V, (hipStream_t)stream);
 }
@@ -450,11 +213,11 @@ extern "C" int hpc_rll_grpo_forward(const void* logit_new, int elem_new, const v
     auto kind_ok = [](int k) { return elem_ok(k) || k == HPC_RLL_GRPO_LOGP; };
     if (!out4) return HPC_RLL_EINVAL;
     if (!empty && (!logit_new || !old || !action || !adv || !ws)) return HPC_RLL_EINVAL;
-    if (B < 0 || S < 0 || V < 0 || !elem_ok(elem_new) || !kind_ok(old_kind) || (ref && !kind_ok(ref_kind))) return HPC_RLL_EINVAL;
-    if (!aligned(logit_new, elem_size(elem_new)) || !aligned(old, elem_size(old_kind)) || !aligned(ref, elem_size(ref_kind)) ||
-        !aligned(action, 8) || !aligned(adv, 4) || !aligned(weight, 4) || !aligned(out4, 4) || !aligned(ws, 4))
-        return HPC_RLL_EALIGN;
-    if (V > kGrpoMaxV) return HPC_RLL_EUNSUPPORTED;
+    if (!kind_ok(old_kind) || (ref && !kind_ok(ref_kind))) return HPC_RLL_EINVAL;
+    if (const int bad = lm_shape_status(B, S, V, elem_new, aligned(logit_new, elem_size(elem_new)) && aligned(old, elem_size(old_kind)) &&
+                                        aligned(ref, elem_size(ref_kind)) && aligned(action, 8) && aligned(adv, 4) &&
+                                        aligned(weight, 4) && aligned(out4, 4) && aligned(ws, 4)))
+        return bad;
     hipStream_t st = (hipStream_t)stream;
     if (empty) return (int)hipMemsetAsync(out4, 0, 4 * sizeof(float), st);
     const long R = (long)B * S;
@@ -499,11 +262,9 @@ extern "C" int hpc_rll_grpo_backward(const float* g_loss, const void* logit_new,
                                      const float* ws, void* grad_logit, int B, int S, int V, void* stream) {
     const bool empty = B == 0 || S == 0 || V == 0;
     if (!empty && (!logit_new || !action || !ws || !grad_logit)) return HPC_RLL_EINVAL;
-    if (B < 0 || S < 0 || V < 0 || !elem_ok(elem)) return HPC_RLL_EINVAL;
-    if (!aligned(logit_new, elem_size(elem)) || !aligned(grad_logit, elem_size(elem)) || !aligned(action, 8) ||
-        !aligned(g_loss, 4) || !aligned(ws, 4))
-        return HPC_RLL_EALIGN;
-    if (V > kGrpoMaxV) return HPC_RLL_EUNSUPPORTED;
+    if (const int bad = lm_shape_status(B, S, V, elem, aligned(logit_new, elem_size(elem)) && aligned(grad_logit, elem_size(elem)) &&
+                                        aligned(action, 8) && aligned(g_loss, 4) && aligned(ws, 4)))
+        return bad;
     if (empty) return HPC_RLL_OK;
     const long R = (long)B * S;
     return token_grad_any(logit_new, elem, action, ws, ws + R, g_loss, grad_logit, R, V, (hipStream_t)stream);

@@ -5,21 +5,22 @@
 // No reference counterpart; the semantics are those of TRL's / OpenRLHF's PPO trainers (see hpc_rll_hip.h for the formulas).
 //
 // Kernels:
-//   * lm_head_kernel<Elem, ALIGNED, NT>: the head of grpo.hip (one read of the row, kInFlight 16-byte loads in flight,
-//     a wave or a workgroup per row, peeled ends) with an online TRIPLE per lane
+//   * lm_head_kernel<Elem, ALIGNED, NT, true> (lm_head.hpp, the kernel grpo.hip instantiates without the entropy): one read
+//     of the row, kInFlight 16-byte loads in flight, a wave or a workgroup per row, peeled ends, an online TRIPLE per lane
 //         m = max x,   s = sum e^(x-m),   u = sum e^(x-m) (x-m)
-//     so that lse = m + ln s, logp = x[a] - lse, H = ln s - u/s.  An entry whose exponential is 0 (a clamped -inf or NaN,
-//     or anything 88 below the maximum) adds exactly 0 to u BY SELECTION: 0 * (-huge) is never formed.
+//     so that lse = m + ln s, logp = x[a] - lse, H = ln s - u/s.
 //   * lm_gae_kernel: a wave per sequence walks S from the back, 64 tokens (one per lane, coalesced) per step.  A live token
 //     maps the carry (A, Vn) to (gl A + g Vn + (r - V), V), a dropped one is the identity; these maps are closed under
 //     composition as A' = a A + b Vn + c, Vn' = d Vn + e, and a step is a 6-stage suffix scan of the five coefficients.
 //     The whitening statistics (n, mean, M2) are formed from centred values per step and merged with Chan's update in a
 //     fixed order: step -> wave -> workgroup -> one triple per workgroup in the workspace.
 //   * lm_whiten_kernel: every workgroup merges the workgroup triples in the same fixed order, then adv = (A - mu) rsqrt(var + eps).
-//   * lm_ppo_token_kernel: a wave per sequence (as grpo_token_kernel); seven sums leave through publish_sums.
+//   * lm_ppo_token_kernel: a wave per sequence (as grpo_token_kernel: seq_weight_sum, then everything); seven sums leave
+//     through publish_wave_sums (colscan.hpp).
 //   * lm_ppo_final_kernel: the six aggregates from the sums.
 //   * lm_grad_kernel<Elem, WIDE, NT>: grad[r,v] = c1 ([v = a] - p_v) - c2 p_v (x_v - lse + H), nontemporal stores in the
-//     logits' dtype; a row with c1 == c2 == 0 is zero-filled without reading its logits (decided on the device).
+//     logits' dtype through stream_row (lm_head.hpp); a row with c1 == c2 == 0 is zero-filled without reading its logits
+//     (zero_row; decided on the device).  Unlike grpo.hip's gradient, liveness here reads `weight` too.
 //   * lm_value_grad_kernel: grad_value = g cv / den, (B,S).
 // No float atomics; every sum has a fixed order, so two runs give the same bits.
 #include <hip/hip_runtime.h>
@@ -37,171 +38,6 @@ constexpr int kLmSums = 7;        // policy, value, entropy, approx_kl, ratio, c
 constexpr int kGaeChunk = 64;     // tokens per step of a wave
 constexpr float kWhitenEps = 1e-8f;
 
-// ---- online softmax statistics with the entropy moment
-struct MSU { float m, s, u; };
-// e^(d) (d <= 0) and the moment (u + d s) e^(d) of a triple moved from its maximum to one that is -d higher
-__device__ __forceinline__ void msu_shift(const MSU& a, float m, float& s, float& u) {
-    const float d = a.m - m;
-    const float e = ex2(d * kLog2eG);
-    s = a.s * e;
-    u = e == 0.f ? 0.f : (a.u + d * a.s) * e;
-}
-__device__ __forceinline__ MSU msu_merge(const MSU& a, const MSU& b) {
-    MSU r;
-    r.m = fmaxf(a.m, b.m);
-    float sa, ua, sb, ub;
-    msu_shift(a, r.m, sa, ua);
-    msu_shift(b, r.m, sb, ub);
-    r.s = sa + sb;
-    r.u = ua + ub;
-    return r;
-}
-__device__ __forceinline__ MSU msu_wave(MSU a) {   // all 64 lanes end with the wave's triple
-#pragma unroll
-    for (int k = 32; k >= 1; k >>= 1) {
-        MSU o;
-        o.m = __shfl_xor(a.m, k, 64);
-        o.s = __shfl_xor(a.s, k, 64);
-        o.u = __shfl_xor(a.u, k, 64);
-        a = msu_merge(a, o);
-    }
-    return a;
-}
-
-// One batch of kInFlight vectors: a single rescale of the running sums.  GUARD: vector k counts only when ok[k].
-template <class Elem, bool GUARD>
-__device__ __forceinline__ void msu_batch(MSU& a, const vuint4 (&r)[kInFlight], const bool (&ok)[kInFlight]) {
-    constexpr int P = ElemIO<Elem>::P;
-    float x[kInFlight * P];
-    float bm = -kFltMaxG;
-#pragma unroll
-    for (int k = 0; k < kInFlight; ++k) {
-        ElemIO<Elem>::unpack(r[k], x + k * P);
-#pragma unroll
-        for (int j = 0; j < P; ++j) {
-            float v = clampf(x[k * P + j]);
-            if (GUARD) v = ok[k] ? v : -kFltMaxG;
-            x[k * P + j] = v;
-            bm = fmaxf(bm, v);
-        }
-    }
-    const float m2 = fmaxf(a.m, bm);
-    float s, u;
-    msu_shift(a, m2, s, u);
-#pragma unroll
-    for (int i = 0; i < kInFlight * P; ++i) {
-        const float t = x[i] - m2;
-        const float e = ex2(t * kLog2eG);
-        s += e;
-        u = fmaf(e, e == 0.f ? 0.f : t, u);   // a zero exponential selects t away: 0 * 0, exactly nothing
-    }
-    a.m = m2;
-    a.s = s;
-    a.u = u;
-}
-
-// The triple of lane `tid` of the NT that share the row p[0, V).
-template <class Elem, bool ALIGNED, int NT>
-__device__ __forceinline__ MSU row_stats3(const Elem* __restrict__ p, int V, int tid) {
-    using IO = ElemIO<Elem>;
-    constexpr int P = IO::P;
-    int h = 0;
-    if (!ALIGNED) {
-        h = (int)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u) / sizeof(Elem));
-        h = h < V ? h : V;
-    }
-    const int nvec = (V - h) / P;
-    MSU a{-kFltMaxG, 0.f, 0.f};
-    if (!ALIGNED) {   // the elements outside the 16-byte grid of the row: fewer than 2 P, one lane each
-        const int tail = V - h - nvec * P;
-        if (tid < h + tail) {
-            const int i = tid < h ? tid : h + nvec * P + (tid - h);
-            a.m = clampf(IO::get(p + i));
-            a.s = 1.f;
-        }
-    }
-    const vuint4* __restrict__ pv = reinterpret_cast<const vuint4*>(p + h);
-    const bool all[kInFlight] = {true, true, true, true};
-    int v = tid;
-    for (; v + (kInFlight - 1) * NT < nvec; v += kInFlight * NT) {
-        vuint4 r[kInFlight];
-#pragma unroll
-        for (int k = 0; k < kInFlight; ++k) r[k] = __builtin_nontemporal_load(pv + v + k * NT);
-        msu_batch<Elem, false>(a, r, all);
-    }
-    if (v < nvec) {
-        vuint4 r[kInFlight];
-        bool ok[kInFlight];
-#pragma unroll
-        for (int k = 0; k < kInFlight; ++k) {
-            ok[k] = v + k * NT < nvec;
-            const vuint4 z = {0u, 0u, 0u, 0u};
-            r[k] = z;
-            if (ok[k]) r[k] = __builtin_nontemporal_load(pv + v + k * NT);
-        }
-        msu_batch<Elem, true>(a, r, ok);
-    }
-    return a;
-}
-
-// ================================================================================================
-// the head: logp[row] = x[a] - lse, lse[row], ent[row] = ln s - u/s
-// ================================================================================================
-template <class Elem, bool ALIGNED, int NT>
-__global__ __launch_bounds__(256) void lm_head_kernel(const Elem* __restrict__ x, const int64_t* __restrict__ action,
-                                                      const float* __restrict__ weight, float* __restrict__ logp,
-                                                      float* __restrict__ lse, float* __restrict__ ent, long rows, int V) {
-    constexpr int RPW = 256 / NT;
-    __shared__ float red[2][4][3];
-    const int tid = threadIdx.x % NT, sub = threadIdx.x / NT;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int par = 0;
-    for (long r0 = (long)blockIdx.x * RPW; r0 < rows; r0 += (long)gridDim.x * RPW) {
-        const long row = r0 + sub;
-        const bool have = row < rows;
-        long a = -1;
-        float w = 1.f;
-        if (have) {
-            a = action[row];
-            if (weight) w = weight[row];
-        }
-        const bool live = have && a >= 0 && a < (long)V && w != 0.f;   // the same for all NT threads of the row
-        MSU st{-kFltMaxG, 0.f, 0.f};
-        float xa = 0.f;
-        if (live) {
-            const Elem* p = x + (size_t)row * (size_t)V;
-            if (tid == 0) xa = clampf(ElemIO<Elem>::get(p + a));
-            st = msu_wave(row_stats3<Elem, ALIGNED, NT>(p, V, tid));
-            if (NT == 256) {   // a workgroup per row: `live` is uniform over it
-                if (lane == 0) {
-                    red[par][wv][0] = st.m;
-                    red[par][wv][1] = st.s;
-                    red[par][wv][2] = st.u;
-                }
-                __syncthreads();
-                if (threadIdx.x == 0) {
-                    MSU w0{red[par][0][0], red[par][0][1], red[par][0][2]}, w1{red[par][1][0], red[par][1][1], red[par][1][2]};
-                    MSU w2{red[par][2][0], red[par][2][1], red[par][2][2]}, w3{red[par][3][0], red[par][3][1], red[par][3][2]};
-                    st = msu_merge(msu_merge(w0, w1), msu_merge(w2, w3));
-                }
-                par ^= 1;   // the next row writes the other half: one barrier per row
-            }
-        }
-        if (tid == 0 && have) {
-            float l = 0.f, lp = 0.f, h = 0.f;
-            if (live) {
-                const float ls = __builtin_amdgcn_logf(st.s) * kLn2G;   // s is in [1, V]: the bare log2
-                l = st.m + ls;
-                lp = xa - l;
-                h = ls - st.u / st.s;
-            }
-            logp[row] = lp;
-            lse[row] = l;
-            ent[row] = h;
-        }
-    }
-}
-
 // The dispatch records (hpc_rll_lm_ppo_last_config)
 constexpr int kHeadInts = 7, kGaeInts = 5, kWhitenInts = 3, kTokenInts = 3, kGradInts = 6;
 LaunchRecord<kHeadInts> g_lm_head;
@@ -210,30 +46,10 @@ LaunchRecord<kWhitenInts> g_lm_whiten;
 LaunchRecord<kTokenInts> g_lm_token;
 LaunchRecord<kGradInts> g_lm_grad;
 
-template <class Elem>
-int lm_head_launch(const void* xv, const int64_t* action, const float* weight, float* logp, float* lse, float* ent, long rows,
-                   int V, hipStream_t st) {
-    const Elem* x = static_cast<const Elem*>(xv);
-    const bool al = aligned(x, 16) && ((size_t)V * sizeof(Elem)) % 16 == 0;
-    const bool wide_row = V > kWaveRowMaxV;
-    const int rpw = wide_row ? 1 : 4;
-    const long grid = row_grid_of(rows, rpw);
-#define HPC_RLL_LM_HEAD(AL_, NT_)                                                                                  \
-    hipLaunchKernelGGL((lm_head_kernel<Elem, AL_, NT_>), dim3((unsigned)grid), dim3(256), 0, st, x, action, weight, \
-                       logp, lse, ent, rows, V)
-    if (al && wide_row) HPC_RLL_LM_HEAD(true, 256);
-    else if (al) HPC_RLL_LM_HEAD(true, 64);
-    else if (wide_row) HPC_RLL_LM_HEAD(false, 256);
-    else HPC_RLL_LM_HEAD(false, 64);
-#undef HPC_RLL_LM_HEAD
-    const int rc = last_error();
-    if (!rc) g_lm_head.note({ElemIO<Elem>::kCode, 16, al ? 0 : 1, wide_row ? 256 : 64, rpw, (int)grid});
-    return rc;
-}
+// the head with the entropy: logp[row] = x[a] - lse, lse[row], ent[row] = ln s - u/s
 int lm_head_any(const void* x, int elem, const int64_t* action, const float* weight, float* logp, float* lse, float* ent,
                 long rows, int V, hipStream_t st) {
-    return elem == 1 ? lm_head_launch<uint16_t>(x, action, weight, logp, lse, ent, rows, V, st)
-                     : lm_head_launch<float>(x, action, weight, logp, lse, ent, rows, V, st);
+    return lm_head_launch<true>(x, elem, action, weight, logp, lse, ent, rows, V, st, g_lm_head);
 }
 
 // ================================================================================================
@@ -247,8 +63,6 @@ struct LmGradArgs {
 template <class Elem, bool WIDE, int NT>
 __global__ __launch_bounds__(256) void lm_grad_kernel(const Elem* __restrict__ x, const LmGradArgs q, Elem* __restrict__ grad,
                                                       long rows, int V) {
-    using IO = ElemIO<Elem>;
-    constexpr int P = IO::P;
     constexpr int RPW = 256 / NT;
     const int tid = threadIdx.x % NT, sub = threadIdx.x / NT;
     float u1 = q.g1 ? q.g1[0] : q.gdef, u2 = q.g2 ? q.g2[0] : q.gdef;
@@ -269,79 +83,35 @@ __global__ __launch_bounds__(256) void lm_grad_kernel(const Elem* __restrict__ x
         const int ai = live ? (int)a : -1;
         const Elem* p = x + (size_t)row * (size_t)V;
         Elem* o = grad + (size_t)row * (size_t)V;
-        if (c1 == 0.f && c2 == 0.f) {   // nothing of the row is read
-            if (WIDE) {
-                const vuint4 z = {0u, 0u, 0u, 0u};
-                vuint4* ov = reinterpret_cast<vuint4*>(o);
-                for (int v = tid; v < V / P; v += NT) __builtin_nontemporal_store(z, ov + v);
-            } else {
-                for (int i = tid; i < V; i += NT) IO::put(o + i, 0.f);
-            }
+        if (c1 == 0.f && c2 == 0.f) {
+            zero_row<Elem, WIDE, NT>(o, V, tid);
             continue;
         }
         const float l = q.lse[row];
         const float c0 = fmaf(c2, q.ent[row], c1);   // grad = [v = a] c1 - (c0 + c2 t) e^t,  t = x - lse
-        auto elem_grad = [&](float xv, bool chosen) {
+        stream_row<Elem, WIDE, NT>(p, o, V, tid, ai, [&](float xv, bool chosen) {
             const float t = clampf(xv) - l;
             const float e = ex2(t * kLog2eG);
             const float pg = e == 0.f ? 0.f : fmaf(c2, t, c0) * e;   // a masked entry: exactly 0, never 0 * huge
             return (chosen ? c1 : 0.f) - pg;
-        };
-        if (WIDE) {
-            const int nvec = V / P;
-            const vuint4* __restrict__ pv = reinterpret_cast<const vuint4*>(p);
-            vuint4* ov = reinterpret_cast<vuint4*>(o);
-            for (int v = tid; v < nvec; v += kInFlight * NT) {
-                vuint4 r[kInFlight];
-#pragma unroll
-                for (int k = 0; k < kInFlight; ++k)
-                    if (v + k * NT < nvec) r[k] = __builtin_nontemporal_load(pv + v + k * NT);
-#pragma unroll
-                for (int k = 0; k < kInFlight; ++k)
-                    if (v + k * NT < nvec) {
-                        float xx[P];
-                        IO::unpack(r[k], xx);
-                        const int da = ai - (v + k * NT) * P;
-#pragma unroll
-                        for (int j = 0; j < P; ++j) xx[j] = elem_grad(xx[j], da == j);
-                        __builtin_nontemporal_store(IO::pack(xx), ov + v + k * NT);
-                    }
-            }
-        } else {
-            for (int i = tid; i < V; i += kInFlight * NT) {
-                float xx[kInFlight];
-#pragma unroll
-                for (int k = 0; k < kInFlight; ++k)
-                    if (i + k * NT < V) xx[k] = IO::get(p + i + k * NT);
-#pragma unroll
-                for (int k = 0; k < kInFlight; ++k)
-                    if (i + k * NT < V) IO::put(o + i + k * NT, elem_grad(xx[k], ai == i + k * NT));
-            }
-        }
+        });
     }
 }
 
-template <class Elem>
-int lm_grad_launch(const void* xv, const LmGradArgs& q, void* gradv, long rows, int V, hipStream_t st) {
-    const Elem* x = static_cast<const Elem*>(xv);
-    Elem* grad = static_cast<Elem*>(gradv);
-    const bool wide = aligned(x, 16) && aligned(grad, 16) && ((size_t)V * sizeof(Elem)) % 16 == 0;
-    const bool wide_row = V > kWaveRowMaxV;
-    const int rpw = wide_row ? 1 : 4;
-    const long grid = row_grid_of(rows, rpw);
-#define HPC_RLL_LM_GRAD(W_, NT_) \
-    hipLaunchKernelGGL((lm_grad_kernel<Elem, W_, NT_>), dim3((unsigned)grid), dim3(256), 0, st, x, q, grad, rows, V)
-    if (wide && wide_row) HPC_RLL_LM_GRAD(true, 256);
-    else if (wide) HPC_RLL_LM_GRAD(true, 64);
-    else if (wide_row) HPC_RLL_LM_GRAD(false, 256);
-    else HPC_RLL_LM_GRAD(false, 64);
-#undef HPC_RLL_LM_GRAD
-    const int rc = last_error();
-    if (!rc) g_lm_grad.note({ElemIO<Elem>::kCode, wide ? 16 : (int)sizeof(Elem), wide_row ? 256 : 64, rpw, (int)grid});
-    return rc;
-}
-int lm_grad_any(const void* x, int elem, const LmGradArgs& q, void* grad, long rows, int V, hipStream_t st) {
-    return elem == 1 ? lm_grad_launch<uint16_t>(x, q, grad, rows, V, st) : lm_grad_launch<float>(x, q, grad, rows, V, st);
+int lm_grad_any(const void* xv, int elem, const LmGradArgs& q, void* gradv, long rows, int V, hipStream_t st) {
+    return with_elem(elem, [&](auto e) {
+        using Elem = decltype(e);
+        const Elem* x = static_cast<const Elem*>(xv);
+        Elem* grad = static_cast<Elem*>(gradv);
+        const RowLaunch L = row_launch<Elem>(x, grad, rows, V);
+        with_row_kernel(L, [&](auto W, auto NT) {
+            hipLaunchKernelGGL((lm_grad_kernel<Elem, decltype(W)::value, decltype(NT)::value>), dim3((unsigned)L.grid), dim3(256),
+                               0, st, x, q, grad, rows, V);
+        });
+        const int rc = last_error();
+        if (!rc) g_lm_grad.note({ElemIO<Elem>::kCode, L.wide ? 16 : (int)sizeof(Elem), L.nt, L.rpw, (int)L.grid});
+        return rc;
+    });
 }
 
 // grad_value[i] = g cv[i] / den (g NULL: 0 everywhere)
@@ -505,7 +275,6 @@ struct LmTokenArgs {
 
 __global__ __launch_bounds__(256) void lm_ppo_token_kernel(const LmTokenArgs p, float* __restrict__ partials,
                                                            const ScanFold fold) {
-    __shared__ float red[4][kLmSums];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const float lo = 1.f - p.clip, hi = 1.f + p.clip;
     const bool dual_on = p.dual > 1.f;
@@ -514,13 +283,7 @@ __global__ __launch_bounds__(256) void lm_ppo_token_kernel(const LmTokenArgs p, 
     for (int k = 0; k < kLmSums; ++k) acc[k] = 0.f;
     for (long b = (long)blockIdx.x * 4 + wv; b < (long)p.B; b += (long)gridDim.x * 4) {
         const size_t base = (size_t)b * (size_t)p.S;
-        float sw = 0.f;
-        for (int s = lane; s < p.S; s += 64) {
-            const long a = p.action[base + s];
-            const float w = p.weight ? p.weight[base + s] : 1.f;
-            sw += (a >= 0 && a < (long)p.V && w != 0.f) ? w : 0.f;
-        }
-        sw = wave_sum(sw);
+        const float sw = seq_weight_sum(p.action, p.weight, base, p.S, p.V, lane);
         // 'sequence': every sum of the sequence is divided by its weight (a sequence without weight contributes 0 and still
         // counts in B) and `scale` = 1/B is applied with the batch sums; 'token': plain sums, divided by sum w at the end
         const float inv = p.seq_mean ? (sw != 0.f ? 1.f / sw : 0.f) : 1.f;
@@ -578,16 +341,7 @@ __global__ __launch_bounds__(256) void lm_ppo_token_kernel(const LmTokenArgs p, 
         for (int k = 0; k < 6; ++k) acc[k] += wave_sum(sm[k]) * inv;
         acc[6] += sw;
     }
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < kLmSums; ++k) red[wv][k] = acc[k];
-    __syncthreads();
-    float sum = 0.f;
-    if (threadIdx.x < kLmSums) {
-        const int k = threadIdx.x;
-        sum = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
-    }
-    publish_sums<kLmSums, 256>(sum, partials, fold);
+    publish_wave_sums<kLmSums>(acc, partials, fold);
 }
 
 // sums (7) -> out8: the six aggregates, the denominator (sum w in 'token' mode, 1 in 'sequence' mode), 0.  raw: the
@@ -614,11 +368,9 @@ extern "C" int hpc_rll_lm_head_forward(const void* logits, int elem, const int64
                                        float* lse, float* entropy, int64_t rows, int V, void* stream) {
     const bool empty = rows == 0 || V == 0;
     if (!empty && (!logits || !action || !logp || !lse || !entropy)) return HPC_RLL_EINVAL;
-    if (rows < 0 || V < 0 || !elem_ok(elem)) return HPC_RLL_EINVAL;
-    if (!aligned(logits, elem_size(elem)) || !aligned(action, 8) || !aligned(weight, 4) || !aligned(logp, 4) ||
-        !aligned(lse, 4) || !aligned(entropy, 4))
-        return HPC_RLL_EALIGN;
-    if (V > kGrpoMaxV) return HPC_RLL_EUNSUPPORTED;
+    if (const int bad = lm_shape_status(rows, 1, V, elem, aligned(logits, elem_size(elem)) && aligned(action, 8) &&
+                                        aligned(weight, 4) && aligned(logp, 4) && aligned(lse, 4) && aligned(entropy, 4)))
+        return bad;
     hipStream_t st = (hipStream_t)stream;
     if (empty) {   // V == 0 with rows: no token has a probability; zeros
         for (float* o : {logp, lse, entropy})
@@ -636,11 +388,10 @@ extern "C" int hpc_rll_lm_head_backward(const float* g_logp, const float* g_entr
                                         void* grad_logits, int64_t rows, int V, void* stream) {
     const bool empty = rows == 0 || V == 0;
     if (!empty && (!logits || !action || !lse || !entropy || !grad_logits)) return HPC_RLL_EINVAL;
-    if (rows < 0 || V < 0 || !elem_ok(elem)) return HPC_RLL_EINVAL;
-    if (!aligned(logits, elem_size(elem)) || !aligned(grad_logits, elem_size(elem)) || !aligned(action, 8) ||
-        !aligned(g_logp, 4) || !aligned(g_entropy, 4) || !aligned(weight, 4) || !aligned(lse, 4) || !aligned(entropy, 4))
-        return HPC_RLL_EALIGN;
-    if (V > kGrpoMaxV) return HPC_RLL_EUNSUPPORTED;
+    if (const int bad = lm_shape_status(rows, 1, V, elem, aligned(logits, elem_size(elem)) && aligned(grad_logits, elem_size(elem)) &&
+                                        aligned(action, 8) && aligned(g_logp, 4) && aligned(g_entropy, 4) &&
+                                        aligned(weight, 4) && aligned(lse, 4) && aligned(entropy, 4)))
+        return bad;
     if (empty) return HPC_RLL_OK;
     const LmGradArgs q{action, weight, lse, entropy, g_logp, g_entropy, nullptr, nullptr, nullptr, 1.f};
     return lm_grad_any(logits, elem, q, grad_logits, (long)rows, V, (hipStream_t)stream);
@@ -692,12 +443,10 @@ extern "C" int hpc_rll_lm_ppo_forward(const void* logit_new, int elem, const flo
     if (!empty && (!logit_new || !old_logp || !action || !adv || !ws)) return HPC_RLL_EINVAL;
     const int nval = (value_new ? 1 : 0) + (value_old ? 1 : 0) + (ret ? 1 : 0);
     if (nval != 0 && nval != 3) return HPC_RLL_EINVAL;
-    if (B < 0 || S < 0 || V < 0 || !elem_ok(elem)) return HPC_RLL_EINVAL;
-    if (!aligned(logit_new, elem_size(elem)) || !aligned(old_logp, 4) || !aligned(action, 8) || !aligned(adv, 4) ||
-        !aligned(weight, 4) || !aligned(value_new, 4) || !aligned(value_old, 4) || !aligned(ret, 4) || !aligned(out8, 4) ||
-        !aligned(ws, 4))
-        return HPC_RLL_EALIGN;
-    if (V > kGrpoMaxV) return HPC_RLL_EUNSUPPORTED;
+    if (const int bad = lm_shape_status(B, S, V, elem, aligned(logit_new, elem_size(elem)) && aligned(old_logp, 4) &&
+                                        aligned(action, 8) && aligned(adv, 4) && aligned(weight, 4) && aligned(value_new, 4) &&
+                                        aligned(value_old, 4) && aligned(ret, 4) && aligned(out8, 4) && aligned(ws, 4)))
+        return bad;
     hipStream_t st = (hipStream_t)stream;
     if (empty) return (int)hipMemsetAsync(out8, 0, 8 * sizeof(float), st);
     const long R = (long)B * S;
@@ -730,12 +479,10 @@ extern "C" int hpc_rll_lm_ppo_backward(const float* g_policy, const float* g_ent
                                        void* stream) {
     const bool empty = B == 0 || S == 0 || V == 0;
     if (!empty && (!action || !ws || (grad_logit && !logit_new))) return HPC_RLL_EINVAL;
-    if (B < 0 || S < 0 || V < 0 || !elem_ok(elem)) return HPC_RLL_EINVAL;
-    if (!aligned(logit_new, elem_size(elem)) || !aligned(grad_logit, elem_size(elem)) || !aligned(action, 8) ||
-        !aligned(g_policy, 4) || !aligned(g_entropy, 4) || !aligned(g_value, 4) || !aligned(weight, 4) || !aligned(ws, 4) ||
-        !aligned(grad_value, 4))
-        return HPC_RLL_EALIGN;
-    if (V > kGrpoMaxV) return HPC_RLL_EUNSUPPORTED;
+    if (const int bad = lm_shape_status(B, S, V, elem, aligned(logit_new, elem_size(elem)) && aligned(grad_logit, elem_size(elem)) &&
+                                        aligned(action, 8) && aligned(g_policy, 4) && aligned(g_entropy, 4) &&
+                                        aligned(g_value, 4) && aligned(weight, 4) && aligned(ws, 4) && aligned(grad_value, 4)))
+        return bad;
     if (empty) return HPC_RLL_OK;
     hipStream_t st = (hipStream_t)stream;
     const long R = (long)B * S;

@@ -22,34 +22,14 @@ import torch
 
 import lm_ppo_oracle as O
 from conftest import grad_err, rel_err
+from lm_rows import DTYPES, GRID_MAX, WAVE_ROW_MAX, _width_cases, dev, expect_grad, expect_head, place
 
 pytestmark = pytest.mark.gpu
 
 F64 = torch.float64
 CLIP, VCLIP = 0.2, 0.2
-WIDTHS = (1, 3, 7, 255, 1023, 1024, 1025, 4099, 16384, 16388, 32768, 50257, 151936, 262144)
-WAVE_ROW_MAX = 2048
-GRID_MAX = 1 << 16       # workgroups of a row launch; above it they loop
 FOLD_MAX = 512           # workgroups of the token and GAE launches; above it they loop
 CHUNK = 64               # tokens per step of a GAE wave
-DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16}
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def place(x, off=0):
-    """A contiguous GPU copy of ``x`` whose base lies ``off`` ELEMENTS past a 16-byte boundary (None passes through)."""
-    if x is None:
-        return None
-    n = x.numel()
-    buf = torch.empty(n + 16, dtype=x.dtype, device=dev())
-    assert buf.data_ptr() % 16 == 0
-    t = buf[off:off + n].view(x.shape)
-    t.copy_(x)
-    assert t.is_contiguous() and t.data_ptr() % 16 == (off * x.element_size()) % 16
-    return t
 
 
 def last_config():
@@ -58,23 +38,6 @@ def last_config():
     assert cabi.lib.hpc_rll_lm_ppo_last_config(out) == 0
     out = list(out)
     return dict(head=out[0:7], gae=out[7:12], whiten=out[12:15], token=out[15:18], grad=out[18:24])
-
-
-def expect_head(x, rows, V):
-    """[element type, bytes per load, peeled, threads per row, rows per workgroup, workgroups] of the head launch."""
-    e = x.element_size()
-    al = x.data_ptr() % 16 == 0 and (V * e) % 16 == 0
-    wide_row = V > WAVE_ROW_MAX
-    rpw = 1 if wide_row else 4
-    return [0 if e == 4 else 1, 16, 0 if al else 1, 256 if wide_row else 64, rpw, min(-(-rows // rpw), GRID_MAX)]
-
-
-def expect_grad(x, grad, rows, V):
-    e = x.element_size()
-    wide = x.data_ptr() % 16 == 0 and grad.data_ptr() % 16 == 0 and (V * e) % 16 == 0
-    wide_row = V > WAVE_ROW_MAX
-    rpw = 1 if wide_row else 4
-    return [0 if e == 4 else 1, 16 if wide else e, 256 if wide_row else 64, rpw, min(-(-rows // rpw), GRID_MAX)]
 
 
 # ------------------------------------------------------------------------------------------------------------- the bars
@@ -197,10 +160,6 @@ def check_against(c, o, res, what, **kw):
 
 
 # ---------------------------------------------------------------------------------------------------- vocabulary widths
-def _width_cases():
-    return [(V, name, off) for V in WIDTHS for name in DTYPES for off in (0, 1)]
-
-
 def test_the_widths_reach_every_kernel_variant():
     """(element type, peeled, threads per row) of the head and (element type, load width, threads per row) of the gradient
     launch, computed as the tests below pin them: all 8 + 8 variants of the dispatchers occur."""
