@@ -866,6 +866,15 @@ __global__ __launch_bounds__(256, 4) void qrdqn_fwd_quad_kernel(
 
 inline int group_lanes(int n) { return n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : 64; }
 
+// The dispatch records (hpc_rll_dist_last_config): one per op, noted next to every forward launch with the template arguments
+// OF THAT LAUNCH, so that a record names the instantiation that ran, not a second evaluation of the rule.  G = lanes that hold
+// one sample (64 for the kernels that give a sample the whole wave), SW = samples a wave walks (0: the kernel has no such
+// loop), folded = the loss was finalised inside the launch (fold.out) instead of by finalize_sums.
+LaunchRecord<HPC_RLL_DIST_CONFIG_INTS> g_dist_last[HPC_RLL_DIST_OPS];
+void dist_note(int op, int family, int g, int sw, bool full, bool bnt, int grid, const ScanFold& fold) {
+    g_dist_last[op].note({family, g, sw, full ? 1 : 0, bnt ? 1 : 0, grid, fold.out ? 1 : 0});
+}
+
 }  // namespace
 
 int g_sample_batch = 0;   // hpc_rll_tune_set key 24: samples per wave of the large-batch QR-DQN forward (0 = by batch size, 1 = off)
@@ -896,20 +905,25 @@ extern "C" int hpc_rll_dist_nstep_td_forward(const float* dist, const float* nex
     const float gamma_n = (float)pow((double)gamma, (double)nstep);
     if (sw > 1) {
 #define HPC_RLL_C51_B(SW_)                                                                                            \
-        if (sw == SW_)                                                                                                \
+        if (sw == SW_) {                                                                                              \
             hipLaunchKernelGGL(dist_nstep_fwd_batch_kernel<SW_>, dim3(blocks), dim3(256), 0, st, dist, next_n_dist,    \
                                action, next_n_action, reward, done, weight, td_err, buf, partials, nstep, B, N, n_atom, \
-                               gamma, gamma_n, v_min, v_max, dz, inv_dz, scale, fold);
+                               gamma, gamma_n, v_min, v_max, dz, inv_dz, scale, fold);                                 \
+            dist_note(HPC_RLL_DIST_OP_C51, HPC_RLL_DIST_FAMILY_BATCH, 64, SW_, false, false, blocks, fold);            \
+        }
         HPC_RLL_C51_B(8) HPC_RLL_C51_B(16) HPC_RLL_C51_B(32) HPC_RLL_C51_B(64)
 #undef HPC_RLL_C51_B
-    } else if (n_atom <= 64)
+    } else if (n_atom <= 64) {
         hipLaunchKernelGGL(dist_nstep_fwd64_kernel<1>, dim3(blocks), dim3(256), 0, st, dist, next_n_dist, action,
                            next_n_action, reward, done, weight, td_err, buf, partials, nstep, B, N, n_atom, gamma, gamma_n,
                            v_min, v_max, dz, scale, fold);
-    else
+        dist_note(HPC_RLL_DIST_OP_C51, HPC_RLL_DIST_FAMILY_WAVE64, 64, 0, false, false, blocks, fold);
+    } else {
         hipLaunchKernelGGL(dist_nstep_fwd_kernel, dim3(blocks), dim3(256), 0, st, dist, next_n_dist, action,
                            next_n_action, reward, done, weight, td_err, buf, partials, nstep, B, N, n_atom, gamma, gamma_n,
                            v_min, v_max, dz, scale, fold);
+        dist_note(HPC_RLL_DIST_OP_C51, HPC_RLL_DIST_FAMILY_GENERAL, 64, 0, false, false, blocks, fold);
+    }
     const int rc = last_error();
     if (rc || fold.out) return rc;
     return finalize_sums(partials, blocks, 1, &scale, loss, st);
@@ -951,6 +965,7 @@ int iqn_forward_impl(const float* q, const float* next_n_q, const int64_t* actio
                 hipLaunchKernelGGL((iqn_fwd_group_kernel<G_, false>), dim3(blocks), dim3(256), 0, st, q, next_n_q, action, \
                                    next_n_action, reward, done, replay_quantiles, weight, value_gamma, td_err, buf,     \
                                    partials, tau, tau_prime, nstep, B, N, gamma, gamma_n, kappa, scale, fold);          \
+            dist_note(HPC_RLL_DIST_OP_IQN, HPC_RLL_DIST_FAMILY_GROUP, G_, 0, false, bnt, blocks, fold);                 \
         }
         HPC_RLL_IQN_G(8) HPC_RLL_IQN_G(16) HPC_RLL_IQN_G(32) HPC_RLL_IQN_G(64)
 #undef HPC_RLL_IQN_G
@@ -958,6 +973,7 @@ int iqn_forward_impl(const float* q, const float* next_n_q, const int64_t* actio
         hipLaunchKernelGGL(iqn_fwd_kernel, dim3(blocks), dim3(256), 0, st, q, next_n_q, action, next_n_action, reward,
                            done, replay_quantiles, weight, value_gamma, td_err, buf, partials, tau, tau_prime, nstep, B,
                            N, gamma, gamma_n, kappa, scale, fold, bnt ? 1 : 0);
+        dist_note(HPC_RLL_DIST_OP_IQN, HPC_RLL_DIST_FAMILY_WAVE, 64, 0, false, bnt, blocks, fold);
     }
     const int rc = last_error();
     if (rc || fold.out) return rc;
@@ -1039,7 +1055,8 @@ extern "C" int hpc_rll_qrdqn_nstep_td_forward(const float* q, const float* next_
         const int G = tau <= 32 ? 8 : 16;
 #define HPC_RLL_QR_Q(G_, SW_)                                                                                         \
         if (G == G_ && sw == SW_) {                                                                                   \
-            if (tau == 4 * G_)                                                                                        \
+            const bool full = tau == 4 * G_;                                                                          \
+            if (full)                                                                                                 \
                 hipLaunchKernelGGL((qrdqn_fwd_quad_kernel<G_, SW_, true>), dim3(blocks), dim3(256), 0, st, q, next_n_q, \
                                    action, next_n_action, reward, done, weight, value_gamma, td_err, buf, partials, tau, \
                                    nstep, B, N, gamma, gamma_n, tau_value, scale, fold);                              \
@@ -1047,6 +1064,7 @@ extern "C" int hpc_rll_qrdqn_nstep_td_forward(const float* q, const float* next_
                 hipLaunchKernelGGL((qrdqn_fwd_quad_kernel<G_, SW_, false>), dim3(blocks), dim3(256), 0, st, q, next_n_q, \
                                    action, next_n_action, reward, done, weight, value_gamma, td_err, buf, partials, tau, \
                                    nstep, B, N, gamma, gamma_n, tau_value, scale, fold);                              \
+            dist_note(HPC_RLL_DIST_OP_QRDQN, HPC_RLL_DIST_FAMILY_QUAD, G_, SW_, full, false, blocks, fold);           \
         }
         HPC_RLL_QR_Q(8, 8) HPC_RLL_QR_Q(8, 16) HPC_RLL_QR_Q(8, 32) HPC_RLL_QR_Q(8, 64)
         HPC_RLL_QR_Q(16, 8) HPC_RLL_QR_Q(16, 16) HPC_RLL_QR_Q(16, 32) HPC_RLL_QR_Q(16, 64)
@@ -1055,7 +1073,8 @@ extern "C" int hpc_rll_qrdqn_nstep_td_forward(const float* q, const float* next_
         const int G = group_lanes(tau);
 #define HPC_RLL_QR_B(G_, SW_)                                                                                         \
         if (G == G_ && sw == SW_) {                                                                                   \
-            if (tau == G_)                                                                                            \
+            const bool full = tau == G_;                                                                              \
+            if (full)                                                                                                 \
                 hipLaunchKernelGGL((qrdqn_fwd_batch_kernel<G_, SW_, true>), dim3(blocks), dim3(256), 0, st, q, next_n_q, \
                                    action, next_n_action, reward, done, weight, value_gamma, td_err, buf, partials, tau, \
                                    nstep, B, N, gamma, gamma_n, tau_value, scale, fold);                              \
@@ -1063,6 +1082,7 @@ extern "C" int hpc_rll_qrdqn_nstep_td_forward(const float* q, const float* next_
                 hipLaunchKernelGGL((qrdqn_fwd_batch_kernel<G_, SW_, false>), dim3(blocks), dim3(256), 0, st, q, next_n_q, \
                                    action, next_n_action, reward, done, weight, value_gamma, td_err, buf, partials, tau, \
                                    nstep, B, N, gamma, gamma_n, tau_value, scale, fold);                              \
+            dist_note(HPC_RLL_DIST_OP_QRDQN, HPC_RLL_DIST_FAMILY_BATCH, G_, SW_, full, false, blocks, fold);          \
         }
         HPC_RLL_QR_B(8, 8) HPC_RLL_QR_B(8, 16) HPC_RLL_QR_B(8, 32) HPC_RLL_QR_B(8, 64) HPC_RLL_QR_B(16, 8) HPC_RLL_QR_B(16, 16)
         HPC_RLL_QR_B(16, 32) HPC_RLL_QR_B(16, 64) HPC_RLL_QR_B(32, 8) HPC_RLL_QR_B(32, 16) HPC_RLL_QR_B(32, 32) HPC_RLL_QR_B(32, 64)
@@ -1071,16 +1091,19 @@ extern "C" int hpc_rll_qrdqn_nstep_td_forward(const float* q, const float* next_
     } else if (tau <= 64) {
         const int G = group_lanes(tau);
 #define HPC_RLL_QR_G(G_)                                                                                              \
-        if (G == G_)                                                                                                  \
+        if (G == G_) {                                                                                                \
             hipLaunchKernelGGL(qrdqn_fwd_group_kernel<G_>, dim3(blocks), dim3(256), 0, st, q, next_n_q, action,        \
                                next_n_action, reward, done, weight, value_gamma, td_err, buf, partials, tau, nstep, B, N, \
-                               gamma, gamma_n, tau_value, scale, fold);
+                               gamma, gamma_n, tau_value, scale, fold);                                                \
+            dist_note(HPC_RLL_DIST_OP_QRDQN, HPC_RLL_DIST_FAMILY_GROUP, G_, 0, false, false, blocks, fold);            \
+        }
         HPC_RLL_QR_G(8) HPC_RLL_QR_G(16) HPC_RLL_QR_G(32) HPC_RLL_QR_G(64)
 #undef HPC_RLL_QR_G
     } else {
         hipLaunchKernelGGL(qrdqn_fwd_kernel, dim3(blocks), dim3(256), 0, st, q, next_n_q, action, next_n_action, reward,
                            done, weight, value_gamma, td_err, buf, partials, tau, nstep, B, N, gamma, gamma_n, tau_value,
                            scale, fold);
+        dist_note(HPC_RLL_DIST_OP_QRDQN, HPC_RLL_DIST_FAMILY_WAVE, 64, 0, false, false, blocks, fold);
     }
     const int rc = last_error();
     if (rc || fold.out) return rc;
@@ -1093,4 +1116,10 @@ extern "C" int hpc_rll_qrdqn_nstep_td_backward(const float* grad_loss, const flo
     if (B == 0) return HPC_RLL_OK;
     if (!grad_loss || !buf || !action || !grad_q) return HPC_RLL_EINVAL;
     return onehot_scatter(grad_loss, buf, action, grad_q, B, N, tau, (hipStream_t)stream);
+}
+
+extern "C" int hpc_rll_dist_last_config(int op, int* out) {
+    if (op < 0 || op >= HPC_RLL_DIST_OPS || !out) return HPC_RLL_EINVAL;
+    g_dist_last[op].read(out);
+    return HPC_RLL_OK;
 }

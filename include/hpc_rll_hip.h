@@ -770,6 +770,35 @@ int hpc_rll_qrdqn_nstep_td_forward(const float* q, const float* next_n_q, const 
                                    float tau_value, float scale, void* stream);
 int hpc_rll_qrdqn_nstep_td_backward(const float* grad_loss, const float* buf, const int64_t* action, float* grad_q,
                                     int tau, int B, int N, void* stream);
+/* Diagnostic (no reference counterpart; read-only, modelled on hpc_rll_categorical_last_config / hpc_rll_r2d2_last_config): which
+ * forward kernel the most recent launch of hpc_rll_dist_nstep_td_forward (op HPC_RLL_DIST_OP_C51), of
+ * hpc_rll_iqn_nstep_td_forward / _forward_bnt (HPC_RLL_DIST_OP_IQN) or of hpc_rll_qrdqn_nstep_td_forward
+ * (HPC_RLL_DIST_OP_QRDQN) ran in this process, recorded on the host where the kernel is launched.  Each op keeps its own
+ * record.  out[HPC_RLL_DIST_CONFIG_INTS] = {
+ *    [0] forward launches of this op so far (0 = no launch yet: every other entry is then -1),
+ *    [1] kernel family, one of HPC_RLL_DIST_FAMILY_*,
+ *    [2] G: lanes that hold one sample -- 8 / 16 / 32 / 64 for GROUP, BATCH and QUAD of IQN / QR-DQN (QUAD: 8 or 16, four
+ *        quantiles per lane), 64 for every kernel that gives a sample the whole wave (WAVE, and all three C51 families),
+ *    [3] SW: consecutive samples a wave walks, 8 / 16 / 32 / 64 for BATCH and QUAD (tune key 24, or by batch size); 0 for the
+ *        families without that loop,
+ *    [4] FULL: 1 = the instantiation without a tail (QR-DQN BATCH: tau == G, QUAD: tau == 4 G), else 0,
+ *    [5] layout: 1 = quantile axis innermost (hpc_rll_iqn_nstep_td_forward_bnt), 0 otherwise,
+ *    [6] workgroups of the launch,
+ *    [7] 1 = the loss was finalised inside the launch (the fold of tune key 21), 0 = by a separate finalize launch }.
+ * Calls that return before launching (B == 0, argument errors) leave the record as it was; the backward entry points keep
+ * no record.  Plain ints of the host process, not synchronised.  HPC_RLL_EINVAL for an op outside the three or out == NULL. */
+#define HPC_RLL_DIST_OP_C51 (0)
+#define HPC_RLL_DIST_OP_IQN (1)
+#define HPC_RLL_DIST_OP_QRDQN (2)
+#define HPC_RLL_DIST_OPS (3)
+#define HPC_RLL_DIST_FAMILY_WAVE (0)      /* IQN, QR-DQN: a wave per sample, any tau (the only kernels for tau or tau' > 64) */
+#define HPC_RLL_DIST_FAMILY_GROUP (1)     /* IQN, QR-DQN: a sample per group of G lanes, 64 / G samples per wave */
+#define HPC_RLL_DIST_FAMILY_BATCH (2)     /* C51 (n_atom <= 64), QR-DQN: SW consecutive samples per wave */
+#define HPC_RLL_DIST_FAMILY_QUAD (3)      /* QR-DQN: BATCH with four quantiles per lane (tau % 4 == 0, tau >= 8, 16-byte aligned rows) */
+#define HPC_RLL_DIST_FAMILY_WAVE64 (4)    /* C51, n_atom <= 64: a wave per sample, sources gathered in source order */
+#define HPC_RLL_DIST_FAMILY_GENERAL (5)   /* C51, n_atom > 64: a wave per sample, every target walks every source */
+#define HPC_RLL_DIST_CONFIG_INTS (8)
+int hpc_rll_dist_last_config(int op, int* out);
 
 /* ------------------------------------------------------------------------------------------
  * Pad / Unpad of a ragged list of n contiguous fp32 tensors of rank 1..3 -- replaces Pad{1,2,3}DForward,

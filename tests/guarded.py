@@ -68,6 +68,27 @@ class GuardedU8:
         assert self.t.is_contiguous() and self.t.data_ptr() % 2 == off, "the mask lost its byte offset"
 
 
+SENTINEL64 = 0x5EED5EED5EED5EED
+
+
+class GuardedI64:
+    """A copy of the int64 vector ``src`` (the actions of a head or a TD op) on ``dev`` between two sentinel bands;
+    ``check()`` also asserts that the values themselves are still those of ``src``."""
+
+    def __init__(self, src, dev):
+        n = src.numel()
+        self.raw = torch.full((GUARD + n + GUARD,), SENTINEL64, dtype=torch.int64, device=dev)
+        self.lo, self.hi = GUARD, GUARD + n
+        self.t = self.raw[self.lo:self.hi]
+        self.t.copy_(src)
+        self.src = src.clone()
+
+    def check(self, what=""):
+        assert bool((self.raw[:self.lo] == SENTINEL64).all()) and bool((self.raw[self.hi:] == SENTINEL64).all()), \
+            f"{what}: a guard word around the actions was overwritten"
+        assert torch.equal(self.t.cpu(), self.src), f"{what}: the actions were overwritten"
+
+
 def place(x, off):
     """A copy of the float32 (rows, ...) tensor ``x`` at ``off`` floats past a 16-byte boundary, guard bands around it."""
     x = x.detach()

@@ -2,7 +2,7 @@
 (``hpc_rll_categorical_forward`` / ``_backward``) on an MI355X (``-m gpu``) and compared per row with an fp64 oracle.
 
 How a launch is checked.  Every operand and every output lives in a buffer with sentinel bands on both sides
-(tests/guarded.py; the int64 actions in this file's own ``GuardedI64``), outputs are pre-filled with NaN.  After EVERY launch:
+(tests/guarded.py; the int64 actions in its ``GuardedI64``), outputs are pre-filled with NaN.  After EVERY launch:
 ``hpc_rll_categorical_last_config`` shows exactly one more launch in that direction and names the family, (G, VEC, E), R, the
 entropy flag and the grid that the tables below hold as LITERALS; both bands of every buffer are intact; no NaN is left in an
 output.  A case is four launches on the same inputs: forward with entropy, forward with ``entropy = NULL`` (the no-entropy
@@ -41,7 +41,7 @@ import pytest
 import torch
 
 from conftest import grad_err, rel_err
-from guarded import GUARD, GuardedF32
+from guarded import GuardedF32, GuardedI64
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -155,24 +155,6 @@ class launches:
 # ---------------------------------------------------------------------------------------------------------------------
 # buffers
 # ---------------------------------------------------------------------------------------------------------------------
-SENTINEL64 = 0x5EED5EED5EED5EED
-
-
-class GuardedI64:
-    """The int64 actions between two sentinel bands (tests/guarded.py has float32 and byte buffers only)."""
-
-    def __init__(self, src):
-        n = src.numel()
-        self.raw = torch.full((GUARD + n + GUARD,), SENTINEL64, dtype=torch.int64, device=DEV)
-        self.lo, self.hi = GUARD, GUARD + n
-        self.t = self.raw[self.lo:self.hi]
-        self.t.copy_(src)
-        self.src = src.clone()
-
-    def check(self, what=""):
-        assert bool((self.raw[:self.lo] == SENTINEL64).all()) and bool((self.raw[self.hi:] == SENTINEL64).all()), \
-            f"{what}: a guard word around the actions was overwritten"
-        assert torch.equal(self.t.cpu(), self.src), f"{what}: the actions were overwritten"
 
 
 class Problem:
@@ -186,7 +168,7 @@ class Problem:
         self.c1 = torch.randn(rows, generator=g) + 0.25
         self.c2 = torch.randn(rows, generator=g) - 0.25
         self.dx = GuardedF32(rows, N, off_x, DEV, src=x.to(DEV))
-        self.da = GuardedI64(a)
+        self.da = GuardedI64(a, DEV)
         self.dc1 = GuardedF32(rows, 1, 0, DEV, src=self.c1.view(rows, 1).to(DEV))
         self.dc2 = GuardedF32(rows, 1, 0, DEV, src=self.c2.view(rows, 1).to(DEV))
         self.du1 = GuardedF32(1, 1, 0, DEV, src=torch.tensor([[U1]], device=DEV))

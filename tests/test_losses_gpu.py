@@ -671,7 +671,10 @@ def test_qrdqn_samples_per_wave_kernel_equals_group_kernel(tau, B, sw):
     of 4 qrdqn_fwd_quad_kernel; scalars loaded coalesced by owner lanes, targets staged through LDS).  Against the
     group-per-sample kernel (tune key 24 = 1) on ragged batches, every group width, full and partial groups: unit gradients
     bit for bit (batch kernel) or to the order of the tau-term sum (quad kernel), per-sample errors up to the order of the
-    sum (DPP instead of butterfly), and both against the fp64 oracle."""
+    sum (DPP instead of butterfly), and both against the fp64 oracle.  Of the batch kernel this reaches the instantiations
+    with a tail only (FULL = false): tau == G is a multiple of 4, and torch allocations are 16-byte aligned, so such a tau
+    takes the quad kernel here.  qrdqn_fwd_batch_kernel<G, SW, true> runs in tests/test_dist_td_gpu.py, through an operand
+    4 bytes off alignment."""
     import hpc_rl_utils as U
     from hpc_rll.rl_utils.td import QRDQNNStepTDError
     T, N = 3, 6
