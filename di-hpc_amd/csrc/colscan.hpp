@@ -415,8 +415,19 @@ inline int scan_and_finalize(const Op& op, const ScanCfg& c, int T, int B, float
     return finalize_sums(partials, (int)scan_grid(c, B), nacc, scale, out, st);
 }
 
+// One launch of `grid` workgroups that ends in `nacc` loss sums (publish_sums above), finalised into `out` (x scales[k]): the
+// fold is armed for this grid, launch(grid, fold) issues the kernel and returns its status (last_error()), and finalize_sums
+// adds the partials in a second launch where no fold was available.
+template <class L>
+int launch_folded(long grid, int nacc, const float* scales, float* out, float* partials, hipStream_t st, L&& launch) {
+    const ScanFold fold = make_fold(st, nacc, scales, out, grid);
+    const int rc = launch((unsigned)grid, fold);
+    if (rc || fold.out) return rc;
+    return finalize_sums(partials, (int)grid, nacc, scales, out, st);
+}
+
 // The forward of a head that ends in `nacc` loss sums: at most kFoldMaxGrid workgroups, which loop, so that the sums are
-// folded inside the launch (publish_sums above); finalize_sums where no fold is available.  launch(grid, fold) issues the kernel.
+// folded inside the launch; finalize_sums where no fold is available.  launch(grid, fold) issues the kernel.
 // *grid is set once the launch has succeeded (the caller's dispatch record).
 template <class L>
 int launch_rows_folded(long rows, long rows_per_block, int nacc, const float* scales, float* out, float* partials,
@@ -424,13 +435,12 @@ int launch_rows_folded(long rows, long rows_per_block, int nacc, const float* sc
     long g = (rows + rows_per_block - 1) / rows_per_block;
     if (g > kFoldMaxGrid) g = kFoldMaxGrid;
     if (g < 1) g = 1;
-    const ScanFold fold = make_fold(st, nacc, scales, out, g);
-    launch((unsigned)g, fold);
-    const int rc = last_error();
-    if (rc) return rc;
-    *grid = g;
-    if (fold.out) return rc;
-    return finalize_sums(partials, (int)g, nacc, scales, out, st);
+    return launch_folded(g, nacc, scales, out, partials, st, [&](unsigned blocks, const ScanFold& fold) {
+        launch(blocks, fold);
+        const int rc = last_error();
+        if (!rc) *grid = g;
+        return rc;
+    });
 }
 
 }  // namespace hpc_rll

@@ -30,19 +30,61 @@ namespace {
 // 4 waves (= 4 samples) per workgroup; workgroup partial = sum of its 4 per-sample weighted losses.
 template <class F>
 __device__ __forceinline__ void wave_per_sample(int B, float* __restrict__ partials, const ScanFold& fold, F&& body) {
-    __shared__ float red[4];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int b = blockIdx.x * 4 + w;
-    float contrib = 0.f;
-    if (b < B) contrib = body(b, lane);
-    if (lane == 0) red[w] = contrib;
-    __syncthreads();
-    float s = 0.f;
-    if (threadIdx.x == 0) s = (red[0] + red[1]) + (red[2] + red[3]);
-    publish_sums<1, 256>(s, partials, fold);   // with a fold: the last workgroup also finalises the loss (colscan.hpp)
+    float contrib[1] = {0.f};
+    if (b < B) contrib[0] = body(b, lane);
+    publish_wave_sums<1>(contrib, partials, fold);   // with a fold: the last workgroup also finalises the loss (colscan.hpp)
+}
+
+// The per-sample scalars every kernel below starts from.  All of them are requested before the first use: the reward loop
+// of nstep_return1 waits for its loads, and only then can the sample's rows be addressed.
+struct SampleScalars {
+    long b, a, na;   // the sample the scalars were loaded from, its action and next action
+    float vg;        // the discount of the bootstrap: (value_gamma or gamma^n) * (1 - done)
+    float w, R;      // weight (1 when absent), n-step return
+};
+__device__ __forceinline__ SampleScalars load_sample(long b, const int64_t* __restrict__ action,
+                                                     const int64_t* __restrict__ next_action,
+                                                     const float* __restrict__ reward, const float* __restrict__ done,
+                                                     const float* __restrict__ weight,
+                                                     const float* __restrict__ value_gamma, int nstep, int B, float gamma,
+                                                     float gamma_n) {
+    SampleScalars s;
+    s.b = b;
+    s.a = action[b];
+    s.na = next_action[b];
+    const float dn = done[b], vgm = value_gamma ? value_gamma[b] : gamma_n;
+    s.w = weight ? weight[b] : 1.f;
+    s.R = nstep_return1(reward, B, nstep, gamma, b);
+    s.vg = vgm * (1.f - dn);
+    return s;
+}
+
+// The tail of the samples-per-wave kernels, whose lane l < SW owns sample `bown` (weight `w_l`, td_err `mine`): the workgroup
+// partial adds its samples in butterfly order.  Called by all 256 threads.
+template <int SW>
+__device__ __forceinline__ void publish_owned_samples(int lane, long bown, float w_l, float mine, int B, float* __restrict__ td_err,
+                                                      float* __restrict__ partials, const ScanFold& fold) {
+    const bool own = lane < SW && bown < (long)B;
+    if (own) td_err[bown] = mine;
+    const float contrib[1] = {wave_sum(own ? mine * w_l : 0.f)};
+    publish_wave_sums<1>(contrib, partials, fold);
 }
 
 // ------------------------------------------------------------------------------------------------ C51
+// Where source atom j lands: tz_j = clamp(R + nd_scale * support_j, v_min, v_max).  Its atom position bp = (tz - v_min) / dz
+// is left to the caller (the division and its host-reciprocal form, c51_project_scan).
+__device__ __forceinline__ float c51_source_value(int j, int n_atom, float R, float nd_scale, float v_min, float v_max) {
+    // support_j: torch.linspace(v_min, v_max, n_atom) evaluates start + j*step below the midpoint
+    // and end - (n-1-j)*step above it
+    const float step = (v_max - v_min) / (float)(n_atom - 1);
+    const float sup = (j < n_atom / 2) ? (v_min + step * (float)j) : (v_max - step * (float)(n_atom - 1 - j));
+    // unfused mul/add, like the oracle's tensor ops (origin/td.py:95-98)
+    const float tz = __fadd_rn(R, __fmul_rn(nd_scale, sup));
+    return fminf(fmaxf(tz, v_min), v_max);
+}
+
 // buf[b, k] = -w_b * proj[b,k] / p[b,a,k] * scale    (unit gradient wrt dist[b, a_b, k])
 __global__ __launch_bounds__(256) void dist_nstep_fwd_kernel(
     const float* __restrict__ dist, const float* __restrict__ next_dist, const int64_t* __restrict__ action,
@@ -61,13 +103,8 @@ __global__ __launch_bounds__(256) void dist_nstep_fwd_kernel(
             float proj = 0.f;
             // gather: source atoms j whose floor / ceil position is k (source order => deterministic sum)
             for (int j = 0; j < n_atom; ++j) {
-                // support_j: torch.linspace(v_min, v_max, n_atom) evaluates start + j*step below the midpoint
-                // and end - (n-1-j)*step above it
-                const float step = (v_max - v_min) / (float)(n_atom - 1);
-                const float sup = (j < n_atom / 2) ? (v_min + step * (float)j) : (v_max - step * (float)(n_atom - 1 - j));
-                // unfused mul/add/div, like the oracle's tensor ops (origin/td.py:95-98)
-                float tz = __fadd_rn(R, __fmul_rn(nd_scale, sup));
-                tz = fminf(fmaxf(tz, v_min), v_max);
+                const float tz = c51_source_value(j, n_atom, R, nd_scale, v_min, v_max);
+                // unfused sub/div, like the oracle's tensor ops (origin/td.py:95-98)
                 const float bp = __fdiv_rn(__fsub_rn(tz, v_min), dz);
                 const float lo = floorf(bp), up = ceilf(bp);
                 if ((int)lo == k) proj = fmaf(pn[j], up - bp, proj);
@@ -214,11 +251,7 @@ __device__ __forceinline__ void group_per_sample(int B, float* __restrict__ part
 __device__ __forceinline__ float c51_project64(int lane, int n_atom, float R, float nd_scale, float pn_j, float v_min,
                                                float v_max, float dz) {
     // source atom j = lane (the expressions of dist_nstep_fwd_kernel, evaluated once per source)
-    const int j = lane < n_atom ? lane : n_atom - 1;
-    const float step = (v_max - v_min) / (float)(n_atom - 1);
-    const float sup = (j < n_atom / 2) ? (v_min + step * (float)j) : (v_max - step * (float)(n_atom - 1 - j));
-    float tz = __fadd_rn(R, __fmul_rn(nd_scale, sup));
-    tz = fminf(fmaxf(tz, v_min), v_max);
+    const float tz = c51_source_value(lane < n_atom ? lane : n_atom - 1, n_atom, R, nd_scale, v_min, v_max);
     const float bp = __fdiv_rn(__fsub_rn(tz, v_min), dz);
     const float lo = floorf(bp), up = ceilf(bp);
     const int i_lo = (int)lo, i_up = (int)up;
@@ -274,64 +307,39 @@ __device__ __forceinline__ float c51_project64(int lane, int n_atom, float R, fl
     return proj;
 }
 
-// Round 3: S consecutive samples per wave (4 waves x S samples per workgroup).  A sample is a chain of dependent memory
-// round trips -- action -> row address -> row -- and with one sample per wave the kernel was bound by that latency times
-// the number of waves a SIMD can hold (0.26 ms for 248 + 59 MB at B = 262144): here the per-sample
-// scalars of all S samples are fetched together, then the 2*S rows, then the S projections run back to back.  The
-// arithmetic of a sample is unchanged (bit-identical td_err / buf); the workgroup partial adds 4*S contributions in order.
-// (Dispatched with S = 1 since dist_nstep_fwd_batch_kernel took over the large batches; S = 4 measured 0.187 ms at
-// B = 262144 against 0.069 ms for the batch kernel, tests/tools/r03_batch_probe.py.)
-template <int S>
+// n_atom <= 64, one sample per wave: the sample's scalars are fetched together, then its two rows, then the projection
+// runs.  A sample is a chain of dependent memory round trips -- action -> row address -> row -- and with one sample per wave
+// the kernel is bound by that latency times the number of waves a SIMD can hold (0.26 ms for 248 + 59 MB at B = 262144,
+// DESIGN.md section 4.4).  (Round 3 walked S consecutive samples per wave here: S = 4 measured 0.187 ms at B = 262144 against
+// 0.069 ms for dist_nstep_fwd_batch_kernel, which took over the large batches, tests/tools/r03_batch_probe.py.)
 __global__ __launch_bounds__(256) void dist_nstep_fwd64_kernel(
     const float* __restrict__ dist, const float* __restrict__ next_dist, const int64_t* __restrict__ action,
     const int64_t* __restrict__ next_action, const float* __restrict__ reward, const float* __restrict__ done,
     const float* __restrict__ weight, float* __restrict__ td_err, float* __restrict__ buf,
     float* __restrict__ partials, int nstep, int B, int N, int n_atom, float gamma, float gamma_n, float v_min,
     float v_max, float dz, float scale, const ScanFold fold) {
-    __shared__ float red[4];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const long first = ((long)blockIdx.x * 4 + w) * S;
-    long bb[S];
-    long a[S], na[S];
-    float dn[S], wt[S], R[S];
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-        bb[s] = first + s < (long)B ? first + s : (long)B - 1;       // clamped: every load below is unconditional
-        a[s] = action[bb[s]];
-        na[s] = next_action[bb[s]];
-        dn[s] = done[bb[s]];
-        wt[s] = weight ? weight[bb[s]] : 1.f;
-    }
-    nstep_returns<S>(reward, B, nstep, gamma, bb, R);
+    const long first = (long)blockIdx.x * 4 + w;
+    const bool live = first < (long)B;
+    // clamped: every load below is unconditional
+    const SampleScalars s = load_sample(live ? first : (long)B - 1, action, next_action, reward, done, weight, nullptr, nstep,
+                                        B, gamma, gamma_n);
     const int jl = lane < n_atom ? lane : n_atom - 1;
-    float pk[S], pnj[S];
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-        pk[s] = dist[((size_t)bb[s] * N + a[s]) * n_atom + jl];
-        pnj[s] = next_dist[((size_t)bb[s] * N + na[s]) * n_atom + jl];
+    const float pk = dist[((size_t)s.b * N + s.a) * n_atom + jl];
+    const float pnj = next_dist[((size_t)s.b * N + s.na) * n_atom + jl];
+    const float proj = c51_project64(lane, n_atom, s.R, s.vg, pnj, v_min, v_max, dz);
+    float ce = 0.f;
+    if (lane < n_atom) {
+        ce = proj * logf(pk);
+        if (live) buf[(size_t)s.b * n_atom + lane] = -s.w * proj / pk * scale;
     }
-    float contrib = 0.f;
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-        const float nd_scale = (1.f - dn[s]) * gamma_n;
-        const float proj = c51_project64(lane, n_atom, R[s], nd_scale, pnj[s], v_min, v_max, dz);
-        float ce = 0.f;
-        const bool live = first + s < (long)B;
-        if (lane < n_atom) {
-            ce = proj * logf(pk[s]);
-            if (live) buf[(size_t)bb[s] * n_atom + lane] = -wt[s] * proj / pk[s] * scale;
-        }
-        ce = wave_sum(ce);
-        if (live) {
-            if (lane == 0) td_err[bb[s]] = -ce;
-            contrib += -ce * wt[s];
-        }
+    ce = wave_sum(ce);
+    float contrib[1] = {0.f};
+    if (live) {
+        if (lane == 0) td_err[s.b] = -ce;
+        contrib[0] += -ce * s.w;
     }
-    if (lane == 0) red[w] = contrib;
-    __syncthreads();
-    float tot = 0.f;
-    if (threadIdx.x == 0) tot = (red[0] + red[1]) + (red[2] + red[3]);
-    publish_sums<1, 256>(tot, partials, fold);
+    publish_wave_sums<1>(contrib, partials, fold);
 }
 
 // The projection for large batches.  (A first version scattered with LDS float atomics, two ds_add_f32 per sample in the
@@ -354,11 +362,7 @@ __device__ __forceinline__ int dpp_mov(int old, int x) { return __builtin_amdgcn
 __device__ __forceinline__ float c51_project_scan(int* __restrict__ se, int lane, int n_atom, float R, float nd_scale,
                                                   float pn_j, float v_min, float v_max, float dz, float inv_dz) {
     const bool src = lane < n_atom;
-    const int j = src ? lane : n_atom - 1;
-    const float step = (v_max - v_min) / (float)(n_atom - 1);
-    const float sup = (j < n_atom / 2) ? (v_min + step * (float)j) : (v_max - step * (float)(n_atom - 1 - j));
-    float tz = __fadd_rn(R, __fmul_rn(nd_scale, sup));
-    tz = fminf(fmaxf(tz, v_min), v_max);
+    const float tz = c51_source_value(src ? lane : n_atom - 1, n_atom, R, nd_scale, v_min, v_max);
     // bp = (tz - v_min) / dz, correctly rounded, without the division sequence (two v_div_scale, v_rcp, five fmas, v_div_fmas,
     // v_div_fixup): dz is one number per launch, so its correctly rounded reciprocal comes from the host, and two residual
     // corrections of x * (1 / dz) give the rounded quotient (Markstein; the hardware sequence is the same two corrections on a
@@ -426,17 +430,16 @@ __global__ __launch_bounds__(256) void dist_nstep_fwd_batch_kernel(
     float v_max, float dz, float inv_dz, float scale, const ScanFold fold) {
     constexpr int U = 8;
     static_assert(SW % U == 0, "samples per wave");
-    __shared__ float red[4];
     __shared__ __attribute__((aligned(8))) int runs[4][128];       // per wave: {start, end} lane of the run of every atom
     // the wave index as a scalar: sample numbers and the addresses built from them stay in the scalar unit
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const long b0 = ((long)blockIdx.x * 4 + w) * SW;
+    // phase A as qrdqn_fwd_batch_kernel: lane l holds the scalars of sample b0 + l (lanes >= SW repeat the first SW samples)
     const long bown = b0 + lane % SW;
-    const long bl = bown < (long)B ? bown : (long)B - 1;
-    const int a_l = (int)action[bl], na_l = (int)next_action[bl];
-    const float w_l = weight ? weight[bl] : 1.f;
-    const float nd_l = (1.f - done[bl]) * gamma_n;
-    const float R_l = nstep_return1(reward, B, nstep, gamma, bl);
+    const SampleScalars own = load_sample(bown < (long)B ? bown : (long)B - 1, action, next_action, reward, done, weight, nullptr,
+                                          nstep, B, gamma, gamma_n);
+    const int a_l = (int)own.a, na_l = (int)own.na;
+    const float w_l = own.w, nd_l = own.vg, R_l = own.R;
     const int jl = lane < n_atom ? lane : n_atom - 1;
     auto bcast = [](float x, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), l)); };
     float mine = 0.f;
@@ -475,14 +478,17 @@ __global__ __launch_bounds__(256) void dist_nstep_fwd_batch_kernel(
             if (lane % SW == c + u) mine = -tot;
         }
     }
-    const bool own = lane < SW && bown < (long)B;
-    if (own) td_err[bown] = mine;
-    const float contrib = wave_sum(own ? mine * w_l : 0.f);
-    if (lane == 0) red[w] = contrib;
-    __syncthreads();
-    float tot = 0.f;
-    if (threadIdx.x == 0) tot = (red[0] + red[1]) + (red[2] + red[3]);
-    publish_sums<1, 256>(tot, partials, fold);
+    publish_owned_samples<SW>(lane, bown, w_l, mine, B, td_err, partials, fold);
+}
+
+// The pair loops of the group kernels take two targets per iteration: targets j and j + 1 of the group whose first lane is
+// `base`, lane l of it holding target l.  `two` (wave-uniform) is false at an odd tail, where .y repeats target j and the caller
+// takes it out of the sums.
+__device__ __forceinline__ vfloat2 fetch_two_targets(float tgt, int base, int j, bool two) {
+    vfloat2 t2;
+    t2.x = __shfl(tgt, base + j, 64);
+    t2.y = __shfl(tgt, base + (two ? j + 1 : j), 64);
+    return t2;
 }
 
 // BNT (round 6): q (B,N,tau), next_q (B,N,tau') -- the sample's quantiles are ONE contiguous row (128 bytes at tau = 32) instead of
@@ -497,7 +503,9 @@ __global__ __launch_bounds__(256) void iqn_fwd_group_kernel(
     group_per_sample<G>(B, partials, fold, [&](long b, bool ok, int gl, int base) -> float {
         float R = 0.f, vg = 0.f, w = 0.f, qi = 0.f, rho = 0.f, tgt = 0.f;
         if (ok) {
-            // every scalar of the sample is requested before the first use (the reward loop below waits for its loads)
+            // every scalar of the sample is requested before the first use (the reward loop below waits for its loads).  Not
+            // load_sample: rho is requested between the weight and the rewards, and moving it ahead of the other scalars
+            // cost 0.8 us of 126 at tau = tau' = 32, B = 65536 in the (tau,B,N) layout (profiles/r21_dist_ops_share.txt)
             const long a = action[b], na = next_action[b];
             const float dn = done[b], vgm = value_gamma ? value_gamma[b] : gamma_n;
             w = weight ? weight[b] : 1.f;
@@ -519,11 +527,8 @@ __global__ __launch_bounds__(256) void iqn_fwd_group_kernel(
         const vfloat2 q2 = {qi, qi}, mh2 = {-0.5f, -0.5f};
         vfloat2 li2 = {0.f, 0.f}, gi2 = {0.f, 0.f};
         for (int j = 0; j < tau_p; j += 2) {
-            const bool two = j + 1 < tau_p;                         // wave-uniform
-            vfloat2 t2;
-            t2.x = __shfl(tgt, base + j, 64);
-            t2.y = __shfl(tgt, base + (two ? j + 1 : j), 64);
-            const vfloat2 e = t2 - q2;
+            const bool two = j + 1 < tau_p;
+            const vfloat2 e = fetch_two_targets(tgt, base, j, two) - q2;
             vfloat2 dh, qw;
             dh.x = __builtin_amdgcn_fmed3f(e.x, -kappa, kappa);
             dh.y = __builtin_amdgcn_fmed3f(e.y, -kappa, kappa);
@@ -559,14 +564,16 @@ __device__ __forceinline__ vfloat2 pk_sub_clamp01(vfloat2 a, vfloat2 b) {
     asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1] clamp" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
-__device__ __forceinline__ void qr_pair(QrSums& s, vfloat2 t2, vfloat2 q2) {
+// the four sums take the terms of e with its clamped halves dp, dn
+__device__ __forceinline__ void qr_accumulate(QrSums& s, vfloat2 e, vfloat2 dp, vfloat2 dn) {
     const vfloat2 mh2 = {-0.5f, -0.5f};
-    const vfloat2 e = t2 - q2;
-    const vfloat2 dp = pk_sub_clamp01(t2, q2), dn = pk_sub_clamp01(q2, t2);
     s.up = __builtin_elementwise_fma(dp, __builtin_elementwise_fma(mh2, dp, e), s.up);
     s.un = __builtin_elementwise_fma(dn, __builtin_elementwise_fma(mh2, dn, -e), s.un);
     s.dp += dp;
     s.dn += dn;
+}
+__device__ __forceinline__ void qr_pair(QrSums& s, vfloat2 t2, vfloat2 q2) {
+    qr_accumulate(s, t2 - q2, pk_sub_clamp01(t2, q2), pk_sub_clamp01(q2, t2));
 }
 // (li, gi) of lane i from the four sums: even targets in .x, odd ones in .y
 __device__ __forceinline__ void qr_finish(const QrSums& s, float qneg, float qpos, float& li, float& gi) {
@@ -582,16 +589,13 @@ __global__ __launch_bounds__(256) void qrdqn_fwd_group_kernel(
     float* __restrict__ buf, float* __restrict__ partials, int tau, int nstep, int B, int N, float gamma,
     float gamma_n, float tau_value, float scale, const ScanFold fold) {
     group_per_sample<G>(B, partials, fold, [&](long b, bool ok, int gl, int base) -> float {
-        float R = 0.f, w = 0.f, qi = 0.f, tgt = 0.f;
+        float w = 0.f, qi = 0.f, tgt = 0.f;
         if (ok) {
-            const long a = action[b], na = next_action[b];
-            const float dn = done[b], vgm = value_gamma ? value_gamma[b] : gamma_n;
-            w = weight ? weight[b] : 1.f;
-            R = nstep_return1(reward, B, nstep, gamma, b);
-            const float vg = vgm * (1.f - dn);
+            const SampleScalars s = load_sample(b, action, next_action, reward, done, weight, value_gamma, nstep, B, gamma, gamma_n);
+            w = s.w;
             if (gl < tau) {
-                qi = q[((size_t)b * N + a) * tau + gl];
-                tgt = fmaf(vg, next_q[((size_t)b * N + na) * tau + gl], R);
+                qi = q[((size_t)b * N + s.a) * tau + gl];
+                tgt = fmaf(s.vg, next_q[((size_t)b * N + s.na) * tau + gl], s.R);
             }
         }
         const float inv_tau = 1.f / (float)tau;
@@ -601,9 +605,7 @@ __global__ __launch_bounds__(256) void qrdqn_fwd_group_kernel(
         QrSums sm = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
         for (int j = 0; j < tau; j += 2) {
             const bool two = j + 1 < tau;
-            vfloat2 t2;
-            t2.x = __shfl(tgt, base + j, 64);
-            t2.y = __shfl(tgt, base + (two ? j + 1 : j), 64);
+            vfloat2 t2 = fetch_two_targets(tgt, base, j, two);
             if (!two) t2.y = qi;
             qr_pair(sm, t2, q2);
         }
@@ -615,6 +617,10 @@ __global__ __launch_bounds__(256) void qrdqn_fwd_group_kernel(
         return loss * w;
     });
 }
+
+// the operands of __builtin_amdgcn_global_load_lds (the rows of the two samples-per-wave kernels below come by LDS-DMA)
+typedef __attribute__((address_space(3))) void* lds_ptr;
+typedef const __attribute__((address_space(1))) void* gl_ptr;
 
 // Round 3, large batches: a wave takes SW CONSECUTIVE samples.  The group kernel above is a chain of dependent round trips
 // per sample (action -> row address -> row) with 64/G samples in flight per wave: at B = 262144, tau = 32 it ran 0.128 ms
@@ -634,20 +640,17 @@ __global__ __launch_bounds__(256, 4) void qrdqn_fwd_batch_kernel(
     float gamma_n, float tau_value, float scale, const ScanFold fold) {
     constexpr int SPW = 64 / G, NIT = SW / SPW, U = NIT < 4 ? NIT : 4;
     static_assert(SW % SPW == 0 && NIT % U == 0, "samples per wave");
-    __shared__ float red[4];
     // per wave, two buffers of U iterations: the q row elements (lane = element) and the next-q row elements, which become the
     // targets in place
     __shared__ __attribute__((aligned(16))) float rq[4][2][U][64], tg[4][2][U][64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, gl = lane % G, gs = lane / G;
     const long b0 = ((long)blockIdx.x * 4 + w) * SW;
-    // phase A (lanes >= SW repeat the first SW samples: harmless)
+    // phase A (lanes >= SW repeat the first SW samples: harmless); the index is clamped, every load is unconditional
     const long bown = b0 + lane % SW;
-    const long bl = bown < (long)B ? bown : (long)B - 1;
-    const long row_l = ((long)bl * N + action[bl]) * tau, rown_l = ((long)bl * N + next_action[bl]) * tau;   // element offsets
-    const float dn_l = done[bl], vgm_l = value_gamma ? value_gamma[bl] : gamma_n;
-    const float w_l = weight ? weight[bl] : 1.f;
-    const float R_l = nstep_return1(reward, B, nstep, gamma, bl);
-    const float vg_l = vgm_l * (1.f - dn_l);
+    const SampleScalars own = load_sample(bown < (long)B ? bown : (long)B - 1, action, next_action, reward, done, weight,
+                                          value_gamma, nstep, B, gamma, gamma_n);
+    const long row_l = (own.b * N + own.a) * tau, rown_l = (own.b * N + own.na) * tau;   // element offsets
+    const float w_l = own.w, R_l = own.R, vg_l = own.vg;
     const int glc = gl < tau ? gl : tau - 1;                  // clamped: the row loads are unconditional
     const float inv_tau = 1.f / (float)tau;
     const float qneg = fabsf(tau_value - 1.f), qpos = fabsf(tau_value);
@@ -658,8 +661,6 @@ __global__ __launch_bounds__(256, 4) void qrdqn_fwd_batch_kernel(
     // with four waves per SIMD to cover it -- the pair loops themselves measured at the VALU issue rate (31 us of the kernel's
     // 57 at B = 262144, tests/tools/r05_qrdqn_ablate.py), the rest was this.  (Prefetching into registers instead: the
     // compiler spilled the prefetched values to scratch, one vmcnt(0) each.)
-    typedef __attribute__((address_space(3))) void* lds_ptr;
-    typedef const __attribute__((address_space(1))) void* gl_ptr;
     auto rows = [&](int c, int pb) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -718,14 +719,7 @@ __global__ __launch_bounds__(256, 4) void qrdqn_fwd_batch_kernel(
             __builtin_amdgcn_sched_barrier(0);                // one sample's 32 target registers at a time (else: spills)
         }
     }
-    const bool own = lane < SW && bown < (long)B;
-    if (own) td_err[bown] = mine;
-    const float contrib = wave_sum(own ? mine * w_l : 0.f);
-    if (lane == 0) red[w] = contrib;
-    __syncthreads();
-    float tot = 0.f;
-    if (threadIdx.x == 0) tot = (red[0] + red[1]) + (red[2] + red[3]);
-    publish_sums<1, 256>(tot, partials, fold);
+    publish_owned_samples<SW>(lane, bown, w_l, mine, B, td_err, partials, fold);
 }
 
 // Round 5, large batches, tau a multiple of 4 (<= 64): FOUR quantiles per lane, a sample on G = 8 (tau <= 32) or 16 lanes,
@@ -738,7 +732,6 @@ __global__ __launch_bounds__(256, 4) void qrdqn_fwd_batch_kernel(
 // of an iteration is spread over four times the samples.  Per-term arithmetic: qr_pair.
 template <bool HI>
 __device__ __forceinline__ void qr_quad(QrSums& s, vfloat2 tp, vfloat2 q2) {
-    const vfloat2 mh2 = {-0.5f, -0.5f};
     const float t = HI ? tp.y : tp.x;
     const vfloat2 e = vfloat2{t, t} - q2;
     vfloat2 dp, dn;
@@ -749,10 +742,7 @@ __device__ __forceinline__ void qr_quad(QrSums& s, vfloat2 tp, vfloat2 q2) {
         asm("v_pk_add_f32 %0, %1, %2 op_sel_hi:[0,1] neg_lo:[0,1] neg_hi:[0,1] clamp" : "=v"(dp) : "v"(tp), "v"(q2));
         asm("v_pk_add_f32 %0, %1, %2 op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1] clamp" : "=v"(dn) : "v"(q2), "v"(tp));
     }
-    s.up = __builtin_elementwise_fma(dp, __builtin_elementwise_fma(mh2, dp, e), s.up);
-    s.un = __builtin_elementwise_fma(dn, __builtin_elementwise_fma(mh2, dn, -e), s.un);
-    s.dp += dp;
-    s.dn += dn;
+    qr_accumulate(s, e, dp, dn);
 }
 
 template <int G, int SW, bool FULL>
@@ -764,7 +754,6 @@ __global__ __launch_bounds__(256, 4) void qrdqn_fwd_quad_kernel(
     float gamma_n, float tau_value, float scale, const ScanFold fold) {
     constexpr int SPW = 64 / G, NIT = SW / SPW;
     static_assert(SW % SPW == 0 && SW <= 64 && G >= 8, "samples per wave");
-    __shared__ float red[4];
     // per wave, two buffers: the q rows (lane l's four quantiles in words 4l ..) and the next-q rows, which become the targets
     // in place (a sample's targets contiguous: G * 4 words)
     __shared__ __attribute__((aligned(16))) float rq[4][2][256], tg[4][2][256];
@@ -772,12 +761,10 @@ __global__ __launch_bounds__(256, 4) void qrdqn_fwd_quad_kernel(
     const long b0 = ((long)blockIdx.x * 4 + w) * SW;
     // phase A as qrdqn_fwd_batch_kernel: lane l holds the scalars of sample b0 + l (lanes >= SW repeat the first SW samples)
     const long bown = b0 + lane % SW;
-    const long bl = bown < (long)B ? bown : (long)B - 1;
-    const long row_l = ((long)bl * N + action[bl]) * tau, rown_l = ((long)bl * N + next_action[bl]) * tau;   // element offsets
-    const float dn_l = done[bl], vgm_l = value_gamma ? value_gamma[bl] : gamma_n;
-    const float w_l = weight ? weight[bl] : 1.f;
-    const float R_l = nstep_return1(reward, B, nstep, gamma, bl);
-    const float vg_l = vgm_l * (1.f - dn_l);
+    const SampleScalars own = load_sample(bown < (long)B ? bown : (long)B - 1, action, next_action, reward, done, weight,
+                                          value_gamma, nstep, B, gamma, gamma_n);
+    const long row_l = (own.b * N + own.a) * tau, rown_l = (own.b * N + own.na) * tau;   // element offsets
+    const float w_l = own.w, R_l = own.R, vg_l = own.vg;
     const int nq4 = tau >> 2;                                 // lanes of a group that hold quantiles
     const int glc = gl < nq4 ? gl : nq4 - 1;                  // clamped: the row loads are unconditional
     const float inv_tau = 1.f / (float)tau;
@@ -788,8 +775,6 @@ __global__ __launch_bounds__(256, 4) void qrdqn_fwd_quad_kernel(
     // front of every LDS read that may alias a DMA destination, so those rows are in fact awaited before the pair loops start;
     // with the LDS reads written in assembly and the buf store deferred past the wait -- vmcnt counts stores on this part -- the
     // overlap is real and the kernel takes the same 51 us: five to six waves per SIMD hide the round trip either way.)
-    typedef __attribute__((address_space(3))) void* lds_ptr;
-    typedef const __attribute__((address_space(1))) void* gl_ptr;
     auto rows = [&](int c, int pb) {
         const int sl = c * SPW + gs;                          // sample of this group, as a lane index of phase A
         __builtin_amdgcn_global_load_lds((gl_ptr)(q + __shfl(row_l, sl, 64) + 4 * glc), (lds_ptr)&rq[w][pb][0], 16, 0, 0);
@@ -854,17 +839,44 @@ __global__ __launch_bounds__(256, 4) void qrdqn_fwd_quad_kernel(
         const float theirs = __shfl(loss, (lane % SPW) * G + G - 1, 64);       // the group that holds my sample in this iteration
         if ((lane % SW) / SPW == c) mine = theirs * inv_tau;
     }
-    const bool own = lane < SW && bown < (long)B;
-    if (own) td_err[bown] = mine;
-    const float contrib = wave_sum(own ? mine * w_l : 0.f);
-    if (lane == 0) red[w] = contrib;
-    __syncthreads();
-    float tot = 0.f;
-    if (threadIdx.x == 0) tot = (red[0] + red[1]) + (red[2] + red[3]);
-    publish_sums<1, 256>(tot, partials, fold);
+    publish_owned_samples<SW>(lane, bown, w_l, mine, B, td_err, partials, fold);
 }
 
 inline int group_lanes(int n) { return n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : 64; }
+
+// The widths that have instantiations, of a lane group (G) and of the samples a wave walks (SW, tune key 24) alike: 8, 16, 32, 64.
+// f(width as a std::integral_constant) for the listed width that equals x, and its status; HPC_RLL_EUNSUPPORTED for any other x
+// (f is not called: nothing is launched).  with_bool: f(std::true_type / std::false_type) for a template flag (FULL, BNT).
+template <class F> int with_width(int x, F&& f) {
+    switch (x) {
+        case 8: return f(std::integral_constant<int, 8>{});
+        case 16: return f(std::integral_constant<int, 16>{});
+        case 32: return f(std::integral_constant<int, 32>{});
+        case 64: return f(std::integral_constant<int, 64>{});
+    }
+    return HPC_RLL_EUNSUPPORTED;
+}
+template <class F> int with_bool(bool x, F&& f) { return x ? f(std::true_type{}) : f(std::false_type{}); }
+// A samples-per-wave width the rule has settled: 1 (the per-sample kernels) or a listed width.  Asked BEFORE the fold is armed:
+// a refused call enqueues nothing, moves no record and writes no output.
+inline int check_sample_width(int sw) {
+    return sw == 1 ? HPC_RLL_OK : with_width(sw, [](auto) { return HPC_RLL_OK; });
+}
+
+// What the three forwards check before they launch, in the order tests/test_dist_td_cpu.py pins: the sizes (`sizes_ok`: the op's
+// own) and `loss` first; an empty batch clears `loss` and is done; then the remaining pointers (`rows_ok`: the op's own).
+// *go is set where the caller goes on to launch; otherwise the value returned is the status of the call.
+inline int forward_checks(bool sizes_ok, bool rows_ok, const int64_t* action, const int64_t* next_action, const float* reward,
+                          const float* done, float* loss, float* td_err, float* buf, float* partials, int nstep, int B, int N,
+                          hipStream_t st, bool* go) {
+    *go = false;
+    if (!sizes_ok || nstep < 0 || B < 0 || N <= 0 || !loss) return HPC_RLL_EINVAL;
+    if (B == 0) return (int)hipMemsetAsync(loss, 0, sizeof(float), st);
+    if (!rows_ok || !action || !next_action || (nstep && !reward) || !done || !td_err || !buf || !partials) return HPC_RLL_EINVAL;
+    *go = true;
+    return HPC_RLL_OK;
+}
+inline float gamma_pow(float gamma, int nstep) { return (float)pow((double)gamma, (double)nstep); }
 
 // The dispatch records (hpc_rll_dist_last_config): one per op, noted next to every forward launch with the template arguments
 // OF THAT LAUNCH, so that a record names the instantiation that ran, not a second evaluation of the rule.  G = lanes that hold
@@ -877,7 +889,10 @@ void dist_note(int op, int family, int g, int sw, bool full, bool bnt, int grid,
 
 }  // namespace
 
-int g_sample_batch = 0;   // hpc_rll_tune_set key 24: samples per wave of the large-batch QR-DQN forward (0 = by batch size, 1 = off)
+// hpc_rll_tune_set key 24: samples per wave of the large-batch C51 and QR-DQN forwards (0 = by batch size, 1 = off, else 8 / 16 /
+// 32 / 64: hpc_rll_tune_set takes no other value, and a width without a kernel that the rules below leave above 1 is refused
+// with HPC_RLL_EUNSUPPORTED all the same)
+int g_sample_batch = 0;
 }  // namespace hpc_rll
 
 using namespace hpc_rll;
@@ -887,46 +902,39 @@ extern "C" int hpc_rll_dist_nstep_td_forward(const float* dist, const float* nex
                                              const float* weight, float* loss, float* td_err, float* buf,
                                              float* partials, int nstep, int B, int N, int n_atom, float gamma,
                                              float v_min, float v_max, float scale, void* stream) {
-    if (nstep < 0 || B < 0 || N <= 0 || n_atom < 2 || !loss) return HPC_RLL_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (B == 0) return (int)hipMemsetAsync(loss, 0, sizeof(float), st);
-    if (!dist || !next_n_dist || !action || !next_n_action || (nstep && !reward) || !done || !td_err || !buf ||
-        !partials)
-        return HPC_RLL_EINVAL;
+    bool go;
+    int rc = forward_checks(n_atom >= 2, dist && next_n_dist, action, next_n_action, reward, done, loss, td_err, buf, partials,
+                            nstep, B, N, st, &go);
+    if (!go) return rc;
     // large batches: SW samples per wave (dist_nstep_fwd_batch_kernel); widths from tests/tools/r03_batch_probe.py
     int sw = g_sample_batch;
     if (sw == 0) sw = B >= 262144 ? 16 : B >= 16384 ? 8 : 1;
     if (n_atom > 64) sw = 1;
+    if ((rc = check_sample_width(sw))) return rc;
     const int blocks = sw > 1 ? (int)(((long)B + 4 * sw - 1) / (4 * sw)) : (B + 3) / 4;
     // delta_z is a python double in the oracle, rounded to fp32 when it meets the fp32 tensor
     const float dz = (float)(((double)v_max - (double)v_min) / (double)(n_atom - 1));
     const float inv_dz = (float)(1.0 / (double)dz);            // the correctly rounded reciprocal (c51_project_scan)
-    const ScanFold fold = make_fold(st, 1, &scale, loss, blocks);
-    const float gamma_n = (float)pow((double)gamma, (double)nstep);
-    if (sw > 1) {
-#define HPC_RLL_C51_B(SW_)                                                                                            \
-        if (sw == SW_) {                                                                                              \
-            hipLaunchKernelGGL(dist_nstep_fwd_batch_kernel<SW_>, dim3(blocks), dim3(256), 0, st, dist, next_n_dist,    \
-                               action, next_n_action, reward, done, weight, td_err, buf, partials, nstep, B, N, n_atom, \
-                               gamma, gamma_n, v_min, v_max, dz, inv_dz, scale, fold);                                 \
-            dist_note(HPC_RLL_DIST_OP_C51, HPC_RLL_DIST_FAMILY_BATCH, 64, SW_, false, false, blocks, fold);            \
-        }
-        HPC_RLL_C51_B(8) HPC_RLL_C51_B(16) HPC_RLL_C51_B(32) HPC_RLL_C51_B(64)
-#undef HPC_RLL_C51_B
-    } else if (n_atom <= 64) {
-        hipLaunchKernelGGL(dist_nstep_fwd64_kernel<1>, dim3(blocks), dim3(256), 0, st, dist, next_n_dist, action,
-                           next_n_action, reward, done, weight, td_err, buf, partials, nstep, B, N, n_atom, gamma, gamma_n,
-                           v_min, v_max, dz, scale, fold);
-        dist_note(HPC_RLL_DIST_OP_C51, HPC_RLL_DIST_FAMILY_WAVE64, 64, 0, false, false, blocks, fold);
-    } else {
-        hipLaunchKernelGGL(dist_nstep_fwd_kernel, dim3(blocks), dim3(256), 0, st, dist, next_n_dist, action,
-                           next_n_action, reward, done, weight, td_err, buf, partials, nstep, B, N, n_atom, gamma, gamma_n,
-                           v_min, v_max, dz, scale, fold);
-        dist_note(HPC_RLL_DIST_OP_C51, HPC_RLL_DIST_FAMILY_GENERAL, 64, 0, false, false, blocks, fold);
-    }
-    const int rc = last_error();
-    if (rc || fold.out) return rc;
-    return finalize_sums(partials, blocks, 1, &scale, loss, st);
+    const float gamma_n = gamma_pow(gamma, nstep);
+    return launch_folded(blocks, 1, &scale, loss, partials, st, [&](unsigned grid, const ScanFold& fold) {
+        if (sw > 1)
+            return with_width(sw, [&](auto SW_) {
+                constexpr int SW = SW_;
+                hipLaunchKernelGGL(dist_nstep_fwd_batch_kernel<SW>, dim3(grid), dim3(256), 0, st, dist, next_n_dist, action,
+                                   next_n_action, reward, done, weight, td_err, buf, partials, nstep, B, N, n_atom, gamma,
+                                   gamma_n, v_min, v_max, dz, inv_dz, scale, fold);
+                dist_note(HPC_RLL_DIST_OP_C51, HPC_RLL_DIST_FAMILY_BATCH, 64, SW, false, false, blocks, fold);
+                return last_error();
+            });
+        const bool wave64 = n_atom <= 64;
+        hipLaunchKernelGGL(wave64 ? dist_nstep_fwd64_kernel : dist_nstep_fwd_kernel, dim3(grid), dim3(256), 0, st, dist,
+                           next_n_dist, action, next_n_action, reward, done, weight, td_err, buf, partials, nstep, B, N, n_atom,
+                           gamma, gamma_n, v_min, v_max, dz, scale, fold);
+        dist_note(HPC_RLL_DIST_OP_C51, wave64 ? HPC_RLL_DIST_FAMILY_WAVE64 : HPC_RLL_DIST_FAMILY_GENERAL, 64, 0, false, false,
+                  blocks, fold);
+        return last_error();
+    });
 }
 
 extern "C" int hpc_rll_dist_nstep_td_backward(const float* grad_loss, const float* buf, const int64_t* action,
@@ -942,42 +950,32 @@ int iqn_forward_impl(const float* q, const float* next_n_q, const int64_t* actio
                      const float* reward, const float* done, const float* replay_quantiles, const float* weight,
                      const float* value_gamma, float* loss, float* td_err, float* buf, float* partials, int tau,
                      int tau_prime, int nstep, int B, int N, float gamma, float kappa, float scale, bool bnt, void* stream) {
-    if (tau <= 0 || tau_prime <= 0 || nstep < 0 || B < 0 || N <= 0 || !loss || !(kappa > 0.f)) return HPC_RLL_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (B == 0) return (int)hipMemsetAsync(loss, 0, sizeof(float), st);
-    if (!q || !next_n_q || !action || !next_n_action || (nstep && !reward) || !done || !replay_quantiles || !td_err ||
-        !buf || !partials)
-        return HPC_RLL_EINVAL;
+    bool go;
+    const int rc = forward_checks(tau > 0 && tau_prime > 0 && kappa > 0.f, q && next_n_q && replay_quantiles, action,
+                                  next_n_action, reward, done, loss, td_err, buf, partials, nstep, B, N, st, &go);
+    if (!go) return rc;
     int blocks = (B + 3) / 4;
-    const float gamma_n = (float)pow((double)gamma, (double)nstep);
+    const float gamma_n = gamma_pow(gamma, nstep);
     const int gmax = tau > tau_prime ? tau : tau_prime;
     if (gmax <= 64) blocks = (B + 4 * (64 / group_lanes(gmax)) - 1) / (4 * (64 / group_lanes(gmax)));
-    const ScanFold fold = make_fold(st, 1, &scale, loss, blocks);
-    if (gmax <= 64) {
-        const int G = group_lanes(gmax);
-#define HPC_RLL_IQN_G(G_)                                                                                               \
-        if (G == G_) {                                                                                                  \
-            if (bnt)                                                                                                    \
-                hipLaunchKernelGGL((iqn_fwd_group_kernel<G_, true>), dim3(blocks), dim3(256), 0, st, q, next_n_q, action, \
-                                   next_n_action, reward, done, replay_quantiles, weight, value_gamma, td_err, buf,     \
-                                   partials, tau, tau_prime, nstep, B, N, gamma, gamma_n, kappa, scale, fold);          \
-            else                                                                                                        \
-                hipLaunchKernelGGL((iqn_fwd_group_kernel<G_, false>), dim3(blocks), dim3(256), 0, st, q, next_n_q, action, \
-                                   next_n_action, reward, done, replay_quantiles, weight, value_gamma, td_err, buf,     \
-                                   partials, tau, tau_prime, nstep, B, N, gamma, gamma_n, kappa, scale, fold);          \
-            dist_note(HPC_RLL_DIST_OP_IQN, HPC_RLL_DIST_FAMILY_GROUP, G_, 0, false, bnt, blocks, fold);                 \
-        }
-        HPC_RLL_IQN_G(8) HPC_RLL_IQN_G(16) HPC_RLL_IQN_G(32) HPC_RLL_IQN_G(64)
-#undef HPC_RLL_IQN_G
-    } else {
-        hipLaunchKernelGGL(iqn_fwd_kernel, dim3(blocks), dim3(256), 0, st, q, next_n_q, action, next_n_action, reward,
-                           done, replay_quantiles, weight, value_gamma, td_err, buf, partials, tau, tau_prime, nstep, B,
-                           N, gamma, gamma_n, kappa, scale, fold, bnt ? 1 : 0);
+    return launch_folded(blocks, 1, &scale, loss, partials, st, [&](unsigned grid, const ScanFold& fold) {
+        if (gmax <= 64)
+            return with_width(group_lanes(gmax), [&](auto G_) { return with_bool(bnt, [&](auto BNT_) {
+                constexpr int G = G_;
+                constexpr bool BNT = BNT_;
+                hipLaunchKernelGGL((iqn_fwd_group_kernel<G, BNT>), dim3(grid), dim3(256), 0, st, q, next_n_q, action,
+                                   next_n_action, reward, done, replay_quantiles, weight, value_gamma, td_err, buf, partials,
+                                   tau, tau_prime, nstep, B, N, gamma, gamma_n, kappa, scale, fold);
+                dist_note(HPC_RLL_DIST_OP_IQN, HPC_RLL_DIST_FAMILY_GROUP, G, 0, false, BNT, blocks, fold);
+                return last_error();
+            }); });
+        hipLaunchKernelGGL(iqn_fwd_kernel, dim3(grid), dim3(256), 0, st, q, next_n_q, action, next_n_action, reward, done,
+                           replay_quantiles, weight, value_gamma, td_err, buf, partials, tau, tau_prime, nstep, B, N, gamma,
+                           gamma_n, kappa, scale, fold, bnt ? 1 : 0);
         dist_note(HPC_RLL_DIST_OP_IQN, HPC_RLL_DIST_FAMILY_WAVE, 64, 0, false, bnt, blocks, fold);
-    }
-    const int rc = last_error();
-    if (rc || fold.out) return rc;
-    return finalize_sums(partials, blocks, 1, &scale, loss, st);
+        return last_error();
+    });
 }
 } }  // namespace hpc_rll::(anonymous)
 
@@ -1029,13 +1027,13 @@ extern "C" int hpc_rll_qrdqn_nstep_td_forward(const float* q, const float* next_
                                               const float* weight, const float* value_gamma, float* loss,
                                               float* td_err, float* buf, float* partials, int tau, int nstep, int B,
                                               int N, float gamma, float tau_value, float scale, void* stream) {
-    if (tau <= 0 || nstep < 0 || B < 0 || N <= 0 || !loss) return HPC_RLL_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (B == 0) return (int)hipMemsetAsync(loss, 0, sizeof(float), st);
-    if (!q || !next_n_q || !action || !next_n_action || (nstep && !reward) || !done || !td_err || !buf || !partials)
-        return HPC_RLL_EINVAL;
+    bool go;
+    int rc = forward_checks(tau > 0, q && next_n_q, action, next_n_action, reward, done, loss, td_err, buf, partials, nstep, B, N,
+                            st, &go);
+    if (!go) return rc;
     int blocks = (B + 3) / 4;
-    const float gamma_n = (float)pow((double)gamma, (double)nstep);
+    const float gamma_n = gamma_pow(gamma, nstep);
     if (tau <= 64) blocks = (B + 4 * (64 / group_lanes(tau)) - 1) / (4 * (64 / group_lanes(tau)));
     // large batches: SW consecutive samples per wave (qrdqn_fwd_batch_kernel); widths from tests/tools/r03_batch_probe.py
     int sw = g_sample_batch;
@@ -1050,64 +1048,41 @@ extern "C" int hpc_rll_qrdqn_nstep_td_forward(const float* q, const float* next_
         if (sw < 64 / G) sw = 64 / G;
         blocks = (int)(((long)B + 4 * sw - 1) / (4 * sw));
     }
-    const ScanFold fold = make_fold(st, 1, &scale, loss, blocks);
-    if (quad) {
-        const int G = tau <= 32 ? 8 : 16;
-#define HPC_RLL_QR_Q(G_, SW_)                                                                                         \
-        if (G == G_ && sw == SW_) {                                                                                   \
-            const bool full = tau == 4 * G_;                                                                          \
-            if (full)                                                                                                 \
-                hipLaunchKernelGGL((qrdqn_fwd_quad_kernel<G_, SW_, true>), dim3(blocks), dim3(256), 0, st, q, next_n_q, \
-                                   action, next_n_action, reward, done, weight, value_gamma, td_err, buf, partials, tau, \
-                                   nstep, B, N, gamma, gamma_n, tau_value, scale, fold);                              \
-            else                                                                                                      \
-                hipLaunchKernelGGL((qrdqn_fwd_quad_kernel<G_, SW_, false>), dim3(blocks), dim3(256), 0, st, q, next_n_q, \
-                                   action, next_n_action, reward, done, weight, value_gamma, td_err, buf, partials, tau, \
-                                   nstep, B, N, gamma, gamma_n, tau_value, scale, fold);                              \
-            dist_note(HPC_RLL_DIST_OP_QRDQN, HPC_RLL_DIST_FAMILY_QUAD, G_, SW_, full, false, blocks, fold);           \
-        }
-        HPC_RLL_QR_Q(8, 8) HPC_RLL_QR_Q(8, 16) HPC_RLL_QR_Q(8, 32) HPC_RLL_QR_Q(8, 64)
-        HPC_RLL_QR_Q(16, 8) HPC_RLL_QR_Q(16, 16) HPC_RLL_QR_Q(16, 32) HPC_RLL_QR_Q(16, 64)
-#undef HPC_RLL_QR_Q
-    } else if (sw > 1) {
-        const int G = group_lanes(tau);
-#define HPC_RLL_QR_B(G_, SW_)                                                                                         \
-        if (G == G_ && sw == SW_) {                                                                                   \
-            const bool full = tau == G_;                                                                              \
-            if (full)                                                                                                 \
-                hipLaunchKernelGGL((qrdqn_fwd_batch_kernel<G_, SW_, true>), dim3(blocks), dim3(256), 0, st, q, next_n_q, \
-                                   action, next_n_action, reward, done, weight, value_gamma, td_err, buf, partials, tau, \
-                                   nstep, B, N, gamma, gamma_n, tau_value, scale, fold);                              \
-            else                                                                                                      \
-                hipLaunchKernelGGL((qrdqn_fwd_batch_kernel<G_, SW_, false>), dim3(blocks), dim3(256), 0, st, q, next_n_q, \
-                                   action, next_n_action, reward, done, weight, value_gamma, td_err, buf, partials, tau, \
-                                   nstep, B, N, gamma, gamma_n, tau_value, scale, fold);                              \
-            dist_note(HPC_RLL_DIST_OP_QRDQN, HPC_RLL_DIST_FAMILY_BATCH, G_, SW_, full, false, blocks, fold);          \
-        }
-        HPC_RLL_QR_B(8, 8) HPC_RLL_QR_B(8, 16) HPC_RLL_QR_B(8, 32) HPC_RLL_QR_B(8, 64) HPC_RLL_QR_B(16, 8) HPC_RLL_QR_B(16, 16)
-        HPC_RLL_QR_B(16, 32) HPC_RLL_QR_B(16, 64) HPC_RLL_QR_B(32, 8) HPC_RLL_QR_B(32, 16) HPC_RLL_QR_B(32, 32) HPC_RLL_QR_B(32, 64)
-        HPC_RLL_QR_B(64, 8) HPC_RLL_QR_B(64, 16) HPC_RLL_QR_B(64, 32) HPC_RLL_QR_B(64, 64)
-#undef HPC_RLL_QR_B
-    } else if (tau <= 64) {
-        const int G = group_lanes(tau);
-#define HPC_RLL_QR_G(G_)                                                                                              \
-        if (G == G_) {                                                                                                \
-            hipLaunchKernelGGL(qrdqn_fwd_group_kernel<G_>, dim3(blocks), dim3(256), 0, st, q, next_n_q, action,        \
-                               next_n_action, reward, done, weight, value_gamma, td_err, buf, partials, tau, nstep, B, N, \
-                               gamma, gamma_n, tau_value, scale, fold);                                                \
-            dist_note(HPC_RLL_DIST_OP_QRDQN, HPC_RLL_DIST_FAMILY_GROUP, G_, 0, false, false, blocks, fold);            \
-        }
-        HPC_RLL_QR_G(8) HPC_RLL_QR_G(16) HPC_RLL_QR_G(32) HPC_RLL_QR_G(64)
-#undef HPC_RLL_QR_G
-    } else {
-        hipLaunchKernelGGL(qrdqn_fwd_kernel, dim3(blocks), dim3(256), 0, st, q, next_n_q, action, next_n_action, reward,
-                           done, weight, value_gamma, td_err, buf, partials, tau, nstep, B, N, gamma, gamma_n, tau_value,
-                           scale, fold);
+    if ((rc = check_sample_width(sw))) return rc;
+    return launch_folded(blocks, 1, &scale, loss, partials, st, [&](unsigned grid, const ScanFold& fold) {
+        // the four kernels take the same arguments
+        auto run = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, q, next_n_q, action, next_n_action, reward, done, weight,
+                               value_gamma, td_err, buf, partials, tau, nstep, B, N, gamma, gamma_n, tau_value, scale, fold);
+            return last_error();
+        };
+        if (quad)
+            return with_bool(tau <= 32, [&](auto NARROW_) { return with_width(sw, [&](auto SW_) {
+                constexpr int G = decltype(NARROW_)::value ? 8 : 16, SW = SW_;
+                return with_bool(tau == 4 * G, [&](auto FULL_) {
+                    constexpr bool FULL = FULL_;
+                    dist_note(HPC_RLL_DIST_OP_QRDQN, HPC_RLL_DIST_FAMILY_QUAD, G, SW, FULL, false, blocks, fold);
+                    return run(qrdqn_fwd_quad_kernel<G, SW, FULL>);
+                });
+            }); });
+        if (sw > 1)
+            return with_width(group_lanes(tau), [&](auto G_) { return with_width(sw, [&](auto SW_) {
+                constexpr int G = G_, SW = SW_;
+                return with_bool(tau == G, [&](auto FULL_) {
+                    constexpr bool FULL = FULL_;
+                    dist_note(HPC_RLL_DIST_OP_QRDQN, HPC_RLL_DIST_FAMILY_BATCH, G, SW, FULL, false, blocks, fold);
+                    return run(qrdqn_fwd_batch_kernel<G, SW, FULL>);
+                });
+            }); });
+        if (tau <= 64)
+            return with_width(group_lanes(tau), [&](auto G_) {
+                constexpr int G = G_;
+                dist_note(HPC_RLL_DIST_OP_QRDQN, HPC_RLL_DIST_FAMILY_GROUP, G, 0, false, false, blocks, fold);
+                return run(qrdqn_fwd_group_kernel<G>);
+            });
         dist_note(HPC_RLL_DIST_OP_QRDQN, HPC_RLL_DIST_FAMILY_WAVE, 64, 0, false, false, blocks, fold);
-    }
-    const int rc = last_error();
-    if (rc || fold.out) return rc;
-    return finalize_sums(partials, blocks, 1, &scale, loss, st);
+        return run(qrdqn_fwd_kernel);
+    });
 }
 
 extern "C" int hpc_rll_qrdqn_nstep_td_backward(const float* grad_loss, const float* buf, const int64_t* action,

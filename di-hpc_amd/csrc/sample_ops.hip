@@ -45,13 +45,11 @@ inline int launch_sample(const Op& op, long n, float* partials, int nacc, const 
     const long nt = wide ? 1024 : 256;
     long blocks = (n + nt - 1) / nt;
     if (blocks > kFoldMaxGrid) blocks = kFoldMaxGrid;
-    const ScanFold fold = make_fold(st, nacc, scale, out, blocks);
-    if (wide) hipLaunchKernelGGL((sample_kernel<Op, 1024>), dim3((unsigned)blocks), dim3(1024), 0, st, op, n, partials, fold);
-    else hipLaunchKernelGGL((sample_kernel<Op, 256>), dim3((unsigned)blocks), dim3(256), 0, st, op, n, partials, fold);
-    const hipError_t e = hipGetLastError();
-    const int rc = e == hipSuccess ? HPC_RLL_OK : (int)e;
-    if (rc || fold.out) return rc;
-    return finalize_sums(partials, (int)blocks, nacc, scale, out, st);
+    return launch_folded(blocks, nacc, scale, out, partials, st, [&](unsigned grid, const ScanFold& fold) {
+        if (wide) hipLaunchKernelGGL((sample_kernel<Op, 1024>), dim3(grid), dim3(1024), 0, st, op, n, partials, fold);
+        else hipLaunchKernelGGL((sample_kernel<Op, 256>), dim3(grid), dim3(256), 0, st, op, n, partials, fold);
+        return last_error();
+    });
 }
 
 // ---------------------------------------------------------------------------------------------- q n-step TD

@@ -29,7 +29,7 @@ const TuneKey kKeys[] = {
     {18, &g_scatter_npb, 0, 64, 0, "channels per workgroup of the LDS-staged scatter kernel (a multiple of 4; 0 = by LDS budget)"},
     {21, &g_scan_fold, 0, 1, 0, "loss finalisation folded into the last workgroup of the launch (grids up to 512); 0 = separate finalize launch"},
     {22, &g_split_algo, 0, 1, 0, "group split of the padding ops: 0 = runs of equal keys, 1 = the element-level DP (host; small n)"},
-    {24, &g_sample_batch, 0, 64, 0, "samples per wave of the large-batch C51 / QR-DQN forwards: 0 by batch size, 1 off, 8 / 16 / 32 / 64"},
+    {24, &g_sample_batch, 0, 64, 0, "samples per wave of the large-batch C51 / QR-DQN forwards: 0 by batch size, 1 off, 8 / 16 / 32 / 64 (the widths with kernels; any other value: HPC_RLL_EINVAL)"},
     {25, &g_gemm_dma, 0, 2, 0, "LDS-DMA staged GEMM tiles: 1 all forms, 2 the 256x256 NT tile only, 0 register staging everywhere"},
     {26, &g_lstm_block, 0, 255, 1 | 8 | 128, "large-batch LSTM row-block kernels: bit 0 forward, bit 3 backward, bit 7 fence-free forward exchanges (default 9)"},
     {27, &g_lstm_block_skew, 0, 200, 0, "microseconds between the starts of consecutive row blocks of those kernels (default 10)"},

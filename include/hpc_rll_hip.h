@@ -201,7 +201,9 @@ int hpc_rll_categorical_last_config(int direction, int* out);
  *   key 18  channels per workgroup of that kernel (a multiple of 4 up to 64; 0, default = by LDS budget)
  *   key 21  loss finalisation folded into the last workgroup of the launch (grids up to 512): 1 (default) / 0 = finalize launch
  *   key 22  group split of the padding ops: 0 (default) = runs of equal keys / 1 = the element-level DP
- *   key 24  samples per wave of the large-batch C51 / QR-DQN forwards: 0 (default) by batch size, 1 off, 8 / 16 / 32 / 64
+ *   key 24  samples per wave of the large-batch C51 / QR-DQN forwards: 0 (default) by batch size, 1 off, 8 / 16 / 32 / 64.  Those
+ *           four are the widths with kernels: hpc_rll_tune_set answers HPC_RLL_EINVAL for any other value, and the forwards
+ *           return HPC_RLL_EUNSUPPORTED, before anything is enqueued, for a width without a kernel that their rule leaves above 1
  *   key 25  LDS-DMA staged GEMM tiles: 1 (default) all forms / 2 the 256x256 NT tile only / 0 register staging
  *   key 26  large-batch LSTM (B >= 4096, B % 256 == 0, 768 <= H <= 1024, H % 64 == 0) row-block kernels, a bit mask: bit 0 the
  *           persistent forward, bit 3 the persistent backward (H % 128 == 0), bit 7 fence-free forward exchanges; default 9;

@@ -31,6 +31,10 @@ is exact in both precisions: supports whose delta_z is a power of two, gamma in 
 ``done`` from the sets above (``C51_GRIDS``).  There no sample is left out.  On the usual grid (51 atoms on [-10, 10], gamma =
 0.95) the reference is the fp32 oracle under the rule of test_dntd_oracle_reference_shape, with at most 1 % of the samples left out.
 
+A width without a kernel.  ``hpc_rll_tune_set`` takes only 0, 1 and the four widths for key 24; behind it the dispatchers refuse
+any other width the rule leaves above 1 with HPC_RLL_EUNSUPPORTED before anything is enqueued
+(test_a_width_without_an_instantiation_is_refused writes the variable behind the key to get there).
+
 Not covered, and why: 64-bit element offsets (B * N * n_atom >= 2^31) and the by-batch-size thresholds themselves (B >= 16384 /
 32768 / 262144) need batches far outside a test of seconds; tests/test_full_size_gpu.py and the large-batch tests of
 tests/test_losses_gpu.py and tests/test_fuzz_gpu.py stay the only cover of those.
@@ -679,6 +683,75 @@ def test_iqn_group_kernel_both_layouts(tau, taup, G, N, off_grad):
 @pytest.mark.parametrize("tau,taup,N,off_grad", [(65, 10, 4, 0), (10, 70, None, 0), (66, 67, 4, 1)])
 def test_iqn_wave_kernel_both_layouts(tau, taup, N, off_grad):
     iqn_case(tau, taup, WAVE, 64, tau + taup, N, off_grad)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# tune key 24 at a width that has no instantiation
+# ---------------------------------------------------------------------------------------------------------------------
+EINVAL, EUNSUPPORTED = -1, -3              # HPC_RLL_EINVAL, HPC_RLL_EUNSUPPORTED
+
+
+@contextlib.contextmanager
+def width_behind_key_24(sw):
+    """``hpc_rll_tune_set(24, sw)`` itself answers HPC_RLL_EINVAL for a width without kernels (asserted here), so the dispatchers'
+    own refusal is reached by writing the variable behind the key, the library's ``hpc_rll::g_sample_batch``; 0 in ``finally``."""
+    import cabi
+    var = ctypes.c_int.in_dll(cabi.lib, "_ZN7hpc_rll14g_sample_batchE")
+    try:
+        assert cabi.lib.hpc_rll_tune_set(24, sw) == EINVAL and var.value == 0
+        var.value = sw
+        yield
+    finally:
+        var.value = 0
+        assert cabi.lib.hpc_rll_tune_set(24, 0) == 0
+
+
+def refused(fn, ops, names, out, scalars, sw, what):
+    """With the width ``sw`` behind tune key 24 the forward returns HPC_RLL_EUNSUPPORTED and has done nothing: no record moved, the
+    NaN prefill of loss, td_err and buf is in place, every guard band is intact and the operands are unchanged."""
+    import cabi
+    what = f"{what} key 24 = {sw}"
+    before = [last(o) for o in (C51, IQN, QR)]
+    with width_behind_key_24(sw):
+        status = getattr(cabi.lib, fn)(*[ops.ptr(n) for n in names], *out.ptrs(), *scalars, cabi.stream_ptr(DEV))
+    torch.cuda.synchronize()
+    assert status == EUNSUPPORTED, (what, "returned", status)
+    assert [last(o) for o in (C51, IQN, QR)] == before, (what, "a refused call moved a dispatch record")
+    for name in ("loss", "td", "buf"):
+        getattr(out, name).assert_untouched(f"{what}: {name}")
+    for name in ("loss", "td", "buf", "partials"):
+        getattr(out, name).check(f"{what}: {name}")
+    ops.check(what)
+
+
+def test_a_width_without_an_instantiation_is_refused():
+    """The samples-per-wave kernels exist at 8 / 16 / 32 / 64.  hpc_rll_tune_set refuses any other width for key 24; should the
+    variable behind the key hold one all the same (2, 12, 63 here), a forward whose rule leaves it above 1 refuses before anything
+    is enqueued -- it used to launch nothing and return 0 with loss unwritten --, and where the rule itself brings the width down
+    to 1 (n_atom > 64, or a width below 64 / G) the per-sample kernel runs as always."""
+    B, N = 9, 3
+    for sw in (2, 12, 63):
+        inp = C51Inputs(2400 + sw, B, N, 51, *C51_GRIDS[51], 0.5, 3, "set", True)
+        refused("hpc_rll_dist_nstep_td_forward", inp.place(), C51_NAMES, Outputs(B, 51),
+                [inp.nstep, B, N, 51, inp.gamma, inp.v_min, inp.v_max, 1.0 / B], sw, "c51 n_atom=51")
+        inp = C51Inputs(2465 + sw, B, N, 65, *C51_GRIDS[65], 0.5, 3, "set", True)
+        with width_behind_key_24(sw):                               # n_atom > 64: the width is 1, GENERAL
+            res = forward("hpc_rll_dist_nstep_td_forward", C51, inp.place(), C51_NAMES, Outputs(B, 65),
+                          [inp.nstep, B, N, 65, inp.gamma, inp.v_min, inp.v_max, 1.0 / B], want(GENERAL, 64, 0, 0, 0, B, 4),
+                          f"c51 n_atom=65 key 24 = {sw}")
+        against_oracle(C51, GENERAL, inp.oracle(), res, f"GENERAL n_atom=65 B={B} key 24 = {sw}")
+        inp = QrInputs(2440 + sw, B, N, 40, 3, "set", True, True)
+        refused("hpc_rll_qrdqn_nstep_td_forward", inp.place(), QR_NAMES, Outputs(B, 40),
+                [40, inp.nstep, B, N, GAMMA, 40.0, 1.0 / B], sw, "qrdqn tau=40")
+        inp = QrInputs(2408 + sw, B, N, 8, 3, "set", True, True)
+        if sw == 2:                                                 # below 64 / G = 8: the width is 1, GROUP
+            with width_behind_key_24(sw):
+                res = forward("hpc_rll_qrdqn_nstep_td_forward", QR, inp.place(), QR_NAMES, Outputs(B, 8),
+                              [8, inp.nstep, B, N, GAMMA, 8.0, 1.0 / B], qr_group_want(8, B), f"qrdqn tau=8 key 24 = {sw}")
+            against_oracle(QR, GROUP, inp.oracle(), res, f"GROUP tau=8 B={B} key 24 = {sw}")
+        else:
+            refused("hpc_rll_qrdqn_nstep_td_forward", inp.place(), QR_NAMES, Outputs(B, 8),
+                    [8, inp.nstep, B, N, GAMMA, 8.0, 1.0 / B], sw, "qrdqn tau=8")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
