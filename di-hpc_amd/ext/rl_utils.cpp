@@ -4,7 +4,7 @@
 //   * the reference's L2 functions `XxxForward(inputs, outputs, scalars...)` / `XxxBackward(inputs, outputs)`
 //     (declared in include/hpc/rll/cuda/rl_utils/entry.h:10-165) -- validated, launched on torch's current stream;
 //   * fused autograd ops (`gae`, `td_lambda`, `vtrace`, `upgo`, `upgo_masked`, `ppo`, `ppo_continuous`, `vtrace_continuous`, `retrace_loss`, `acer_policy_loss`, `coma`, `r2d2_td`, `sac_discrete`, `token_log_prob`, `grpo_policy_loss`, `token_log_prob_entropy`, `lm_ppo_loss`, `q_nstep_td`, `dist_nstep_td`, `iqn_nstep_td`,
-//     `qrdqn_nstep_td`) -- torch::autograd::Function nodes that allocate outputs, launch and register backward in ONE
+//     `qrdqn_nstep_td`, `fqf_fractions`, `fqf_nstep_td`, `fqf_fraction_loss`; `fqf_q_value` is a plain function) -- torch::autograd::Function nodes that allocate outputs, launch and register backward in ONE
 //     pybind call; these are what hpc_rll.rl_utils.* modules use.
 // Host-only C++: every kernel lives behind the C ABI of libhpc_rll_hip.so (include/hpc_rll_hip.h).
 #include "common.hpp"
@@ -1964,6 +1964,154 @@ struct QrFn : public ag::Function<QrFn> {
     }
 };
 
+// =========================================================================================================== FQF
+// (no reference counterpart; DI-engine's fqf_nstep_td_error / fqf_calculate_fraction_loss and the fraction proposal of FQFHead)
+struct FqfFractionsFn : public ag::Function<FqfFractionsFn> {
+    static ag::tensor_list forward(ag::AutogradContext* ctx, const Tensor& logits) {
+        req(logits, "logits");
+        TORCH_CHECK(logits.dim() == 2 && logits.size(1) >= 1, "logits: expected (B,K) with K >= 1, got ", logits.sizes());
+        const int64_t B = logits.size(0), K = logits.size(1);
+        const at::Device dev = logits.device();
+        c10::DeviceGuard g(dev);
+        Tensor quantiles = new_f32({B, K + 1}, dev), hats = new_f32({B, K}, dev), ent = new_f32({B, 1}, dev);
+        check(hpc_rll_fqf_fractions_forward(fptr(logits), fmut(quantiles), fmut(hats), fmut(ent), to_int(B, "B"), to_int(K, "K"),
+                                            stream_of(dev)),
+              "hpc_rll_fqf_fractions_forward (1 <= K <= 1024)");
+        ctx->save_for_backward({logits, ent});
+        ctx->mark_non_differentiable({hats});
+        return {quantiles, hats, ent};
+    }
+    static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
+        ag::tensor_list out(1);
+        if (!ctx->needs_input_grad(0)) return out;
+        const auto saved = ctx->get_saved_variables();
+        const Tensor &logits = saved[0], &ent = saved[1];
+        const at::Device dev = logits.device();
+        c10::DeviceGuard g(dev);
+        const int64_t B = logits.size(0), K = logits.size(1);
+        // either upstream gradient may be absent: it counts as zero
+        Tensor gq = grads[0].defined() ? req(grads[0].contiguous(), "grad_quantiles", dev, {B, K + 1}) : Tensor();
+        Tensor gh = grads[2].defined() ? req(grads[2].contiguous(), "grad_entropies", dev, {B, 1}) : Tensor();
+        Tensor gl = new_f32({B, K}, dev);
+        check(hpc_rll_fqf_fractions_backward(fptr(logits), fptr(ent), fptr(gq), fptr(gh), fmut(gl), (int)B, (int)K, stream_of(dev)),
+              "hpc_rll_fqf_fractions_backward");
+        out[0] = gl;
+        return out;
+    }
+};
+
+struct FqfDims { int64_t B, K, Kp, N, nstep; at::Device dev; };
+FqfDims fqf_td_check(const Tensor& q, const Tensor& nq, const Tensor& action, const Tensor& naction, const Tensor& reward,
+                     const Tensor& done, const Tensor& qh, const OptTensor& weight, const OptTensor& vg) {
+    req(q, "q");
+    TORCH_CHECK(q.dim() == 3 && q.size(1) >= 1 && q.size(2) >= 1, "q: expected (B,K,N), got ", q.sizes());
+    const int64_t B = q.size(0), K = q.size(1), N = q.size(2);
+    const at::Device dev = q.device();
+    req(nq, "next_n_q", dev);
+    TORCH_CHECK(nq.dim() == 3 && nq.size(0) == B && nq.size(1) >= 1 && nq.size(2) == N, "next_n_q: shape ", nq.sizes(),
+                ", expected (", B, ",K',", N, ")");
+    req(action, "action", dev, {B}, at::kLong);
+    req(naction, "next_n_action", dev, {B}, at::kLong);
+    const int64_t nstep = check_nstep_reward(reward, B, dev);
+    req(done, "done", dev, {B});
+    req(qh, "quantiles_hats", dev, {B, K});
+    req_opt(weight, "weight", dev, {B});
+    req_opt(vg, "value_gamma", dev, {B});
+    return {B, K, nq.size(1), N, nstep, dev};
+}
+
+struct FqfTdFn : public ag::Function<FqfTdFn> {
+    static ag::tensor_list forward(ag::AutogradContext* ctx, const Tensor& q, const Tensor& nq, const Tensor& action,
+                                   const Tensor& naction, const Tensor& reward, const Tensor& done, const Tensor& qh,
+                                   const OptTensor& weight, const OptTensor& vg, double gamma, double kappa,
+                                   std::optional<double> scale) {
+        const FqfDims d = fqf_td_check(q, nq, action, naction, reward, done, qh, weight, vg);
+        TORCH_CHECK(kappa > 0.0, "kappa: expected > 0, got ", kappa);
+        c10::DeviceGuard g(d.dev);
+        Tensor loss = new_f32({1}, d.dev), td_err = new_f32({d.B}, d.dev), grad_buf = new_f32({d.B, d.K}, d.dev);
+        Tensor partials = new_f32({hpc_rll_partials_floats(d.B)}, d.dev);
+        check(hpc_rll_fqf_nstep_td_forward(fptr(q), fptr(nq), iptr(action), iptr(naction), fptr(reward), fptr(done), fptr(qh),
+                                           fptr(weight), fptr(vg), fmut(loss), fmut(td_err), fmut(grad_buf), fmut(partials),
+                                           to_int(d.K, "K"), to_int(d.Kp, "K'"), to_int(d.nstep, "nstep"), to_int(d.B, "B"),
+                                           to_int(d.N, "N"), (float)gamma, (float)kappa, loss_scale(scale, d.B), stream_of(d.dev)),
+              "hpc_rll_fqf_nstep_td_forward");
+        ctx->save_for_backward({grad_buf, action});
+        ctx->saved_data["N"] = d.N;
+        ctx->mark_non_differentiable({td_err});
+        return {loss, td_err};
+    }
+    static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
+        ag::tensor_list out(12);
+        if (!ctx->needs_input_grad(0)) return out;
+        const auto saved = ctx->get_saved_variables();
+        const Tensor &grad_buf = saved[0], &action = saved[1];
+        const at::Device dev = grad_buf.device();
+        c10::DeviceGuard g(dev);
+        const int64_t B = grad_buf.size(0), K = grad_buf.size(1), N = ctx->saved_data["N"].toInt();
+        Tensor gq = new_f32({B, K, N}, dev);
+        check(hpc_rll_fqf_nstep_td_backward(fptr(grad1(grads[0], dev, "grad_loss")), fptr(grad_buf), iptr(action), fmut(gq), (int)K,
+                                            (int)B, (int)N, stream_of(dev)),
+              "hpc_rll_fqf_nstep_td_backward");
+        out[0] = gq;
+        return out;
+    }
+};
+
+struct FqfFractionLossFn : public ag::Function<FqfFractionLossFn> {
+    static Tensor forward(ag::AutogradContext* ctx, const Tensor& q_tau_i, const Tensor& q_value, const Tensor& quantiles,
+                          const Tensor& actions, std::optional<double> scale) {
+        req(q_value, "q_value");
+        TORCH_CHECK(q_value.dim() == 3 && q_value.size(1) >= 1 && q_value.size(2) >= 1, "q_value: expected (B,K,N), got ",
+                    q_value.sizes());
+        const int64_t B = q_value.size(0), K = q_value.size(1), N = q_value.size(2);
+        const at::Device dev = q_value.device();
+        req(q_tau_i, "q_tau_i", dev, {B, K - 1, N});
+        req(quantiles, "quantiles", dev, {B, K + 1});
+        req(actions, "actions", dev, {B}, at::kLong);
+        c10::DeviceGuard gd(dev);
+        Tensor loss = new_f32({1}, dev), g = new_f32({B, K - 1}, dev), partials = new_f32({hpc_rll_partials_floats(B)}, dev);
+        const float sc = loss_scale(scale, B);
+        check(hpc_rll_fqf_fraction_loss_forward(fptr(q_tau_i), fptr(q_value), fptr(quantiles), iptr(actions), fmut(loss), fmut(g),
+                                                fmut(partials), to_int(K, "K"), to_int(B, "B"), to_int(N, "N"), sc, stream_of(dev)),
+              "hpc_rll_fqf_fraction_loss_forward");
+        ctx->save_for_backward({g});
+        ctx->saved_data["K"] = K;
+        ctx->saved_data["scale"] = (double)sc;
+        return loss;
+    }
+    static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
+        ag::tensor_list out(5);
+        if (!ctx->needs_input_grad(2)) return out;   // q_tau_i and q_value enter through g, a constant
+        const Tensor g = ctx->get_saved_variables()[0];
+        const at::Device dev = g.device();
+        c10::DeviceGuard gd(dev);
+        const int64_t B = g.size(0), K = ctx->saved_data["K"].toInt();
+        Tensor gq = new_f32({B, K + 1}, dev);
+        check(hpc_rll_fqf_fraction_loss_backward(fptr(grad1(grads[0], dev, "grad_loss")), fptr(g), fmut(gq), (int)K, (int)B,
+                                                 (float)ctx->saved_data["scale"].toDouble(), stream_of(dev)),
+              "hpc_rll_fqf_fraction_loss_backward");
+        out[2] = gq;
+        return out;
+    }
+};
+
+// logit (B,N) and, with return_action, its argmax (B,) int64 from the same launch; forward only
+std::tuple<Tensor, OptTensor> fqf_q_value(const Tensor& q, const Tensor& quantiles, bool return_action) {
+    req(q, "q");
+    TORCH_CHECK(q.dim() == 3 && q.size(1) >= 1 && q.size(2) >= 1, "q: expected (B,K,N), got ", q.sizes());
+    const int64_t B = q.size(0), K = q.size(1), N = q.size(2);
+    const at::Device dev = q.device();
+    req(quantiles, "quantiles", dev, {B, K + 1});
+    c10::DeviceGuard g(dev);
+    Tensor logit = new_f32({B, N}, dev);
+    OptTensor action;
+    if (return_action) action = at::empty({B}, at::TensorOptions().dtype(at::kLong).device(dev));
+    check(hpc_rll_fqf_q_value(fptr(q), fptr(quantiles), fmut(logit), action ? action->data_ptr<int64_t>() : nullptr,
+                              to_int(B, "B"), to_int(K, "K"), to_int(N, "N"), stream_of(dev)),
+          "hpc_rll_fqf_q_value");
+    return {logit, action};
+}
+
 // defined in rl_utils_lists.cpp (V-trace / UPGO / PPO L2 functions incl. the reference's long positional lists) and
 // rl_utils_pad.cpp (Pad / Unpad / group policies)
 void bind_loss_lists(pybind11::module_& m);
@@ -2236,4 +2384,25 @@ PYBIND11_MODULE(hpc_rl_utils, m) {
     }, py::arg("q"), py::arg("next_n_q"), py::arg("action"), py::arg("next_n_action"), py::arg("reward"), py::arg("done"),
           py::arg("weight") = py::none(), py::arg("value_gamma") = py::none(), py::arg("gamma") = 0.99,
           py::arg("tau_value") = py::none(), py::arg("scale") = py::none());
+    m.def("fqf_fractions", [](const Tensor& logits) { return FqfFractionsFn::apply(logits); }, py::arg("logits"),
+          "FQF fraction proposal from (B,K) logits: (quantiles (B,K+1), quantiles_hats (B,K), entropies (B,1)); quantiles and "
+          "entropies are differentiable wrt logits, quantiles_hats is detached");
+    m.def("fqf_nstep_td", [](const Tensor& q, const Tensor& nq, const Tensor& action, const Tensor& naction,
+                             const Tensor& reward, const Tensor& done, const Tensor& qh, const OptTensor& weight,
+                             const OptTensor& vg, double gamma, double kappa, std::optional<double> scale) {
+        return FqfTdFn::apply(q, nq, action, naction, reward, done, qh, weight, vg, gamma, kappa, scale);
+    }, py::arg("q"), py::arg("next_n_q"), py::arg("action"), py::arg("next_n_action"), py::arg("reward"), py::arg("done"),
+          py::arg("quantiles_hats"), py::arg("weight") = py::none(), py::arg("value_gamma") = py::none(),
+          py::arg("gamma") = 0.99, py::arg("kappa") = 1.0, py::arg("scale") = py::none(),
+          "FQF n-step quantile TD loss on q (B,K,N), next_n_q (B,K',N), quantiles_hats (B,K): (loss (1,), td_err (B,)); "
+          "differentiable wrt q; scale = 1/(global B) for a sharded caller");
+    m.def("fqf_fraction_loss", [](const Tensor& q_tau_i, const Tensor& q_value, const Tensor& quantiles, const Tensor& actions,
+                                  std::optional<double> scale) {
+        return FqfFractionLossFn::apply(q_tau_i, q_value, quantiles, actions, scale);
+    }, py::arg("q_tau_i"), py::arg("q_value"), py::arg("quantiles"), py::arg("actions"), py::arg("scale") = py::none(),
+          "FQF fraction loss on q_tau_i (B,K-1,N), q_value (B,K,N), quantiles (B,K+1): loss (1,); differentiable wrt "
+          "quantiles[:,1:K] only");
+    m.def("fqf_q_value", &fqf_q_value, py::arg("q"), py::arg("quantiles"), py::arg("return_action") = false,
+          "FQF expected value (B,N) = sum_i (quantiles[:,i+1] - quantiles[:,i]) q[:,i,:] and, with return_action, its argmax "
+          "(ties to the lowest index) from the same launch; forward only");
 }

@@ -803,6 +803,70 @@ int hpc_rll_qrdqn_nstep_td_backward(const float* grad_loss, const float* buf, co
 int hpc_rll_dist_last_config(int op, int* out);
 
 /* ------------------------------------------------------------------------------------------
+ * FQF (Fully parameterized Quantile Function, Yang et al. 2019) -- no reference counterpart; the formulas restate DI-engine's
+ * fqf_nstep_td_error / fqf_calculate_fraction_loss (ding/rl_utils/td.py) and the fraction proposal of its FQFHead.
+ * K fractions, N actions, B samples; fp32 contiguous, actions int64.  Every entry point answers argument errors before any HIP
+ * call, in this order: HPC_RLL_EINVAL (sizes, then null pointers), HPC_RLL_EALIGN (a float pointer off 4 bytes, an action
+ * pointer off 8), HPC_RLL_EUNSUPPORTED; then an empty batch (B == 0) clears `loss` where there is one and returns 0.  An
+ * action outside [0, N) never addresses memory: the value it would select reads as 0 and its gradient row is zero.
+ *
+ *   fractions  : logits (B,K) -> quantiles (B,K+1) = {0, inclusive scan of softmax}, quantiles_hats (B,K) = midpoints,
+ *                entropies (B,) = -sum p log p.  1 <= K <= 1024.  backward: grad_quantiles (B,K+1) and grad_entropies (B,) may
+ *                each be NULL (= zero); `entropies` is the forward's output.
+ *   nstep_td   : q (B,K,N), next_n_q (B,K',N), reward (nstep,B), done (B,), quantiles_hats (B,K), weight / value_gamma (B,) or
+ *                NULL.  loss (1,) = scale * sum_b weight_b td_err_b, td_err (B,), buf (B,K) = unit gradient wrt q[b,:,a_b];
+ *                partials: hpc_rll_partials_floats(B) floats.  backward: grad_q (B,K,N), rows one-hot at action[b]; B * K < 2^31, else
+ *                HPC_RLL_EUNSUPPORTED.
+ *   fraction_loss : q_tau_i (B,K-1,N), q_value (B,K,N), quantiles (B,K+1).  loss (1,) = scale * sum_b sum_i g_i quantiles[b,i+1],
+ *                g (B,K-1) (K == 1: empty, q_tau_i and g may be NULL, the loss is 0).  backward: grad_quantiles (B,K+1) =
+ *                grad_loss * scale * g in columns 1..K-1, zero in columns 0 and K.
+ *   q_value    : logit (B,N) = sum_i (quantiles[b,i+1] - quantiles[b,i]) q[b,i,:]; action (B,) int64 = argmax_n, ties to the
+ *                lowest index, in the same launch; NULL: no argmax. */
+int hpc_rll_fqf_fractions_forward(const float* logits, float* quantiles, float* quantiles_hats, float* entropies, int B,
+                                  int K, void* stream);
+int hpc_rll_fqf_fractions_backward(const float* logits, const float* entropies, const float* grad_quantiles,
+                                   const float* grad_entropies, float* grad_logits, int B, int K, void* stream);
+int hpc_rll_fqf_nstep_td_forward(const float* q, const float* next_n_q, const int64_t* action,
+                                 const int64_t* next_n_action, const float* reward, const float* done,
+                                 const float* quantiles_hats, const float* weight, const float* value_gamma, float* loss,
+                                 float* td_err, float* buf, float* partials, int K, int K_prime, int nstep, int B, int N,
+                                 float gamma, float kappa, float scale, void* stream);
+int hpc_rll_fqf_nstep_td_backward(const float* grad_loss, const float* buf, const int64_t* action, float* grad_q, int K,
+                                  int B, int N, void* stream);
+int hpc_rll_fqf_fraction_loss_forward(const float* q_tau_i, const float* q_value, const float* quantiles,
+                                      const int64_t* action, float* loss, float* g, float* partials, int K, int B, int N,
+                                      float scale, void* stream);
+int hpc_rll_fqf_fraction_loss_backward(const float* grad_loss, const float* g, float* grad_quantiles, int K, int B,
+                                       float scale, void* stream);
+int hpc_rll_fqf_q_value(const float* q, const float* quantiles, float* logit, int64_t* action, int B, int K, int N,
+                        void* stream);
+/* Diagnostic (read-only, modelled on hpc_rll_dist_last_config): the instantiation the most recent launch of each KIND ran in
+ * this process, noted on the host beside the launch.  out[HPC_RLL_FQF_CONFIG_INTS] holds HPC_RLL_FQF_LAUNCHES parts of
+ * HPC_RLL_FQF_PART_INTS ints, part k (HPC_RLL_FQF_LAUNCH_*) = {
+ *    [0] launches of this kind so far (0 = none yet: every other entry of the part is then -1),
+ *    [1] kernel family, one of HPC_RLL_FQF_FAMILY_*,
+ *    [2] G: lanes that hold one sample or row (8 / 16 / 32 / 64; 64 for WAVE), 0 for the elementwise streaming kernels,
+ *    [3] workgroups of the launch,
+ *    [4] 1 = the loss was finalised inside the launch, 0 = by a separate finalize launch or the kind has no loss,
+ *    [5] floats per load / store of the streamed operand (4 = 16 bytes, 1 = scalar) }.
+ * Calls that return before launching leave the record as it was.  HPC_RLL_EINVAL for out == NULL. */
+#define HPC_RLL_FQF_LAUNCH_TD_FORWARD (0)
+#define HPC_RLL_FQF_LAUNCH_TD_BACKWARD (1)
+#define HPC_RLL_FQF_LAUNCH_FRACTION_LOSS_FORWARD (2)
+#define HPC_RLL_FQF_LAUNCH_FRACTION_LOSS_BACKWARD (3)
+#define HPC_RLL_FQF_LAUNCH_FRACTIONS_FORWARD (4)
+#define HPC_RLL_FQF_LAUNCH_FRACTIONS_BACKWARD (5)
+#define HPC_RLL_FQF_LAUNCH_Q_VALUE (6)
+#define HPC_RLL_FQF_LAUNCHES (7)
+#define HPC_RLL_FQF_FAMILY_WAVE (0)            /* a wave per sample / row: TD loss and fraction loss above 64 fractions, fractions for 64 < K <= 1024 */
+#define HPC_RLL_FQF_FAMILY_GROUP (1)           /* a sample / row per group of G lanes, 64 / G per wave */
+#define HPC_RLL_FQF_FAMILY_STREAM (2)          /* streaming: TD backward, fraction-loss backward, q_value without argmax */
+#define HPC_RLL_FQF_FAMILY_STREAM_ARGMAX (3)   /* q_value with the greedy action in the same launch */
+#define HPC_RLL_FQF_PART_INTS (6)
+#define HPC_RLL_FQF_CONFIG_INTS (42)
+int hpc_rll_fqf_last_config(int* out);
+
+/* ------------------------------------------------------------------------------------------
  * Pad / Unpad of a ragged list of n contiguous fp32 tensors of rank 1..3 -- replaces Pad{1,2,3}DForward,
  * GroupPad{1,2,3}DForward, Unpad{1,2,3}DForward (rl_utils/entry.h:10-59, src/rl_utils/padding.cu:111-582).
  * A rank-1 tensor of length L is described as (d0,d1,d2) = (1,1,L), rank-2 (a,b) as (1,a,b).
