@@ -9,6 +9,11 @@
 // (torch::autograd::Function) the hpc_rll.* Python modules call -- one pybind call per Module.forward, backward
 // entirely inside the autograd engine.
 //
+// What an op's glue is written with: req() / req_opt() for the ops that check the device first, one line per tensor;
+// Args (rl_utils_ops.hpp) for the ops that name a wrong dtype or shape even on host tensors, each tensor declared once;
+// grad1() / grad3() for the scalar gradients, alias_of() / split1() for several losses in one buffer; applier<Fn>() to
+// bind an op whose python arguments are Fn::forward's, so that the signature is written once.
+//
 // There is no CPU / eager fallback: a non-GPU tensor is a RuntimeError.
 #pragma once
 
@@ -18,6 +23,7 @@
 #include <c10/hip/HIPStream.h>
 
 #include <algorithm>
+#include <array>
 #include <cstdint>
 #include <initializer_list>
 #include <mutex>
@@ -96,6 +102,10 @@ inline Tensor grad1(const Tensor& g, const at::Device& dev, const char* name) {
     Tensor r = g.reshape({1});
     if (!r.is_contiguous()) r = r.contiguous();
     return req(r, name, dev);
+}
+// The scalar gradients of the (policy, value, entropy) losses, as a backward receives them.
+inline std::array<Tensor, 3> grad3(const ag::tensor_list& g, const at::Device& dev) {
+    return {grad1(g[0], dev, "grad_policy_loss"), grad1(g[1], dev, "grad_value_loss"), grad1(g[2], dev, "grad_entropy_loss")};
 }
 
 // `n` expected tensors in a python list.
@@ -188,6 +198,19 @@ inline at::Tensor alias_of(const at::Tensor& buf, int64_t offset, int64_t n) {
     at::Tensor t = at::empty({0}, buf.options());
     t.set_(buf.storage(), buf.storage_offset() + offset, {n}, {1});
     return t;
+}
+// The first `n` floats of `buf` as `n` such (1,) tensors: the losses of one launch.
+inline ag::tensor_list split1(const at::Tensor& buf, int n) {
+    ag::tensor_list out;
+    for (int k = 0; k < n; ++k) out.push_back(alias_of(buf, k, 1));
+    return out;
+}
+
+// What a fused op is bound as when python's arguments are Fn::forward's own: `m.def(name, applier<Fn>(&Fn::forward),
+// py::arg(...)...)`.  The signature is read off Fn::forward, so it is written once.  An op that computes something
+// before apply() keeps a lambda.
+template <class Fn, class R, class... A> auto applier(R (*)(ag::AutogradContext*, A...)) {
+    return [](A... a) { return Fn::apply(a...); };
 }
 
 inline void bind_common(pybind11::module_& m) {

@@ -129,14 +129,6 @@ struct GaeFn : public ag::Function<GaeFn> {
 // Textbook GAE with episode ends (hpc_rll_gae_masked_*): value (T+1,B) stacked, or value (T,B) + next_value (T,B);
 // done / traj_flag (T,B) bool, uint8 or float32 (either may be None).  Dtypes and shapes are checked before the device
 // so that a wrong argument is named even on host tensors.
-int mask_code(const Tensor& m, const char* name) {
-    const at::ScalarType s = m.scalar_type();
-    if (s == at::kBool || s == at::kByte) return HPC_RLL_MASK_U8;
-    if (s == at::kFloat) return HPC_RLL_MASK_F32;
-    TORCH_CHECK(false, name, ": dtype ", s, " is not accepted; expected bool, uint8 or float32");
-    return -1;
-}
-
 // The masks as the kernels take them: one dtype code for both (a byte mask next to a float one becomes 0/1 floats).
 struct Masks { Tensor done, flag; int code = HPC_RLL_MASK_U8; };
 
@@ -184,8 +176,6 @@ Masks check_masked_inputs(const char* op, const Tensor& value, const Tensor& rew
     m.code = (codes[0] == HPC_RLL_MASK_F32 || codes[1] == HPC_RLL_MASK_F32) ? HPC_RLL_MASK_F32 : HPC_RLL_MASK_U8;
     return m;
 }
-
-inline const void* vptr(const Tensor& t) { return t.defined() ? t.const_data_ptr() : nullptr; }
 
 struct GaeMaskedFn : public ag::Function<GaeMaskedFn> {
     static Tensor forward(ag::AutogradContext* ctx, const Tensor& value, const Tensor& reward, const OptTensor& done,
@@ -359,7 +349,7 @@ struct VtraceFn : public ag::Function<VtraceFn> {
         vtrace_forward_launch(d, target, behaviour, action, value, reward, weight, losses, ws, gamma, lambda, rho_clip,
                               c_clip, rho_pg_clip, scale);
         ctx->save_for_backward({target, action, ws});
-        return {alias_of(losses, 0, 1), alias_of(losses, 1, 1), alias_of(losses, 2, 1)};
+        return split1(losses, 3);
     }
     static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
         ag::tensor_list out(12);
@@ -370,8 +360,7 @@ struct VtraceFn : public ag::Function<VtraceFn> {
         const at::Device dev = target.device();
         c10::DeviceGuard g(dev);
         const int64_t T = target.size(0), B = target.size(1);
-        Tensor g_pg = grad1(grads[0], dev, "grad_policy_loss"), g_v = grad1(grads[1], dev, "grad_value_loss"),
-               g_e = grad1(grads[2], dev, "grad_entropy_loss");
+        const auto [g_pg, g_v, g_e] = grad3(grads, dev);
         Tensor grad_target = need_t ? at::empty_like(target) : undef();
         Tensor grad_value = need_v ? new_f32({T + 1, B}, dev) : undef();
         vtrace_backward_launch(g_pg, g_v, g_e, target, action, ws, grad_target, grad_value);
@@ -386,12 +375,6 @@ struct VtraceFn : public ag::Function<VtraceFn> {
 // and the checks of gae_masked; only the forward scans differ from td_lambda / vtrace, whose backward entry points consume
 // the saved per-sample coefficients.  Shapes and dtypes are checked before the device, so that a wrong argument is named
 // even on host tensors.
-void check_shape(const Tensor& t, const char* name, at::IntArrayRef shape, at::ScalarType dtype = at::kFloat) {
-    TORCH_CHECK(t.defined(), name, ": expected a tensor, got None");
-    TORCH_CHECK(t.scalar_type() == dtype, name, ": dtype ", t.scalar_type(), ", expected ", dtype);
-    TORCH_CHECK(t.sizes() == shape, name, ": shape ", t.sizes(), ", expected ", shape);
-}
-
 // weight None | (B,) | (T,B) -> weight_mode 0 / 1 / 2 (dtype and shape only; the device is checked by the caller)
 int masked_td_weight_mode(const OptTensor& weight, int64_t T, int64_t B) {
     if (!has(weight)) return 0;
@@ -455,18 +438,14 @@ struct VtraceMaskedFn : public ag::Function<VtraceMaskedFn> {
         TORCH_CHECK(target.defined(), "target_output: expected a tensor, got None");
         TORCH_CHECK(target.dim() == 3, "target_output: expected (T,B,N), got ", target.sizes());
         const int64_t T = target.size(0), B = target.size(1), N = target.size(2);
-        TORCH_CHECK(target.scalar_type() == at::kFloat, "target_output: dtype ", target.scalar_type(), ", expected ",
-                    at::kFloat);
-        check_shape(behaviour, "behaviour_output", {T, B, N});
-        check_shape(action, "action", {T, B}, at::kLong);
-        check_shape(reward, "reward", {T, B});
-        if (has(weight)) check_shape(*weight, "weight", {T, B});
+        Args args;
+        args.add(target, "target_output", {T, B, N});
+        args.add(behaviour, "behaviour_output", {T, B, N});
+        args.add(action, "action", {T, B}, at::kLong);
+        check_shape(reward, "reward", {T, B});   // its device is check_masked_inputs's
+        args.add(weight, "weight", {T, B});
         const Masks m = check_masked_inputs("vtrace_masked", value, reward, done, flag, next_value);
-        const at::Device dev = reward.device();
-        req(target, "target_output", dev);
-        req(behaviour, "behaviour_output", dev);
-        req(action, "action", dev, at::kLong);
-        if (has(weight)) req(*weight, "weight", dev);
+        const at::Device dev = args.on_device_of(reward);
         c10::DeviceGuard g(dev);
         Tensor losses = new_f32({3}, dev);
         Tensor ws = vtrace_workspace(T, B, dev);
@@ -478,7 +457,7 @@ struct VtraceMaskedFn : public ag::Function<VtraceMaskedFn> {
               "hpc_rll_vtrace_masked_forward");
         ctx->save_for_backward({target, action, ws});
         ctx->saved_data["stacked"] = !has(next_value);
-        return {alias_of(losses, 0, 1), alias_of(losses, 1, 1), alias_of(losses, 2, 1)};
+        return split1(losses, 3);
     }
     static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
         ag::tensor_list out(15);
@@ -490,8 +469,7 @@ struct VtraceMaskedFn : public ag::Function<VtraceMaskedFn> {
         const at::Device dev = target.device();
         c10::DeviceGuard g(dev);
         const int64_t T = target.size(0), B = target.size(1);
-        Tensor g_pg = grad1(grads[0], dev, "grad_policy_loss"), g_v = grad1(grads[1], dev, "grad_value_loss"),
-               g_e = grad1(grads[2], dev, "grad_entropy_loss");
+        const auto [g_pg, g_v, g_e] = grad3(grads, dev);
         Tensor grad_target = need_t ? at::empty_like(target) : undef();
         Tensor grad_value = need_v ? new_f32({stacked ? T + 1 : T, B}, dev) : undef();
         // next-value form: the unit value gradient (ws rows 2T*B ...) has T rows and no bootstrap row to zero
@@ -575,16 +553,13 @@ struct UpgoMaskedFn : public ag::Function<UpgoMaskedFn> {
         TORCH_CHECK(target.defined(), "target_output: expected a tensor, got None");
         TORCH_CHECK(target.dim() == 3, "target_output: expected (T,B,N), got ", target.sizes());
         const int64_t T = target.size(0), B = target.size(1), N = target.size(2);
-        TORCH_CHECK(target.scalar_type() == at::kFloat, "target_output: dtype ", target.scalar_type(), ", expected ",
-                    at::kFloat);
-        check_shape(rho, "rhos", {T, B});
-        check_shape(action, "action", {T, B}, at::kLong);
-        check_shape(reward, "rewards", {T, B});
+        Args args;
+        args.add(target, "target_output", {T, B, N});
+        args.add(rho, "rhos", {T, B});
+        args.add(action, "action", {T, B}, at::kLong);
+        check_shape(reward, "rewards", {T, B});   // its device is check_masked_inputs's
         const Masks m = check_masked_inputs("upgo_masked", value, reward, done, flag, next_value);
-        const at::Device dev = reward.device();
-        req(target, "target_output", dev);
-        req(rho, "rhos", dev);
-        req(action, "action", dev, at::kLong);
+        const at::Device dev = args.on_device_of(reward);
         c10::DeviceGuard g(dev);
         Tensor loss = new_f32({1}, dev);
         Tensor ws = upgo_workspace(T, B, dev);
@@ -669,8 +644,7 @@ struct PpoFn : public ag::Function<PpoFn> {
         const Tensor &ln = saved[0], &action = saved[1], &ws = saved[2];
         const at::Device dev = ln.device();
         c10::DeviceGuard g(dev);
-        Tensor g_p = grad1(grads[0], dev, "grad_policy_loss"), g_v = grad1(grads[1], dev, "grad_value_loss"),
-               g_e = grad1(grads[2], dev, "grad_entropy_loss");
+        const auto [g_p, g_v, g_e] = grad3(grads, dev);
         Tensor grad_logits = need_l ? at::empty_like(ln) : undef();
         Tensor grad_value = need_v ? new_f32({ln.size(0)}, dev) : undef();
         ppo_backward_launch(g_p, g_v, g_e, ln, action, ws, grad_logits, grad_value);
@@ -731,8 +705,7 @@ struct PpoContinuousFn : public ag::Function<PpoContinuousFn> {
         const Tensor &mu_new = saved[0], &sigma_new = saved[1], &action = saved[2], &ws = saved[3];
         const at::Device dev = mu_new.device();
         c10::DeviceGuard g(dev);
-        Tensor g_p = grad1(grads[0], dev, "grad_policy_loss"), g_v = grad1(grads[1], dev, "grad_value_loss"),
-               g_e = grad1(grads[2], dev, "grad_entropy_loss");
+        const auto [g_p, g_v, g_e] = grad3(grads, dev);
         Tensor grad_mu = need_m ? at::empty_like(mu_new) : undef();
         Tensor grad_sigma = need_s ? at::empty_like(sigma_new) : undef();
         Tensor grad_value = need_v ? new_f32({mu_new.size(0)}, dev) : undef();
@@ -759,23 +732,18 @@ struct VtraceContinuousFn : public ag::Function<VtraceContinuousFn> {
         TORCH_CHECK(mu_t.defined(), "mu_target: expected a tensor, got None");
         TORCH_CHECK(mu_t.dim() == 3, "mu_target: expected (T,B,A), got ", mu_t.sizes());
         const int64_t T = mu_t.size(0), B = mu_t.size(1), A = mu_t.size(2);
-        check_shape(mu_t, "mu_target", {T, B, A});
-        check_shape(sigma_t, "sigma_target", {T, B, A});
-        check_shape(mu_b, "mu_behaviour", {T, B, A});
-        check_shape(sigma_b, "sigma_behaviour", {T, B, A});
-        check_shape(action, "action", {T, B, A});
-        check_shape(reward, "reward", {T, B});
-        if (has(weight)) check_shape(*weight, "weight", {T, B});
+        Args args;
+        args.add(mu_t, "mu_target", {T, B, A});
+        args.add(sigma_t, "sigma_target", {T, B, A});
+        args.add(mu_b, "mu_behaviour", {T, B, A});
+        args.add(sigma_b, "sigma_behaviour", {T, B, A});
+        args.add(action, "action", {T, B, A});
+        check_shape(reward, "reward", {T, B});   // its device is check_masked_inputs's
+        args.add(weight, "weight", {T, B});
         TORCH_CHECK(A >= 1 && A <= 1024, "vtrace_continuous: an action dimension of ", A,
                     " is not supported by the gfx950 kernels (1 <= A <= 1024)");
         const Masks m = check_masked_inputs("vtrace_continuous", value, reward, done, flag, next_value);
-        const at::Device dev = reward.device();
-        req(mu_t, "mu_target", dev);
-        req(sigma_t, "sigma_target", dev);
-        req(mu_b, "mu_behaviour", dev);
-        req(sigma_b, "sigma_behaviour", dev);
-        req(action, "action", dev);
-        if (has(weight)) req(*weight, "weight", dev);
+        const at::Device dev = args.on_device_of(reward);
         c10::DeviceGuard g(dev);
         Tensor losses = new_f32({3}, dev);
         Tensor ws = vtrace_workspace(T, B, dev);
@@ -788,7 +756,7 @@ struct VtraceContinuousFn : public ag::Function<VtraceContinuousFn> {
               "hpc_rll_vtrace_continuous_forward");
         ctx->save_for_backward({mu_t, sigma_t, action, ws});
         ctx->saved_data["stacked"] = !has(next_value);
-        return {alias_of(losses, 0, 1), alias_of(losses, 1, 1), alias_of(losses, 2, 1)};
+        return split1(losses, 3);
     }
     static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
         ag::tensor_list out(17);
@@ -800,8 +768,7 @@ struct VtraceContinuousFn : public ag::Function<VtraceContinuousFn> {
         const at::Device dev = mu_t.device();
         c10::DeviceGuard g(dev);
         const int64_t T = mu_t.size(0), B = mu_t.size(1), A = mu_t.size(2);
-        Tensor g_pg = grad1(grads[0], dev, "grad_policy_loss"), g_v = grad1(grads[1], dev, "grad_value_loss"),
-               g_e = grad1(grads[2], dev, "grad_entropy_loss");
+        const auto [g_pg, g_v, g_e] = grad3(grads, dev);
         Tensor grad_mu = need_m ? at::empty_like(mu_t) : undef();
         Tensor grad_sigma = need_s ? at::empty_like(sigma_t) : undef();
         Tensor grad_value = need_v ? new_f32({stacked ? T + 1 : T, B}, dev) : undef();
@@ -837,20 +804,15 @@ Tensor retrace_targets(const Tensor& q, const Tensor& v_pred, const Tensor& rewa
     TORCH_CHECK(q.defined(), "q_values: expected a tensor, got None");
     TORCH_CHECK(q.dim() == 3 && q.size(0) >= 1, "q_values: expected (T+1,B,N), got ", q.sizes());
     const int64_t T = q.size(0) - 1, B = q.size(1), N = q.size(2);
-    check_shape(q, "q_values", {T + 1, B, N});
-    check_shape(v_pred, "v_pred", {T + 1, B, 1});
-    check_shape(reward, "rewards", {T, B});
-    check_shape(action, "actions", {T, B}, at::kLong);
-    if (has(weights)) check_shape(*weights, "weights", {T, B});
-    check_shape(ratio, "ratio", {T, B, N});
+    Args args;
+    args.add(q, "q_values", {T + 1, B, N});
+    args.add(v_pred, "v_pred", {T + 1, B, 1});
+    args.add(reward, "rewards", {T, B});
+    args.add(action, "actions", {T, B}, at::kLong);
+    args.add(weights, "weights", {T, B});
+    args.add(ratio, "ratio", {T, B, N});
     retrace_check_n("retrace", N);
-    const at::Device dev = q.device();
-    req(q, "q_values", dev);
-    req(v_pred, "v_pred", dev);
-    req(reward, "rewards", dev);
-    req(action, "actions", dev, at::kLong);
-    if (has(weights)) req(*weights, "weights", dev);
-    req(ratio, "ratio", dev);
+    const at::Device dev = args.on_device_of(q);
     c10::DeviceGuard g(dev);
     if (T == 0 || B == 0) return v_pred.detach().clone();   // no step: Q_T = v_T
     Tensor out = new_f32({T + 1, B, 1}, dev);
@@ -870,22 +832,16 @@ struct RetraceLossFn : public ag::Function<RetraceLossFn> {
         TORCH_CHECK(q.defined(), "q_values: expected a tensor, got None");
         TORCH_CHECK(q.dim() == 3 && q.size(0) >= 1, "q_values: expected (T+1,B,N), got ", q.sizes());
         const int64_t T = q.size(0) - 1, B = q.size(1), N = q.size(2);
-        check_shape(q, "q_values", {T + 1, B, N});
-        check_shape(target, "target_output", {T + 1, B, N});
-        check_shape(behaviour, "behaviour_output", {T, B, N});
-        check_shape(action, "action", {T, B}, at::kLong);
-        check_shape(reward, "reward", {T, B});
-        if (has(weights)) check_shape(*weights, "weights", {T, B});
-        if (has(loss_weight)) check_shape(*loss_weight, "loss_weight", {T, B});
+        Args args;
+        args.add(q, "q_values", {T + 1, B, N});
+        args.add(target, "target_output", {T + 1, B, N});
+        args.add(behaviour, "behaviour_output", {T, B, N});
+        args.add(action, "action", {T, B}, at::kLong);
+        args.add(reward, "reward", {T, B});
+        args.add(weights, "weights", {T, B});
+        args.add(loss_weight, "loss_weight", {T, B});
         retrace_check_n("retrace_loss", N);
-        const at::Device dev = q.device();
-        req(q, "q_values", dev);
-        req(target, "target_output", dev);
-        req(behaviour, "behaviour_output", dev);
-        req(action, "action", dev, at::kLong);
-        req(reward, "reward", dev);
-        if (has(weights)) req(*weights, "weights", dev);
-        if (has(loss_weight)) req(*loss_weight, "loss_weight", dev);
+        const at::Device dev = args.on_device_of(q);
         c10::DeviceGuard g(dev);
         const bool empty = T == 0 || B == 0;
         Tensor loss = new_f32({1}, dev);
@@ -1010,13 +966,12 @@ struct AcerPolicyFn : public ag::Function<AcerPolicyFn> {
 Tensor acer_trust_region(const Tensor& grad, const Tensor& avg_logit, double trust_region) {
     TORCH_CHECK(grad.defined(), "actor_gradients: expected a tensor, got None");
     TORCH_CHECK(grad.dim() >= 1, "actor_gradients: expected (..., N), got ", grad.sizes());
-    check_shape(grad, "actor_gradients", grad.sizes());
-    check_shape(avg_logit, "avg_logit", grad.sizes());
+    Args args;
+    args.add(grad, "actor_gradients", grad.sizes());
+    args.add(avg_logit, "avg_logit", grad.sizes());
     const int64_t N = grad.size(-1);
     retrace_check_n("acer_trust_region_update", N);
-    const at::Device dev = grad.device();
-    req(grad, "actor_gradients", dev);
-    req(avg_logit, "avg_logit", dev);
+    const at::Device dev = args.on_device_of(grad);
     c10::DeviceGuard g(dev);
     Tensor out = at::empty_like(grad);
     check(hpc_rll_acer_trust_region(fptr(grad), fptr(avg_logit), fmut(out), grad.numel() / N, to_int(N, "N"),
@@ -1037,28 +992,17 @@ struct ComaFn : public ag::Function<ComaFn> {
         TORCH_CHECK(logit.defined(), "logit: expected a tensor, got None");
         TORCH_CHECK(logit.dim() == 4, "logit: expected (T,B,A,N), got ", logit.sizes());
         const int64_t T = logit.size(0), B = logit.size(1), A = logit.size(2), N = logit.size(3);
-        check_shape(logit, "logit", {T, B, A, N});
-        check_shape(action, "action", {T, B, A}, at::kLong);
-        check_shape(q, "q_value", {T, B, A, N});
-        check_shape(target_q, "target_q_value", {T, B, A, N});
-        check_shape(reward, "reward", {T, B});
-        if (has(weight)) check_shape(*weight, "weight", {T, B, A});
-        int code = HPC_RLL_MASK_U8;
-        if (has(done)) {
-            code = mask_code(*done, "done");
-            TORCH_CHECK(done->sizes() == reward.sizes(), "done: shape ", done->sizes(), ", expected ", reward.sizes(),
-                        " (the shape of reward)");
-        }
+        Args args;
+        args.add(logit, "logit", {T, B, A, N});
+        args.add(action, "action", {T, B, A}, at::kLong);
+        args.add(q, "q_value", {T, B, A, N});
+        args.add(target_q, "target_q_value", {T, B, A, N});
+        args.add(reward, "reward", {T, B});
+        args.add(weight, "weight", {T, B, A});
+        const Args::Mask dm = args.add_mask(done, "done", reward.sizes(), " (the shape of reward)");
         retrace_check_n("coma", N);
         TORCH_CHECK(B * A <= INT32_MAX, "coma: B*A = ", B * A, " does not fit the kernels' 32-bit column count");
-        const at::Device dev = logit.device();
-        req(logit, "logit", dev);
-        req(action, "action", dev, at::kLong);
-        req(q, "q_value", dev);
-        req(target_q, "target_q_value", dev);
-        req(reward, "reward", dev);
-        if (has(weight)) req(*weight, "weight", dev);
-        if (has(done)) req(*done, "done", dev, done->scalar_type());
+        const at::Device dev = args.on_device_of(logit);
         c10::DeviceGuard g(dev);
         Tensor losses = new_f32({3}, dev);
         const int64_t nws = hpc_rll_coma_workspace_floats(to_int(T, "T"), to_int(B, "B"), to_int(A, "A"));
@@ -1066,12 +1010,12 @@ struct ComaFn : public ag::Function<ComaFn> {
         Tensor ws = new_f32({nws}, dev);
         const float s_pe = loss_scale(scale_pe, T * B * A), s_q = loss_scale(scale_q, (T - 1) * B * A);
         check(hpc_rll_coma_forward(fptr(logit), iptr(action), fptr(q), fptr(target_q), fptr(reward), fptr(weight),
-                                   has(done) ? vptr(*done) : nullptr, code, fmut(losses), fmut(ws), (int)T, (int)B, (int)A,
+                                   dm.ptr, dm.code, fmut(losses), fmut(ws), (int)T, (int)B, (int)A,
                                    to_int(N, "N"), (float)gamma, (float)lambda, s_pe, s_q, stream_of(dev)),
               "hpc_rll_coma_forward");
         ctx->save_for_backward({logit, action, has(weight) ? *weight : undef(), ws});
         ctx->saved_data["scale_pe"] = (double)s_pe;
-        return {alias_of(losses, 0, 1), alias_of(losses, 1, 1), alias_of(losses, 2, 1)};
+        return split1(losses, 3);
     }
     static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
         ag::tensor_list out(11);
@@ -1108,26 +1052,17 @@ struct R2d2Fn : public ag::Function<R2d2Fn> {
         TORCH_CHECK(q.defined(), "q: expected a tensor, got None");
         TORCH_CHECK(q.dim() == 3, "q: expected (T,B,N), got ", q.sizes());
         const int64_t T = q.size(0), B = q.size(1), N = q.size(2);
-        check_shape(q, "q", {T, B, N});
-        check_shape(target_q, "target_q", {T, B, N});
-        check_shape(action, "action", {T, B}, at::kLong);
-        check_shape(reward, "reward", {T, B});
-        int code = HPC_RLL_MASK_U8;
-        if (has(done)) {
-            code = mask_code(*done, "done");
-            TORCH_CHECK(done->sizes() == reward.sizes(), "done: shape ", done->sizes(), ", expected ", reward.sizes(),
-                        " (the shape of reward)");
-        }
-        const int wm = masked_td_weight_mode(weight, T, B);
+        Args args;
+        args.add(q, "q", {T, B, N});
+        args.add(target_q, "target_q", {T, B, N});
+        args.add(action, "action", {T, B}, at::kLong);
+        args.add(reward, "reward", {T, B});
+        const Args::Mask dm = args.add_mask(done, "done", reward.sizes(), " (the shape of reward)");
+        const int wm = masked_td_weight_mode(weight, T, B);   // (B,) or (T,B): its own dtype and shape messages
         TORCH_CHECK(nstep >= 1, "r2d2_td: nstep = ", nstep, ", expected nstep >= 1");
         TORCH_CHECK(burnin >= 0, "r2d2_td: burnin = ", burnin, ", expected burnin >= 0");
         retrace_check_n("r2d2_td", N);
-        const at::Device dev = q.device();
-        req(q, "q", dev);
-        req(target_q, "target_q", dev);
-        req(action, "action", dev, at::kLong);
-        req(reward, "reward", dev);
-        if (has(done)) req(*done, "done", dev, done->scalar_type());
+        const at::Device dev = args.on_device_of(q);
         if (has(weight)) req(*weight, "weight", dev);
         c10::DeviceGuard g(dev);
         const int64_t L = std::max<int64_t>(T - std::min(nstep, T) - std::min(burnin, T), 0);
@@ -1138,8 +1073,8 @@ struct R2d2Fn : public ag::Function<R2d2Fn> {
         Tensor priority = empty ? at::zeros({B}, q.options()) : new_f32({B}, dev);
         Tensor ws = new_f32({empty ? 0 : hpc_rll_r2d2_workspace_floats(to_int(T, "T"), to_int(B, "B"))}, dev);
         const int n = empty ? 1 : to_int(nstep, "nstep"), bi = empty ? (int)T : to_int(burnin, "burnin");
-        check(hpc_rll_r2d2_forward(fptr(q), fptr(target_q), iptr(action), fptr(reward), has(done) ? vptr(*done) : nullptr, code,
-                                   fptr(weight), wm, fmut(loss), fmut(td), fmut(priority), fmut(ws), to_int(T, "T"),
+        check(hpc_rll_r2d2_forward(fptr(q), fptr(target_q), iptr(action), fptr(reward), dm.ptr, dm.code, fptr(weight), wm,
+                                   fmut(loss), fmut(td), fmut(priority), fmut(ws), to_int(T, "T"),
                                    to_int(B, "B"), to_int(N, "N"), n, bi, (float)gamma, value_rescale ? 1 : 0,
                                    double_q ? 1 : 0, (float)priority_eta, loss_scale(scale, L * B), stream_of(dev)),
               "hpc_rll_r2d2_forward");
@@ -1191,36 +1126,23 @@ struct SacDiscreteFn : public ag::Function<SacDiscreteFn> {
                     has(q2) ? "q2" : "target_q2", " alone)");
         const at::IntArrayRef full = logit.sizes(), lead = full.slice(0, full.size() - 1);
         const int64_t N = full.back();
-        check_shape(logit, "logit", full);
-        check_shape(next_logit, "next_logit", full);
-        check_shape(q1, "q1", full);
-        if (has(q2)) check_shape(*q2, "q2", full);
-        check_shape(target_q1, "target_q1", full);
-        if (has(target_q2)) check_shape(*target_q2, "target_q2", full);
-        check_shape(action, "action", lead, at::kLong);
-        check_shape(reward, "reward", lead);
-        int code = HPC_RLL_MASK_U8;
-        if (has(done)) {
-            code = mask_code(*done, "done");
-            TORCH_CHECK(done->sizes() == lead, "done: shape ", done->sizes(), ", expected ", lead);
-        }
-        if (has(weight)) check_shape(*weight, "weight", lead);
-        if (has(alpha_t)) {
+        Args args;
+        args.add(logit, "logit", full);
+        args.add(next_logit, "next_logit", full);
+        args.add(q1, "q1", full);
+        args.add(q2, "q2", full);
+        args.add(target_q1, "target_q1", full);
+        args.add(target_q2, "target_q2", full);
+        args.add(action, "action", lead, at::kLong);
+        args.add(reward, "reward", lead);
+        const Args::Mask dm = args.add_mask(done, "done", lead);
+        args.add(weight, "weight", lead);
+        if (has(alpha_t)) {   // one element of any shape: its own messages
             TORCH_CHECK(alpha_t->scalar_type() == at::kFloat, "alpha: dtype ", alpha_t->scalar_type(), ", expected ", at::kFloat);
             TORCH_CHECK(alpha_t->numel() == 1, "alpha: expected a float or a 1-element tensor, got shape ", alpha_t->sizes());
         }
         retrace_check_n("sac_discrete", N);
-        const at::Device dev = logit.device();
-        req(logit, "logit", dev);
-        req(next_logit, "next_logit", dev);
-        req(q1, "q1", dev);
-        if (has(q2)) req(*q2, "q2", dev);
-        req(target_q1, "target_q1", dev);
-        if (has(target_q2)) req(*target_q2, "target_q2", dev);
-        req(action, "action", dev, at::kLong);
-        req(reward, "reward", dev);
-        if (has(done)) req(*done, "done", dev, done->scalar_type());
-        if (has(weight)) req(*weight, "weight", dev);
+        const at::Device dev = args.on_device_of(logit);
         if (has(alpha_t)) req(*alpha_t, "alpha", dev);
         c10::DeviceGuard g(dev);
         const int64_t rows = action.numel();
@@ -1229,7 +1151,7 @@ struct SacDiscreteFn : public ag::Function<SacDiscreteFn> {
         Tensor unit = (want_grad && rows > 0) ? new_f32(full, dev) : undef();
         Tensor ws = new_f32({rows > 0 ? hpc_rll_sac_discrete_workspace_floats(rows) : 0}, dev);
         check(hpc_rll_sac_discrete_forward(fptr(logit), fptr(next_logit), fptr(q1), fptr(q2), fptr(target_q1), fptr(target_q2),
-                                           iptr(action), fptr(reward), has(done) ? vptr(*done) : nullptr, code, fptr(weight),
+                                           iptr(action), fptr(reward), dm.ptr, dm.code, fptr(weight),
                                            fptr(alpha_t), (float)alpha, fmut(out4), fmut(td), fmut(tq), fmut(unit), fmut(ws),
                                            rows, to_int(N, "N"), (float)gamma, loss_scale(scale, rows), stream_of(dev)),
               "hpc_rll_sac_discrete_forward");
@@ -1287,11 +1209,11 @@ struct TokenLogpFn : public ag::Function<TokenLogpFn> {
         const at::ScalarType st = logits_dtype(logits, "logits");
         TORCH_CHECK(logits.dim() >= 1, "logits: expected (..., V), got ", logits.sizes());
         const int64_t V = logits.size(-1);
-        check_shape(action, "action", logits.sizes().slice(0, logits.dim() - 1), at::kLong);
+        Args args;
+        args.add(logits, "logits", logits.sizes(), st);
+        args.add(action, "action", logits.sizes().slice(0, logits.dim() - 1), at::kLong);
         grpo_check_v("token_log_prob", V);
-        const at::Device dev = logits.device();
-        req(logits, "logits", dev, st);
-        req(action, "action", dev, at::kLong);
+        const at::Device dev = args.on_device_of(logits);
         c10::DeviceGuard g(dev);
         const int64_t rows = action.numel();
         Tensor logp = new_f32(action.sizes(), dev), lse = new_f32({rows}, dev);
@@ -1323,15 +1245,15 @@ struct TokenLogpFn : public ag::Function<TokenLogpFn> {
 // workspace (lse and coef are what the backward reads).
 struct GrpoFn : public ag::Function<GrpoFn> {
     // logits (B,S,V) of either element type, or log-probs (B,S) fp32: the number of dimensions decides
-    static int kind_of(const Tensor& t, const char* name, int64_t B, int64_t S, int64_t V) {
+    static int kind_of(Args& args, const Tensor& t, const char* name, int64_t B, int64_t S, int64_t V) {
         TORCH_CHECK(t.defined(), name, ": expected a tensor, got None");
         TORCH_CHECK(t.dim() == 2 || t.dim() == 3, name, ": expected logits (B,S,V) or log-probs (B,S), got ", t.sizes());
         if (t.dim() == 2) {
-            check_shape(t, name, {B, S});
+            args.add(t, name, {B, S});
             return HPC_RLL_GRPO_LOGP;
         }
         const at::ScalarType st = logits_dtype(t, name);
-        check_shape(t, name, {B, S, V}, st);
+        args.add(t, name, {B, S, V}, st);
         return elem_code(st);
     }
     static ag::tensor_list forward(ag::AutogradContext* ctx, const Tensor& logit_new, const Tensor& old, const OptTensor& ref,
@@ -1340,19 +1262,15 @@ struct GrpoFn : public ag::Function<GrpoFn> {
         const at::ScalarType st = logits_dtype(logit_new, "logit_new");
         TORCH_CHECK(logit_new.dim() == 3, "logit_new: expected (B,S,V), got ", logit_new.sizes());
         const int64_t B = logit_new.size(0), S = logit_new.size(1), V = logit_new.size(2);
-        const int old_kind = kind_of(old, "old", B, S, V);
-        const int ref_kind = has(ref) ? kind_of(*ref, "ref", B, S, V) : HPC_RLL_GRPO_LOGP;
-        check_shape(action, "action", {B, S}, at::kLong);
-        check_shape(adv, "adv", {B});
-        if (has(weight)) check_shape(*weight, "weight", {B, S});
+        Args args;
+        args.add(logit_new, "logit_new", {B, S, V}, st);
+        const int old_kind = kind_of(args, old, "old", B, S, V);
+        const int ref_kind = has(ref) ? kind_of(args, *ref, "ref", B, S, V) : HPC_RLL_GRPO_LOGP;
+        args.add(action, "action", {B, S}, at::kLong);
+        args.add(adv, "adv", {B});
+        args.add(weight, "weight", {B, S});
         grpo_check_v("grpo_policy_loss", V);
-        const at::Device dev = logit_new.device();
-        req(logit_new, "logit_new", dev, st);
-        req(old, "old", dev, old.scalar_type());
-        if (has(ref)) req(*ref, "ref", dev, ref->scalar_type());
-        req(action, "action", dev, at::kLong);
-        req(adv, "adv", dev);
-        if (has(weight)) req(*weight, "weight", dev);
+        const at::Device dev = args.on_device_of(logit_new);
         c10::DeviceGuard g(dev);
         const bool empty = B == 0 || S == 0 || V == 0;
         Tensor out4 = new_f32({4}, dev);
@@ -1364,7 +1282,7 @@ struct GrpoFn : public ag::Function<GrpoFn> {
               "hpc_rll_grpo_forward");
         ctx->save_for_backward({logit_new, action, ws});
         ctx->saved_data["empty"] = empty;
-        ag::tensor_list out = {alias_of(out4, 0, 1), alias_of(out4, 1, 1), alias_of(out4, 2, 1), alias_of(out4, 3, 1)};
+        ag::tensor_list out = split1(out4, 4);
         ctx->mark_non_differentiable({out[1], out[2], out[3]});
         return out;
     }
@@ -1400,13 +1318,12 @@ struct TokenLpeFn : public ag::Function<TokenLpeFn> {
         TORCH_CHECK(logits.dim() >= 1, "logits: expected (..., V), got ", logits.sizes());
         const int64_t V = logits.size(-1);
         const at::IntArrayRef lead = logits.sizes().slice(0, logits.dim() - 1);
-        check_shape(action, "action", lead, at::kLong);
-        if (has(weight)) check_shape(*weight, "weight", lead);
+        Args args;
+        args.add(logits, "logits", logits.sizes(), st);
+        args.add(action, "action", lead, at::kLong);
+        args.add(weight, "weight", lead);
         grpo_check_v("token_log_prob_entropy", V);
-        const at::Device dev = logits.device();
-        req(logits, "logits", dev, st);
-        req(action, "action", dev, at::kLong);
-        if (has(weight)) req(*weight, "weight", dev);
+        const at::Device dev = args.on_device_of(logits);
         c10::DeviceGuard g(dev);
         const int64_t rows = action.numel();
         Tensor logp = new_f32(action.sizes(), dev), ent = new_f32(action.sizes(), dev), lse = new_f32({rows}, dev);
@@ -1443,20 +1360,17 @@ std::tuple<Tensor, Tensor> lm_gae(const Tensor& value, const OptTensor& weight, 
     TORCH_CHECK(value.defined(), "value: expected a tensor, got None");
     TORCH_CHECK(value.dim() == 2, "value: expected (B,S), got ", value.sizes());
     const int64_t B = value.size(0), S = value.size(1);
-    check_shape(value, "value", {B, S});
-    if (has(weight)) check_shape(*weight, "weight", {B, S});
+    Args args;
+    args.add(value, "value", {B, S});
+    args.add(weight, "weight", {B, S});
     TORCH_CHECK(reward.defined(), "reward: expected a tensor, got None");
     TORCH_CHECK(reward.dim() == 1 || reward.dim() == 2, "reward: expected per-token (B,S) or per-sequence (B,), got ",
                 reward.sizes());
     const bool per_seq = reward.dim() == 1;
-    if (per_seq) check_shape(reward, "reward", {B});
-    else check_shape(reward, "reward", {B, S});
-    if (has(kl)) check_shape(*kl, "kl", {B, S});
-    const at::Device dev = value.device();
-    req(value, "value", dev);
-    if (has(weight)) req(*weight, "weight", dev);
-    req(reward, "reward", dev);
-    if (has(kl)) req(*kl, "kl", dev);
+    if (per_seq) args.add(reward, "reward", {B});
+    else args.add(reward, "reward", {B, S});
+    args.add(kl, "kl", {B, S});
+    const at::Device dev = args.on_device_of(value);
     c10::DeviceGuard g(dev);
     Tensor adv = new_f32({B, S}, dev), ret = new_f32({B, S}, dev);
     const bool empty = B == 0 || S == 0;
@@ -1478,32 +1392,21 @@ struct LmPpoFn : public ag::Function<LmPpoFn> {
         const at::ScalarType st = logits_dtype(logit_new, "logit_new");
         TORCH_CHECK(logit_new.dim() == 3, "logit_new: expected (B,S,V), got ", logit_new.sizes());
         const int64_t B = logit_new.size(0), S = logit_new.size(1), V = logit_new.size(2);
-        TORCH_CHECK(old_logp.defined(), "old_logp: expected a tensor, got None");
-        check_shape(old_logp, "old_logp", {B, S});
-        check_shape(action, "action", {B, S}, at::kLong);
-        check_shape(adv, "adv", {B, S});
-        if (has(weight)) check_shape(*weight, "weight", {B, S});
+        Args args;
+        args.add(logit_new, "logit_new", {B, S, V}, st);
+        args.add(old_logp, "old_logp", {B, S});
+        args.add(action, "action", {B, S}, at::kLong);
+        args.add(adv, "adv", {B, S});
+        args.add(weight, "weight", {B, S});
         const int nval = (int)has(value_new) + (int)has(value_old) + (int)has(ret);
         TORCH_CHECK(nval == 0 || nval == 3, "lm_ppo_loss: value_new, value_old and ret are given all three or none (got ", nval,
                     " of them)");
-        if (nval) {
-            check_shape(*value_new, "value_new", {B, S});
-            check_shape(*value_old, "value_old", {B, S});
-            check_shape(*ret, "ret", {B, S});
-        }
+        args.add(value_new, "value_new", {B, S});
+        args.add(value_old, "value_old", {B, S});
+        args.add(ret, "ret", {B, S});
         TORCH_CHECK(!dual_clip.has_value() || *dual_clip > 1.0, "dual_clip: expected None or a value above 1, got ", *dual_clip);
         grpo_check_v("lm_ppo_loss", V);
-        const at::Device dev = logit_new.device();
-        req(logit_new, "logit_new", dev, st);
-        req(old_logp, "old_logp", dev);
-        req(action, "action", dev, at::kLong);
-        req(adv, "adv", dev);
-        if (has(weight)) req(*weight, "weight", dev);
-        if (nval) {
-            req(*value_new, "value_new", dev);
-            req(*value_old, "value_old", dev);
-            req(*ret, "ret", dev);
-        }
+        const at::Device dev = args.on_device_of(logit_new);
         c10::DeviceGuard g(dev);
         const bool empty = B == 0 || S == 0 || V == 0;
         Tensor out8 = new_f32({8}, dev);
@@ -1521,8 +1424,7 @@ struct LmPpoFn : public ag::Function<LmPpoFn> {
         ctx->saved_data["use_den"] = !seq_mean && !raw;
         // needs_input_grad counts the tensor inputs that are present: value_new follows the four required ones and weight
         ctx->saved_data["value_edge"] = (int64_t)(has(weight) ? 5 : 4);
-        ag::tensor_list out;
-        for (int k = 0; k < 7; ++k) out.push_back(alias_of(out8, k, 1));
+        ag::tensor_list out = split1(out8, 7);
         ctx->mark_non_differentiable({out[3], out[4], out[5], out[6]});
         return out;
     }
@@ -1558,12 +1460,45 @@ struct LmPpoFn : public ag::Function<LmPpoFn> {
 };
 
 // ==================================================================================================== q n-step TD
-struct QDims { int64_t B, N, nstep; at::Device dev; };
-int64_t check_nstep_reward(const Tensor& reward, int64_t B, const at::Device& dev) {
+// What the five one-hot n-step TD ops (q, C51, IQN, QR-DQN, FQF) share.  They check the device first, one req() per tensor.
+// The per-sample arguments that follow an op's leading tensors: action, next_n_action (B,) int64, reward (nstep,B), done (B,);
+// returns nstep.  (weight and value_gamma stay with the op: IQN and FQF check a tensor of their own before them.)
+int64_t nstep_sample_check(const Tensor& action, const Tensor& naction, const Tensor& reward, const Tensor& done, int64_t B,
+                           const at::Device& dev) {
+    req(action, "action", dev, {B}, at::kLong);
+    req(naction, "next_n_action", dev, {B}, at::kLong);
     req(reward, "reward", dev);
     TORCH_CHECK(reward.dim() == 2 && reward.size(1) == B, "reward: expected (nstep,", B, "), got ", reward.sizes());
+    req(done, "done", dev, {B});
     return reward.size(0);
 }
+// loss (1,) and td_err (B,) of a list-form forward in the order of its list, then the buffer of the unit gradient, which may
+// be larger than the `need` floats that are written.
+void td_list_outputs(const Tensor& first, const Tensor& second, bool loss_first, const Tensor& buf, const char* buf_name,
+                     int64_t need, const char* need_name, int64_t B, const at::Device& dev) {
+    req(first, loss_first ? "loss" : "td_err", dev, {loss_first ? 1 : B});
+    req(second, loss_first ? "td_err" : "loss", dev, {loss_first ? B : 1});
+    req(buf, buf_name, dev);
+    TORCH_CHECK(buf.numel() >= need, buf_name, ": ", buf.numel(), " floats, need at least ", need_name, " = ", need);
+}
+// The backward of all five: the forward saved {unit gradient, action} and N; the gradient flows to the first of the
+// `n_inputs` arguments only.  `shape(unit, N)` is that gradient's, `launch(grad_loss, unit, action, grad)` fills it.
+template <class Shape, class Launch>
+ag::tensor_list onehot_td_backward(ag::AutogradContext* ctx, const ag::tensor_list& grads, size_t n_inputs, Shape shape,
+                                   Launch launch) {
+    ag::tensor_list out(n_inputs);
+    if (!ctx->needs_input_grad(0)) return out;
+    const auto saved = ctx->get_saved_variables();
+    const Tensor &unit = saved[0], &action = saved[1];
+    const at::Device dev = unit.device();
+    c10::DeviceGuard g(dev);
+    out[0] = new_f32(shape(unit, ctx->saved_data["N"].toInt()), dev);
+    launch(grad1(grads[0], dev, "grad_loss"), unit, action, out[0]);
+    return out;
+}
+at::DimVector shape_bnx(const Tensor& unit, int64_t N) { return {unit.size(0), N, unit.size(1)}; }   // unit (B,X): gradient (B,N,X)
+
+struct QDims { int64_t B, N, nstep; at::Device dev; };
 QDims q_check(const Tensor& q, const Tensor& nq, const Tensor& action, const Tensor& naction, const Tensor& reward,
               const Tensor& done, const OptTensor& weight) {
     req(q, "q");
@@ -1571,10 +1506,7 @@ QDims q_check(const Tensor& q, const Tensor& nq, const Tensor& action, const Ten
     const int64_t B = q.size(0), N = q.size(1);
     const at::Device dev = q.device();
     req(nq, "next_n_q", dev, {B, N});
-    req(action, "action", dev, {B}, at::kLong);
-    req(naction, "next_n_action", dev, {B}, at::kLong);
-    const int64_t nstep = check_nstep_reward(reward, B, dev);
-    req(done, "done", dev, {B});
+    const int64_t nstep = nstep_sample_check(action, naction, reward, done, B, dev);
     req_opt(weight, "weight", dev, {B});
     return {B, N, nstep, dev};
 }
@@ -1636,16 +1568,8 @@ template <int RESCALE> struct QNStepFn : public ag::Function<QNStepFn<RESCALE>> 
         return {loss, td_err};
     }
     static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
-        ag::tensor_list out(9);
-        if (!ctx->needs_input_grad(0)) return out;
-        const auto saved = ctx->get_saved_variables();
-        const Tensor &grad_buf = saved[0], &action = saved[1];
-        const at::Device dev = grad_buf.device();
-        c10::DeviceGuard g(dev);
-        Tensor gq = new_f32({grad_buf.size(0), ctx->saved_data["N"].toInt()}, dev);
-        q_backward_launch(grad1(grads[0], dev, "grad_loss"), grad_buf, action, gq);
-        out[0] = gq;
-        return out;
+        return onehot_td_backward(ctx, grads, 9, [](const Tensor& gb, int64_t N) { return at::DimVector{gb.size(0), N}; },
+                                  q_backward_launch);
     }
 };
 
@@ -1658,10 +1582,7 @@ DistDims dist_check(const Tensor& dist, const Tensor& ndist, const Tensor& actio
     const int64_t B = dist.size(0), N = dist.size(1), A = dist.size(2);
     const at::Device dev = dist.device();
     req(ndist, "next_n_dist", dev, {B, N, A});
-    req(action, "action", dev, {B}, at::kLong);
-    req(naction, "next_n_action", dev, {B}, at::kLong);
-    const int64_t nstep = check_nstep_reward(reward, B, dev);
-    req(done, "done", dev, {B});
+    const int64_t nstep = nstep_sample_check(action, naction, reward, done, B, dev);
     req_opt(weight, "weight", dev, {B});
     return {B, N, A, nstep, dev};
 }
@@ -1687,10 +1608,7 @@ void DistNStepTdForward(const OptList& in, const TensorList& out, double gamma, 
     expect_len(out, 3, "DistNStepTdForward outputs");
     for (int i = 0; i < 6; ++i) TORCH_CHECK(has(in[i]), "DistNStepTdForward: inputs[", i, "] is None");
     const DistDims d = dist_check(*in[0], *in[1], *in[2], *in[3], *in[4], *in[5], in[6]);
-    req(out[0], "td_err", d.dev, {d.B});
-    req(out[1], "loss", d.dev, {1});
-    req(out[2], "buf", d.dev);
-    TORCH_CHECK(out[2].numel() >= d.B * d.A, "buf: ", out[2].numel(), " floats, need at least B*n_atom = ", d.B * d.A);
+    td_list_outputs(out[0], out[1], false, out[2], "buf", d.B * d.A, "B*n_atom", d.B, d.dev);
     c10::DeviceGuard g(d.dev);
     dist_forward_launch(d, *in[0], *in[1], *in[2], *in[3], *in[4], *in[5], in[6], out[0], out[1], out[2], gamma, v_min,
                         v_max, scale);
@@ -1730,16 +1648,7 @@ struct DistFn : public ag::Function<DistFn> {
         return {loss, td_err};
     }
     static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
-        ag::tensor_list out(11);
-        if (!ctx->needs_input_grad(0)) return out;
-        const auto saved = ctx->get_saved_variables();
-        const Tensor &buf = saved[0], &action = saved[1];
-        const at::Device dev = buf.device();
-        c10::DeviceGuard g(dev);
-        Tensor gd = new_f32({buf.size(0), ctx->saved_data["N"].toInt(), buf.size(1)}, dev);
-        dist_backward_launch(grad1(grads[0], dev, "grad_loss"), buf, action, gd);
-        out[0] = gd;
-        return out;
+        return onehot_td_backward(ctx, grads, 11, shape_bnx, dist_backward_launch);
     }
 };
 
@@ -1760,10 +1669,7 @@ IqnDims iqn_check(const Tensor& q, const Tensor& nq, const Tensor& action, const
         TORCH_CHECK(nq.dim() == 3 && nq.size(1) == B && nq.size(2) == N, "next_n_q: shape ", nq.sizes(), ", expected (tau',",
                     B, ",", N, ")");
     }
-    req(action, "action", dev, {B}, at::kLong);
-    req(naction, "next_n_action", dev, {B}, at::kLong);
-    const int64_t nstep = check_nstep_reward(reward, B, dev);
-    req(done, "done", dev, {B});
+    const int64_t nstep = nstep_sample_check(action, naction, reward, done, B, dev);
     req(rq, "replay_quantiles", dev);
     TORCH_CHECK(rq.numel() == tau * B, "replay_quantiles: ", rq.sizes(), " does not hold tau*B = ", tau * B, " values");
     req_opt(weight, "weight", dev, {B});
@@ -1795,19 +1701,20 @@ void IQNNStepTDErrorForward(const OptList& in, const TensorList& out, double gam
                 out.size());
     for (int i = 0; i < 7; ++i) TORCH_CHECK(has(in[i]), "IQNNStepTDErrorForward: inputs[", i, "] is None");
     const IqnDims d = iqn_check(*in[0], *in[1], *in[2], *in[3], *in[4], *in[5], *in[6], in[7], in[8]);
-    const Tensor& gb = out.back();
-    req(out[0], "loss", d.dev, {1});
-    req(out[1], "td_err", d.dev, {d.B});
-    req(gb, "grad_buf", d.dev);
-    TORCH_CHECK(gb.numel() >= d.B * d.tau, "grad_buf: ", gb.numel(), " floats, need at least B*tau = ", d.B * d.tau);
+    td_list_outputs(out[0], out[1], true, out.back(), "grad_buf", d.B * d.tau, "B*tau", d.B, d.dev);
     c10::DeviceGuard g(d.dev);
-    iqn_forward_launch(d, *in[0], *in[1], *in[2], *in[3], *in[4], *in[5], *in[6], in[7], in[8], out[0], out[1], gb, gamma,
-                       kappa, scale);
+    iqn_forward_launch(d, *in[0], *in[1], *in[2], *in[3], *in[4], *in[5], *in[6], in[7], in[8], out[0], out[1], out.back(),
+                       gamma, kappa, scale);
 }
 void iqn_backward_launch(const Tensor& gl, const Tensor& grad_buf, const Tensor& action, const Tensor& grad_q) {
     check(hpc_rll_iqn_nstep_td_backward(fptr(gl), fptr(grad_buf), iptr(action), fmut(grad_q), (int)grad_q.size(0),
                                         (int)grad_q.size(1), (int)grad_q.size(2), stream_of(grad_q.device())),
           "hpc_rll_iqn_nstep_td_backward");
+}
+void iqn_backward_bnt_launch(const Tensor& gl, const Tensor& grad_buf, const Tensor& action, const Tensor& grad_q) {   // (B,N,tau)
+    check(hpc_rll_iqn_nstep_td_backward_bnt(fptr(gl), fptr(grad_buf), iptr(action), fmut(grad_q), (int)grad_q.size(2),
+                                            (int)grad_q.size(0), (int)grad_q.size(1), stream_of(grad_q.device())),
+          "hpc_rll_iqn_nstep_td_backward_bnt");
 }
 // inputs = [grad_loss, grad_buf, action] or the reference's [grad_loss, grad_buf, weight, action] (td.py:382; the
 // weight is already folded into grad_buf); outputs = [grad_q (tau,B,N)].  iqn_nstep_td_error.cu:74-104.
@@ -1842,25 +1749,9 @@ struct IqnFn : public ag::Function<IqnFn> {
         return {loss, td_err};
     }
     static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
-        ag::tensor_list out(13);
-        if (!ctx->needs_input_grad(0)) return out;
-        const auto saved = ctx->get_saved_variables();
-        const Tensor &grad_buf = saved[0], &action = saved[1];
-        const at::Device dev = grad_buf.device();
-        c10::DeviceGuard g(dev);
-        if (ctx->saved_data["bnt"].toBool()) {   // grad_q (B,N,tau): one-hot rows of tau values
-            const int64_t B = grad_buf.size(0), tau = grad_buf.size(1), N = ctx->saved_data["N"].toInt();
-            Tensor gq = new_f32({B, N, tau}, dev);
-            check(hpc_rll_iqn_nstep_td_backward_bnt(fptr(grad1(grads[0], dev, "grad_loss")), fptr(grad_buf), iptr(action), fmut(gq),
-                                                    (int)tau, (int)B, (int)N, stream_of(dev)),
-                  "hpc_rll_iqn_nstep_td_backward_bnt");
-            out[0] = gq;
-            return out;
-        }
-        Tensor gq = new_f32({grad_buf.size(1), grad_buf.size(0), ctx->saved_data["N"].toInt()}, dev);
-        iqn_backward_launch(grad1(grads[0], dev, "grad_loss"), grad_buf, action, gq);
-        out[0] = gq;
-        return out;
+        if (ctx->saved_data["bnt"].toBool()) return onehot_td_backward(ctx, grads, 13, shape_bnx, iqn_backward_bnt_launch);
+        return onehot_td_backward(ctx, grads, 13, [](const Tensor& gb, int64_t N) { return at::DimVector{gb.size(1), gb.size(0), N}; },
+                                  iqn_backward_launch);
     }
 };
 
@@ -1873,10 +1764,7 @@ QrDims qr_check(const Tensor& q, const Tensor& nq, const Tensor& action, const T
     const int64_t B = q.size(0), N = q.size(1), tau = q.size(2);
     const at::Device dev = q.device();
     req(nq, "next_n_q", dev, {B, N, tau});
-    req(action, "action", dev, {B}, at::kLong);
-    req(naction, "next_n_action", dev, {B}, at::kLong);
-    const int64_t nstep = check_nstep_reward(reward, B, dev);
-    req(done, "done", dev, {B});
+    const int64_t nstep = nstep_sample_check(action, naction, reward, done, B, dev);
     req_opt(weight, "weight", dev, {B});
     req_opt(vg, "value_gamma", dev, {B});
     return {B, N, tau, nstep, dev};
@@ -1905,13 +1793,9 @@ void QRDQNNStepTDErrorForward(const OptList& in, const TensorList& out, double g
                 out.size());
     for (int i = 0; i < 6; ++i) TORCH_CHECK(has(in[i]), "QRDQNNStepTDErrorForward: inputs[", i, "] is None");
     const QrDims d = qr_check(*in[0], *in[1], *in[2], *in[3], *in[4], *in[5], in[6], in[7]);
-    const Tensor& gb = out.back();
-    req(out[0], "loss", d.dev, {1});
-    req(out[1], "td_err", d.dev, {d.B});
-    req(gb, "grad_buf", d.dev);
-    TORCH_CHECK(gb.numel() >= d.B * d.tau, "grad_buf: ", gb.numel(), " floats, need at least B*tau = ", d.B * d.tau);
+    td_list_outputs(out[0], out[1], true, out.back(), "grad_buf", d.B * d.tau, "B*tau", d.B, d.dev);
     c10::DeviceGuard g(d.dev);
-    qr_forward_launch(d, *in[0], *in[1], *in[2], *in[3], *in[4], *in[5], in[6], in[7], out[0], out[1], gb, gamma,
+    qr_forward_launch(d, *in[0], *in[1], *in[2], *in[3], *in[4], *in[5], in[6], in[7], out[0], out[1], out.back(), gamma,
                       tau_value, scale);
 }
 void qr_backward_launch(const Tensor& gl, const Tensor& grad_buf, const Tensor& action, const Tensor& grad_q) {
@@ -1951,16 +1835,7 @@ struct QrFn : public ag::Function<QrFn> {
         return {loss, td_err};
     }
     static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
-        ag::tensor_list out(11);
-        if (!ctx->needs_input_grad(0)) return out;
-        const auto saved = ctx->get_saved_variables();
-        const Tensor &grad_buf = saved[0], &action = saved[1];
-        const at::Device dev = grad_buf.device();
-        c10::DeviceGuard g(dev);
-        Tensor gq = new_f32({grad_buf.size(0), ctx->saved_data["N"].toInt(), grad_buf.size(1)}, dev);
-        qr_backward_launch(grad1(grads[0], dev, "grad_loss"), grad_buf, action, gq);
-        out[0] = gq;
-        return out;
+        return onehot_td_backward(ctx, grads, 11, shape_bnx, qr_backward_launch);
     }
 };
 
@@ -2010,10 +1885,7 @@ FqfDims fqf_td_check(const Tensor& q, const Tensor& nq, const Tensor& action, co
     req(nq, "next_n_q", dev);
     TORCH_CHECK(nq.dim() == 3 && nq.size(0) == B && nq.size(1) >= 1 && nq.size(2) == N, "next_n_q: shape ", nq.sizes(),
                 ", expected (", B, ",K',", N, ")");
-    req(action, "action", dev, {B}, at::kLong);
-    req(naction, "next_n_action", dev, {B}, at::kLong);
-    const int64_t nstep = check_nstep_reward(reward, B, dev);
-    req(done, "done", dev, {B});
+    const int64_t nstep = nstep_sample_check(action, naction, reward, done, B, dev);
     req(qh, "quantiles_hats", dev, {B, K});
     req_opt(weight, "weight", dev, {B});
     req_opt(vg, "value_gamma", dev, {B});
@@ -2041,19 +1913,13 @@ struct FqfTdFn : public ag::Function<FqfTdFn> {
         return {loss, td_err};
     }
     static ag::tensor_list backward(ag::AutogradContext* ctx, ag::tensor_list grads) {
-        ag::tensor_list out(12);
-        if (!ctx->needs_input_grad(0)) return out;
-        const auto saved = ctx->get_saved_variables();
-        const Tensor &grad_buf = saved[0], &action = saved[1];
-        const at::Device dev = grad_buf.device();
-        c10::DeviceGuard g(dev);
-        const int64_t B = grad_buf.size(0), K = grad_buf.size(1), N = ctx->saved_data["N"].toInt();
-        Tensor gq = new_f32({B, K, N}, dev);
-        check(hpc_rll_fqf_nstep_td_backward(fptr(grad1(grads[0], dev, "grad_loss")), fptr(grad_buf), iptr(action), fmut(gq), (int)K,
-                                            (int)B, (int)N, stream_of(dev)),
-              "hpc_rll_fqf_nstep_td_backward");
-        out[0] = gq;
-        return out;
+        return onehot_td_backward(
+            ctx, grads, 12, [](const Tensor& gb, int64_t N) { return at::DimVector{gb.size(0), gb.size(1), N}; },
+            [](const Tensor& gl, const Tensor& gb, const Tensor& action, const Tensor& gq) {   // gq (B,K,N)
+                check(hpc_rll_fqf_nstep_td_backward(fptr(gl), fptr(gb), iptr(action), fmut(gq), (int)gq.size(1), (int)gq.size(0),
+                                                    (int)gq.size(2), stream_of(gq.device())),
+                      "hpc_rll_fqf_nstep_td_backward");
+            });
     }
 };
 
@@ -2161,14 +2027,11 @@ PYBIND11_MODULE(hpc_rl_utils, m) {
     bind_padding(m);      // Pad / GroupPad / Unpad {1,2,3}D, split policies, packed variants
 
     // ---- fused autograd ops (what hpc_rll.rl_utils.* calls)
-    m.def("gae", [](const Tensor& value, const Tensor& reward, double gamma, double lambda) {
-        return GaeFn::apply(value, reward, gamma, lambda);
-    }, py::arg("value"), py::arg("reward"), py::arg("gamma") = 0.99, py::arg("lambda_") = 0.97,
+    m.def("gae", applier<GaeFn>(&GaeFn::forward),
+          py::arg("value"), py::arg("reward"), py::arg("gamma") = 0.99, py::arg("lambda_") = 0.97,
           "adv = GAE(value (T+1,B), reward (T,B)); differentiable wrt value and reward");
-    m.def("gae_masked", [](const Tensor& value, const Tensor& reward, const OptTensor& done, const OptTensor& traj_flag,
-                           const OptTensor& next_value, double gamma, double lambda) {
-        return GaeMaskedFn::apply(value, reward, done, traj_flag, next_value, gamma, lambda);
-    }, py::arg("value"), py::arg("reward"), py::arg("done") = py::none(), py::arg("traj_flag") = py::none(),
+    m.def("gae_masked", applier<GaeMaskedFn>(&GaeMaskedFn::forward),
+          py::arg("value"), py::arg("reward"), py::arg("done") = py::none(), py::arg("traj_flag") = py::none(),
           py::arg("next_value") = py::none(), py::arg("gamma") = 0.99, py::arg("lambda_") = 0.97,
           "adv = textbook GAE with done / traj_flag masks; value (T+1,B), or value (T,B) with next_value (T,B); "
           "differentiable wrt value, next_value and reward");
@@ -2177,80 +2040,47 @@ PYBIND11_MODULE(hpc_rl_utils, m) {
         c10::DeviceGuard g(dev);
         return gae_coef(T, gamma, lambda, dev);
     });
-    m.def("td_lambda_masked", [](const Tensor& value, const Tensor& reward, const OptTensor& done,
-                                 const OptTensor& traj_flag, const OptTensor& next_value, const OptTensor& weight,
-                                 double gamma, double lambda, std::optional<double> scale) {
-        return TdLambdaMaskedFn::apply(value, reward, done, traj_flag, next_value, weight, gamma, lambda, scale);
-    }, py::arg("value"), py::arg("reward"), py::arg("done") = py::none(), py::arg("traj_flag") = py::none(),
+    m.def("td_lambda_masked", applier<TdLambdaMaskedFn>(&TdLambdaMaskedFn::forward),
+          py::arg("value"), py::arg("reward"), py::arg("done") = py::none(), py::arg("traj_flag") = py::none(),
           py::arg("next_value") = py::none(), py::arg("weight") = py::none(), py::arg("gamma") = 0.9,
           py::arg("lambda_") = 0.8, py::arg("scale") = py::none(),
           "episode-aware TD(lambda) loss (1,) with done / traj_flag masks; differentiable wrt value");
-    m.def("vtrace_masked", [](const Tensor& target, const Tensor& behaviour, const Tensor& action, const Tensor& value,
-                              const Tensor& reward, const OptTensor& done, const OptTensor& traj_flag,
-                              const OptTensor& next_value, const OptTensor& weight, double gamma, double lambda,
-                              double rho_clip, double c_clip, double rho_pg_clip, std::optional<double> scale) {
-        return VtraceMaskedFn::apply(target, behaviour, action, value, reward, done, traj_flag, next_value, weight, gamma,
-                                     lambda, rho_clip, c_clip, rho_pg_clip, scale);
-    }, py::arg("target_output"), py::arg("behaviour_output"), py::arg("action"), py::arg("value"), py::arg("reward"),
+    m.def("vtrace_masked", applier<VtraceMaskedFn>(&VtraceMaskedFn::forward),
+          py::arg("target_output"), py::arg("behaviour_output"), py::arg("action"), py::arg("value"), py::arg("reward"),
           py::arg("done") = py::none(), py::arg("traj_flag") = py::none(), py::arg("next_value") = py::none(),
           py::arg("weight") = py::none(), py::arg("gamma") = 0.99, py::arg("lambda_") = 0.95,
           py::arg("rho_clip_ratio") = 1.0, py::arg("c_clip_ratio") = 1.0, py::arg("rho_pg_clip_ratio") = 1.0,
           py::arg("scale") = py::none(),
           "episode-aware V-trace losses (policy, value, entropy) with done / traj_flag masks");
-    m.def("td_lambda", [](const Tensor& value, const Tensor& reward, const OptTensor& weight, double gamma, double lambda,
-                          std::optional<double> scale) {
-        return TdLambdaFn::apply(value, reward, weight, gamma, lambda, scale);
-    }, py::arg("value"), py::arg("reward"), py::arg("weight") = py::none(), py::arg("gamma") = 0.9,
+    m.def("td_lambda", applier<TdLambdaFn>(&TdLambdaFn::forward),
+          py::arg("value"), py::arg("reward"), py::arg("weight") = py::none(), py::arg("gamma") = 0.9,
           py::arg("lambda_") = 0.8, py::arg("scale") = py::none());
-    m.def("vtrace", [](const Tensor& target, const Tensor& behaviour, const Tensor& action, const Tensor& value,
-                       const Tensor& reward, const OptTensor& weight, double gamma, double lambda, double rho_clip,
-                       double c_clip, double rho_pg_clip, std::optional<double> scale) {
-        return VtraceFn::apply(target, behaviour, action, value, reward, weight, gamma, lambda, rho_clip, c_clip,
-                               rho_pg_clip, scale);
-    }, py::arg("target_output"), py::arg("behaviour_output"), py::arg("action"), py::arg("value"), py::arg("reward"),
+    m.def("vtrace", applier<VtraceFn>(&VtraceFn::forward),
+          py::arg("target_output"), py::arg("behaviour_output"), py::arg("action"), py::arg("value"), py::arg("reward"),
           py::arg("weight") = py::none(), py::arg("gamma") = 0.99, py::arg("lambda_") = 0.95,
           py::arg("rho_clip_ratio") = 1.0, py::arg("c_clip_ratio") = 1.0, py::arg("rho_pg_clip_ratio") = 1.0,
           py::arg("scale") = py::none());
-    m.def("upgo", [](const Tensor& target, const Tensor& rho, const Tensor& action, const Tensor& reward,
-                     const Tensor& value, std::optional<double> scale) {
-        return UpgoFn::apply(target, rho, action, reward, value, scale);
-    }, py::arg("target_output"), py::arg("rhos"), py::arg("action"), py::arg("rewards"), py::arg("bootstrap_values"),
+    m.def("upgo", applier<UpgoFn>(&UpgoFn::forward),
+          py::arg("target_output"), py::arg("rhos"), py::arg("action"), py::arg("rewards"), py::arg("bootstrap_values"),
           py::arg("scale") = py::none());
-    m.def("upgo_masked", [](const Tensor& target, const Tensor& rho, const Tensor& action, const Tensor& reward,
-                            const Tensor& value, const OptTensor& done, const OptTensor& traj_flag,
-                            const OptTensor& next_value, double gamma, std::optional<double> scale) {
-        return UpgoMaskedFn::apply(target, rho, action, reward, value, done, traj_flag, next_value, gamma, scale);
-    }, py::arg("target_output"), py::arg("rhos"), py::arg("action"), py::arg("rewards"), py::arg("bootstrap_values"),
+    m.def("upgo_masked", applier<UpgoMaskedFn>(&UpgoMaskedFn::forward),
+          py::arg("target_output"), py::arg("rhos"), py::arg("action"), py::arg("rewards"), py::arg("bootstrap_values"),
           py::arg("done") = py::none(), py::arg("traj_flag") = py::none(), py::arg("next_value") = py::none(),
           py::arg("gamma") = 1.0, py::arg("scale") = py::none(),
           "episode-aware UPGO loss (1,) with done / traj_flag masks; differentiable wrt target_output");
-    m.def("ppo", [](const Tensor& ln, const Tensor& lo, const Tensor& action, const Tensor& vn, const Tensor& vo,
-                    const Tensor& adv, const Tensor& ret, const OptTensor& weight, double clip_ratio, bool use_value_clip,
-                    double dual_clip, std::optional<double> scale) {
-        return PpoFn::apply(ln, lo, action, vn, vo, adv, ret, weight, clip_ratio, use_value_clip, dual_clip, scale);
-    }, py::arg("logits_new"), py::arg("logits_old"), py::arg("action"), py::arg("value_new"), py::arg("value_old"),
+    m.def("ppo", applier<PpoFn>(&PpoFn::forward),
+          py::arg("logits_new"), py::arg("logits_old"), py::arg("action"), py::arg("value_new"), py::arg("value_old"),
           py::arg("adv"), py::arg("return_"), py::arg("weight") = py::none(), py::arg("clip_ratio") = 0.2,
           py::arg("use_value_clip") = true, py::arg("dual_clip") = 0.0, py::arg("scale") = py::none());
-    m.def("ppo_continuous", [](const Tensor& mu_new, const Tensor& sigma_new, const Tensor& mu_old, const Tensor& sigma_old,
-                               const Tensor& action, const Tensor& vn, const Tensor& vo, const Tensor& adv, const Tensor& ret,
-                               const OptTensor& weight, double clip_ratio, bool use_value_clip, double dual_clip,
-                               std::optional<double> scale) {
-        return PpoContinuousFn::apply(mu_new, sigma_new, mu_old, sigma_old, action, vn, vo, adv, ret, weight, clip_ratio,
-                                      use_value_clip, dual_clip, scale);
-    }, py::arg("mu_new"), py::arg("sigma_new"), py::arg("mu_old"), py::arg("sigma_old"), py::arg("action"),
+    m.def("ppo_continuous", applier<PpoContinuousFn>(&PpoContinuousFn::forward),
+          py::arg("mu_new"), py::arg("sigma_new"), py::arg("mu_old"), py::arg("sigma_old"), py::arg("action"),
           py::arg("value_new"), py::arg("value_old"), py::arg("adv"), py::arg("return_"), py::arg("weight") = py::none(),
           py::arg("clip_ratio") = 0.2, py::arg("use_value_clip") = true, py::arg("dual_clip") = 0.0,
           py::arg("scale") = py::none(),
           "PPO losses (policy, value, entropy, info) for a diagonal-Gaussian policy: mu / sigma / action (B,A) fp32, "
           "sigma > 0; differentiable wrt mu_new, sigma_new and value_new");
-    m.def("vtrace_continuous", [](const Tensor& mu_t, const Tensor& sigma_t, const Tensor& mu_b, const Tensor& sigma_b,
-                                  const Tensor& action, const Tensor& value, const Tensor& reward, const OptTensor& done,
-                                  const OptTensor& traj_flag, const OptTensor& next_value, const OptTensor& weight,
-                                  double gamma, double lambda, double rho_clip, double c_clip, double rho_pg_clip,
-                                  std::optional<double> scale) {
-        return VtraceContinuousFn::apply(mu_t, sigma_t, mu_b, sigma_b, action, value, reward, done, traj_flag, next_value,
-                                         weight, gamma, lambda, rho_clip, c_clip, rho_pg_clip, scale);
-    }, py::arg("mu_target"), py::arg("sigma_target"), py::arg("mu_behaviour"), py::arg("sigma_behaviour"), py::arg("action"),
+    m.def("vtrace_continuous", applier<VtraceContinuousFn>(&VtraceContinuousFn::forward),
+          py::arg("mu_target"), py::arg("sigma_target"), py::arg("mu_behaviour"), py::arg("sigma_behaviour"), py::arg("action"),
           py::arg("value"), py::arg("reward"), py::arg("done") = py::none(), py::arg("traj_flag") = py::none(),
           py::arg("next_value") = py::none(), py::arg("weight") = py::none(), py::arg("gamma") = 0.99,
           py::arg("lambda_") = 0.95, py::arg("rho_clip_ratio") = 1.0, py::arg("c_clip_ratio") = 1.0,
@@ -2260,11 +2090,8 @@ PYBIND11_MODULE(hpc_rl_utils, m) {
     m.def("retrace", &retrace_targets, py::arg("q_values"), py::arg("v_pred"), py::arg("rewards"), py::arg("actions"),
           py::arg("weights"), py::arg("ratio"), py::arg("gamma") = 0.9, py::arg("lambda_") = 1.0,
           "Retrace(lambda) Q targets (T+1,B,1) from given state values (T+1,B,1) and importance ratios (T,B,N); no gradient");
-    m.def("retrace_loss", [](const Tensor& q, const Tensor& target, const Tensor& behaviour, const Tensor& action,
-                             const Tensor& reward, const OptTensor& weights, const OptTensor& loss_weight, double gamma,
-                             double lambda, std::optional<double> scale) {
-        return RetraceLossFn::apply(q, target, behaviour, action, reward, weights, loss_weight, gamma, lambda, scale);
-    }, py::arg("q_values"), py::arg("target_output"), py::arg("behaviour_output"), py::arg("action"), py::arg("reward"),
+    m.def("retrace_loss", applier<RetraceLossFn>(&RetraceLossFn::forward),
+          py::arg("q_values"), py::arg("target_output"), py::arg("behaviour_output"), py::arg("action"), py::arg("reward"),
           py::arg("weights") = py::none(), py::arg("loss_weight") = py::none(), py::arg("gamma") = 0.9,
           py::arg("lambda_") = 1.0, py::arg("scale") = py::none(),
           "Retrace(lambda) critic loss (1,), Q targets (T+1,B) and state values (T+1,B) from q_values and the two policies' "
@@ -2297,12 +2124,8 @@ PYBIND11_MODULE(hpc_rl_utils, m) {
           py::arg("scales") = py::none(),
           "COMA losses (policy, q_value, entropy; (1,) each) from (T,B,A,N) logits and action values, (T,B,A) int64 actions "
           "and (T,B) rewards; differentiable wrt logit and q_value; scales = (scale_pe, scale_q) for a sharded caller");
-    m.def("r2d2_td", [](const Tensor& q, const Tensor& target_q, const Tensor& action, const Tensor& reward,
-                        const OptTensor& done, const OptTensor& weight, double gamma, int64_t nstep, int64_t burnin,
-                        bool value_rescale, bool double_q, double priority_eta, std::optional<double> scale) {
-        return R2d2Fn::apply(q, target_q, action, reward, done, weight, gamma, nstep, burnin, value_rescale, double_q,
-                             priority_eta, scale);
-    }, py::arg("q"), py::arg("target_q"), py::arg("action"), py::arg("reward"), py::arg("done") = py::none(),
+    m.def("r2d2_td", applier<R2d2Fn>(&R2d2Fn::forward),
+          py::arg("q"), py::arg("target_q"), py::arg("action"), py::arg("reward"), py::arg("done") = py::none(),
           py::arg("weight") = py::none(), py::arg("gamma") = 0.997, py::arg("nstep") = 5, py::arg("burnin") = 0,
           py::arg("value_rescale") = true, py::arg("double_q") = true, py::arg("priority_eta") = 0.9,
           py::arg("scale") = py::none(),
@@ -2324,32 +2147,22 @@ PYBIND11_MODULE(hpc_rl_utils, m) {
           "td_error, target_q (...)); q2 / target_q2 both tensors or both None (twin_critic_loss is then 0); alpha_tensor, a "
           "1-element fp32 GPU tensor, replaces alpha and is read on the device; differentiable wrt logit, q1 and q2; "
           "scale = 1/(global rows) for a sharded caller");
-    m.def("token_log_prob", [](const Tensor& logits, const Tensor& action) { return TokenLogpFn::apply(logits, action); },
-          py::arg("logits"), py::arg("action"),
+    m.def("token_log_prob", applier<TokenLogpFn>(&TokenLogpFn::forward), py::arg("logits"), py::arg("action"),
           "logits[..., a] - logsumexp(logits) per token: (..., V) fp32 or bf16 logits, (...) int64 actions -> (...) fp32; "
           "differentiable wrt logits");
-    m.def("grpo_policy_loss", [](const Tensor& logit_new, const Tensor& old, const OptTensor& ref, const Tensor& action,
-                                 const Tensor& adv, const OptTensor& weight, double clip_ratio, double beta,
-                                 std::optional<double> scale) {
-        return GrpoFn::apply(logit_new, old, ref, action, adv, weight, clip_ratio, beta, scale);
-    }, py::arg("logit_new"), py::arg("old"), py::arg("ref"), py::arg("action"), py::arg("adv"),
+    m.def("grpo_policy_loss", applier<GrpoFn>(&GrpoFn::forward),
+          py::arg("logit_new"), py::arg("old"), py::arg("ref"), py::arg("action"), py::arg("adv"),
           py::arg("weight") = py::none(), py::arg("clip_ratio") = 0.2, py::arg("beta") = 0.1, py::arg("scale") = py::none(),
           "GRPO token loss over (B,S,V) logits: (loss, mean_kl, mean_ratio, mean_clipped), (1,) each; old / ref are logits "
           "(B,S,V) or log-probs (B,S), ref may be None; differentiable wrt logit_new; scale = 1/(global B) for a sharded caller");
-    m.def("token_log_prob_entropy", [](const Tensor& logits, const Tensor& action, const OptTensor& weight) {
-        return TokenLpeFn::apply(logits, action, weight);
-    }, py::arg("logits"), py::arg("action"), py::arg("weight") = py::none(),
+    m.def("token_log_prob_entropy", applier<TokenLpeFn>(&TokenLpeFn::forward),
+          py::arg("logits"), py::arg("action"), py::arg("weight") = py::none(),
           "(logp, entropy) per token from one read of (..., V) fp32 or bf16 logits; both differentiable wrt logits");
     m.def("lm_gae", &lm_gae, py::arg("value"), py::arg("weight"), py::arg("reward"), py::arg("kl") = py::none(),
           py::arg("beta") = 0.0, py::arg("gamma") = 1.0, py::arg("lam") = 0.95, py::arg("whiten") = true,
           "Token-level GAE over (B,S) under a response mask: (adv, ret); reward is (B,S) or a terminal score (B,)");
-    m.def("lm_ppo_loss", [](const Tensor& logit_new, const Tensor& old_logp, const Tensor& action, const Tensor& adv,
-                            const OptTensor& weight, const OptTensor& value_new, const OptTensor& value_old,
-                            const OptTensor& ret, double clip_ratio, std::optional<double> dual_clip,
-                            std::optional<double> value_clip, bool seq_mean, bool raw, std::optional<double> scale) {
-        return LmPpoFn::apply(logit_new, old_logp, action, adv, weight, value_new, value_old, ret, clip_ratio, dual_clip,
-                              value_clip, seq_mean, raw, scale);
-    }, py::arg("logit_new"), py::arg("old_logp"), py::arg("action"), py::arg("adv"), py::arg("weight") = py::none(),
+    m.def("lm_ppo_loss", applier<LmPpoFn>(&LmPpoFn::forward),
+          py::arg("logit_new"), py::arg("old_logp"), py::arg("action"), py::arg("adv"), py::arg("weight") = py::none(),
           py::arg("value_new") = py::none(), py::arg("value_old") = py::none(), py::arg("ret") = py::none(),
           py::arg("clip_ratio") = 0.2, py::arg("dual_clip") = py::none(), py::arg("value_clip") = 0.2,
           py::arg("seq_mean") = false, py::arg("raw") = false, py::arg("scale") = py::none(),
@@ -2363,43 +2176,29 @@ PYBIND11_MODULE(hpc_rl_utils, m) {
                        : QNStepFn<0>::apply(q, nq, action, naction, reward, done, weight, gamma, scale);
     }, py::arg("q"), py::arg("next_n_q"), py::arg("action"), py::arg("next_n_action"), py::arg("reward"), py::arg("done"),
           py::arg("weight"), py::arg("gamma"), py::arg("rescale") = false, py::arg("scale") = py::none());
-    m.def("dist_nstep_td", [](const Tensor& dist, const Tensor& ndist, const Tensor& action, const Tensor& naction,
-                              const Tensor& reward, const Tensor& done, const OptTensor& weight, double gamma,
-                              double v_min, double v_max, std::optional<double> scale) {
-        return DistFn::apply(dist, ndist, action, naction, reward, done, weight, gamma, v_min, v_max, scale);
-    }, py::arg("dist"), py::arg("next_n_dist"), py::arg("action"), py::arg("next_n_action"), py::arg("reward"),
+    m.def("dist_nstep_td", applier<DistFn>(&DistFn::forward),
+          py::arg("dist"), py::arg("next_n_dist"), py::arg("action"), py::arg("next_n_action"), py::arg("reward"),
           py::arg("done"), py::arg("weight"), py::arg("gamma"), py::arg("v_min"), py::arg("v_max"),
           py::arg("scale") = py::none());
-    m.def("iqn_nstep_td", [](const Tensor& q, const Tensor& nq, const Tensor& action, const Tensor& naction,
-                             const Tensor& reward, const Tensor& done, const Tensor& rq, const OptTensor& weight,
-                             const OptTensor& vg, double gamma, double kappa, std::optional<double> scale, bool bnt) {
-        return IqnFn::apply(q, nq, action, naction, reward, done, rq, weight, vg, gamma, kappa, scale, bnt);
-    }, py::arg("q"), py::arg("next_n_q"), py::arg("action"), py::arg("next_n_action"), py::arg("reward"), py::arg("done"),
+    m.def("iqn_nstep_td", applier<IqnFn>(&IqnFn::forward),
+          py::arg("q"), py::arg("next_n_q"), py::arg("action"), py::arg("next_n_action"), py::arg("reward"), py::arg("done"),
           py::arg("replay_quantiles"), py::arg("weight") = py::none(), py::arg("value_gamma") = py::none(),
           py::arg("gamma") = 0.99, py::arg("kappa") = 1.0, py::arg("scale") = py::none(), py::arg("bnt") = false);
-    m.def("qrdqn_nstep_td", [](const Tensor& q, const Tensor& nq, const Tensor& action, const Tensor& naction,
-                               const Tensor& reward, const Tensor& done, const OptTensor& weight, const OptTensor& vg,
-                               double gamma, std::optional<double> tau_value, std::optional<double> scale) {
-        return QrFn::apply(q, nq, action, naction, reward, done, weight, vg, gamma, tau_value, scale);
-    }, py::arg("q"), py::arg("next_n_q"), py::arg("action"), py::arg("next_n_action"), py::arg("reward"), py::arg("done"),
+    m.def("qrdqn_nstep_td", applier<QrFn>(&QrFn::forward),
+          py::arg("q"), py::arg("next_n_q"), py::arg("action"), py::arg("next_n_action"), py::arg("reward"), py::arg("done"),
           py::arg("weight") = py::none(), py::arg("value_gamma") = py::none(), py::arg("gamma") = 0.99,
           py::arg("tau_value") = py::none(), py::arg("scale") = py::none());
-    m.def("fqf_fractions", [](const Tensor& logits) { return FqfFractionsFn::apply(logits); }, py::arg("logits"),
+    m.def("fqf_fractions", applier<FqfFractionsFn>(&FqfFractionsFn::forward), py::arg("logits"),
           "FQF fraction proposal from (B,K) logits: (quantiles (B,K+1), quantiles_hats (B,K), entropies (B,1)); quantiles and "
           "entropies are differentiable wrt logits, quantiles_hats is detached");
-    m.def("fqf_nstep_td", [](const Tensor& q, const Tensor& nq, const Tensor& action, const Tensor& naction,
-                             const Tensor& reward, const Tensor& done, const Tensor& qh, const OptTensor& weight,
-                             const OptTensor& vg, double gamma, double kappa, std::optional<double> scale) {
-        return FqfTdFn::apply(q, nq, action, naction, reward, done, qh, weight, vg, gamma, kappa, scale);
-    }, py::arg("q"), py::arg("next_n_q"), py::arg("action"), py::arg("next_n_action"), py::arg("reward"), py::arg("done"),
+    m.def("fqf_nstep_td", applier<FqfTdFn>(&FqfTdFn::forward),
+          py::arg("q"), py::arg("next_n_q"), py::arg("action"), py::arg("next_n_action"), py::arg("reward"), py::arg("done"),
           py::arg("quantiles_hats"), py::arg("weight") = py::none(), py::arg("value_gamma") = py::none(),
           py::arg("gamma") = 0.99, py::arg("kappa") = 1.0, py::arg("scale") = py::none(),
           "FQF n-step quantile TD loss on q (B,K,N), next_n_q (B,K',N), quantiles_hats (B,K): (loss (1,), td_err (B,)); "
           "differentiable wrt q; scale = 1/(global B) for a sharded caller");
-    m.def("fqf_fraction_loss", [](const Tensor& q_tau_i, const Tensor& q_value, const Tensor& quantiles, const Tensor& actions,
-                                  std::optional<double> scale) {
-        return FqfFractionLossFn::apply(q_tau_i, q_value, quantiles, actions, scale);
-    }, py::arg("q_tau_i"), py::arg("q_value"), py::arg("quantiles"), py::arg("actions"), py::arg("scale") = py::none(),
+    m.def("fqf_fraction_loss", applier<FqfFractionLossFn>(&FqfFractionLossFn::forward),
+          py::arg("q_tau_i"), py::arg("q_value"), py::arg("quantiles"), py::arg("actions"), py::arg("scale") = py::none(),
           "FQF fraction loss on q_tau_i (B,K-1,N), q_value (B,K,N), quantiles (B,K+1): loss (1,); differentiable wrt "
           "quantiles[:,1:K] only");
     m.def("fqf_q_value", &fqf_q_value, py::arg("q"), py::arg("quantiles"), py::arg("return_action") = false,

@@ -575,6 +575,16 @@ def write_api_surface():
     print("wrote", A.SNAP)
 
 
+def write_ext_signatures():
+    """tests/golden/ext_signatures.json: the pybind docstring of every callable of the three built extension modules
+    (what tests/test_ext_signatures_cpu.py compares a build against).  Names and docstrings only.  Written ONLY here."""
+    import json
+    sys.path.insert(0, os.path.join(HERE, ".."))
+    import test_ext_signatures_cpu as S
+    json.dump(S.current_signatures(), open(S.SNAP, "w"), indent=1, sort_keys=True)
+    print("wrote", S.SNAP)
+
+
 if __name__ == "__main__":
     only = set(sys.argv[1:])
     gens = dict(gae=gen_gae, td_lambda=gen_td_lambda, vtrace=gen_vtrace, upgo=gen_upgo, ppo=gen_ppo, qntd=gen_qntd,
@@ -585,4 +595,6 @@ if __name__ == "__main__":
             fn()
     if not only or "api_surface" in only:
         write_api_surface()
+    if not only or "ext_signatures" in only:
+        write_ext_signatures()
     print("all golden fixtures written and the oracle restatement agrees with hpc_rll.origin")
