@@ -2,7 +2,8 @@
 
 The drop-in API lives under the reference's own module names, which is the point of a drop-in:
 ``hpc_rll.rl_utils.*``, ``hpc_rll.torch_utils.network.*`` (Python) and the compiled extension modules ``hpc_rl_utils``,
-``hpc_torch_utils_network``, ``hpc_models``.  This module only answers "where is the native code":
+``hpc_torch_utils_network``, ``hpc_models``, and ``hpc_marl`` (the multi-agent ops, which the reference lacks).  This module
+only answers "where is the native code":
 
     di_hpc_amd.get_library()   path of libhpc_rll_hip.so (the torch-free C ABI)
     di_hpc_amd.get_include()   directory holding hpc_rll_hip.h (the C ABI header)

@@ -59,7 +59,7 @@ class Args {
         TORCH_INTERNAL_ASSERT(n_ < (int)items_.size(), "Args: more tensors than it holds");
         items_[n_++] = {&t, name};
     }
-    std::array<Item, 12> items_;
+    std::array<Item, 16> items_;   // (qmix_td declares thirteen)
     int n_ = 0;
 };
 

@@ -519,6 +519,58 @@ int hpc_rll_sac_discrete_backward(const float* g_policy, const float* g_critic, 
                                   int64_t rows, int N, void* stream);
 int hpc_rll_sac_discrete_last_config(int* out);
 
+/* QMIX: the monotonic mixing network from the hypernetworks' outputs on, and the mixed one-step TD loss of a learner (no
+ * reference counterpart; the semantics restate DI-engine's Mixer.forward and v_1step_td_error on the mixed values).  Per
+ * sample (row): agent_q (A) the agents' chosen-action values; w1 (A,E) row-major, element [a,e] at a*E + e; b1 (E); w2 (E);
+ * b2 (1) -- the RAW hypernetwork outputs, the absolute values are taken here.  The arrays hold `rows` such rows back to back.
+ *   pre_e = b1_e + sum_a q_a |w1[a,e]|,   h_e = elu(pre_e) = pre_e > 0 ? pre_e : expm1(pre_e),   q_tot = b2 + sum_e h_e |w2_e|
+ * The learner's loss takes the same five operands of the target network (target_*; they get no gradient), reward (rows),
+ * done (rows) of `mask_dtype` (HPC_RLL_MASK_U8 / HPC_RLL_MASK_F32; NULL = no episode ends), k = 1 - done, and weight (rows)
+ * (NULL = ones: an exact 1 is multiplied):
+ *   y = reward + gamma k target_q_tot  (a constant),   d = q_tot - y,   td_error = d^2 (unweighted),
+ *   loss[0] = scale sum_rows w d^2,   delta = 2 scale w d.
+ * A NaN or inf of the target side reaches y even where done = 1 (k multiplies): it poisons td_error, delta and the gradients
+ * of its own row, and the loss sum, and nothing else.
+ * Gradients from g = dL/dq_tot per row:  dpre_e = g |w2_e| (pre_e > 0 ? 1 : exp(pre_e)),  grad_b2 = g,
+ *   grad_w2_e = g h_e sgn(w2_e),  grad_b1_e = dpre_e,  grad_w1[a,e] = dpre_e q_a sgn(w1[a,e]),  grad_q_a = sum_e dpre_e |w1[a,e]|
+ * with sgn(0) = 0: an entry of w1 or w2 that is exactly 0 gets gradient exactly 0.  pre_e is accumulated in fp32; the sum over
+ * e, y and d are formed in fp64 and rounded once (td_error squares a difference of two long sums).
+ * hpc_rll_qmix_mix_forward -- one launch: q_tot (rows).  Every input float is read once, nothing else is written.
+ * hpc_rll_qmix_td_forward -- one launch: both mixes, td_error, q_tot, target_q_tot (rows each) and loss[0].
+ *   ws: hpc_rll_qmix_workspace_floats(rows) floats: delta (rows) | the partial sums.  rows == 0 zeroes loss[0] and launches
+ *   nothing.
+ * hpc_rll_qmix_backward -- one launch without atomics: every float of each given output (grad_q (rows,A), grad_w1 (rows,A,E),
+ *   grad_b1, grad_w2 (rows,E), grad_b2 (rows)) is written once.  Any output may be NULL (it is then neither computed nor
+ *   written); with all NULL nothing is launched.  g is g_rows[row] when g_rows (rows), the upstream gradient of the plain mix,
+ *   is given; otherwise delta[row] of `ws` times g_loss[0], a device scalar (NULL = 1).  pre_e is recomputed from the inputs;
+ *   w1 is read a second time when grad_w1 or grad_q is wanted.
+ * hpc_rll_qmix_last_config -- out[HPC_RLL_QMIX_CONFIG_INTS] = {
+ *    [0..6]  the last forward of either kind: launches so far, G, VEC, PL (lanes per row, floats per load, loads per lane and
+ *            E floats), R (rows per group and iteration), flags (bit 0 weight given; bits 1-2 done: 0 none, 1 bytes,
+ *            2 floats; bit 3 the TD form), workgroups,
+ *    [7..13] the backward: launches so far, G, VEC, PL, R, flags (bits 0-4 grad_q, grad_w1, grad_b1, grad_w2, grad_b2
+ *            written; bit 5 g_rows given), workgroups };
+ *   each part is {0, -1 ...} before its first launch; HPC_RLL_EINVAL for out == NULL.
+ * The 16-byte loads and stores (VEC = 4) need E % 4 == 0 and w1, b1, w2 (of both networks; in the backward also grad_w1,
+ * grad_b1, grad_w2) on 16 bytes; agent_q, b2 and the per-row arrays restrict nothing.
+ * 1 <= A <= 64 and 1 <= E <= 256, beyond that HPC_RLL_EUNSUPPORTED.  Argument errors, before any HIP call: HPC_RLL_EINVAL
+ * (null operands, then negative sizes, A <= 0, E <= 0 or an unknown mask_dtype), HPC_RLL_EALIGN (a float pointer off 4-byte
+ * alignment; a byte mask has none), then HPC_RLL_EUNSUPPORTED; then empty shapes return 0. */
+#define HPC_RLL_QMIX_CONFIG_INTS (14)
+int64_t hpc_rll_qmix_workspace_floats(int64_t rows);
+int hpc_rll_qmix_mix_forward(const float* agent_q, const float* w1, const float* b1, const float* w2, const float* b2,
+                             float* q_tot, int64_t rows, int A, int E, void* stream);
+int hpc_rll_qmix_td_forward(const float* agent_q, const float* w1, const float* b1, const float* w2, const float* b2,
+                            const float* target_agent_q, const float* target_w1, const float* target_b1,
+                            const float* target_w2, const float* target_b2, const float* reward, const void* done,
+                            int mask_dtype, const float* weight, float* loss, float* td_error, float* q_tot,
+                            float* target_q_tot, float* ws, int64_t rows, int A, int E, float gamma, float scale,
+                            void* stream);
+int hpc_rll_qmix_backward(const float* g_loss, const float* g_rows, const float* ws, const float* agent_q, const float* w1,
+                          const float* b1, const float* w2, const float* b2, float* grad_q, float* grad_w1, float* grad_b1,
+                          float* grad_w2, float* grad_b2, int64_t rows, int A, int E, void* stream);
+int hpc_rll_qmix_last_config(int* out);
+
 /* Language-model policy losses: the per-token log-probability over a large vocabulary and GRPO's clipped-ratio + k3-KL token
  * loss with per-sequence masked means (no reference counterpart; the semantics restate DI-engine's grpo_policy_error /
  * rloo_policy_error and their log_prob_utils helper).  Logits are (rows, V) of element type HPC_RLL_ELEM_F32 or
