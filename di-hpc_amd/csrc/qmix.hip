@@ -102,15 +102,9 @@ __device__ __forceinline__ void qmix_pre(const QmixSide& s, long row, int A, int
     }
 }
 
-// The sum over the group in fp64.  q_tot is a sum of up to 256 terms of both signs and the TD error squares a DIFFERENCE of two
+// The sum over the group is in fp64 (group_all_f64 of rowgroup.hpp).  q_tot is a sum of up to 256 terms of both signs and the TD error squares a DIFFERENCE of two
 // such sums: carried in fp32, the rounding of the sums alone put td_error past the project's bar wherever q_tot and its target
 // nearly cancel (measured: 1.4e-5 at A = 3, E = 100).  The stream over w1 stays fp32; this is E fp64 operations per row.
-template <int G> __device__ __forceinline__ double group_all_f64(double x) {
-#pragma unroll
-    for (int m = 1; m < G; m <<= 1) x += __shfl_xor(x, m, 64);
-    return x;
-}
-
 // q_tot of one row in every lane of its group, before it is rounded to fp32
 template <int G, int VEC, int PL>
 __device__ __forceinline__ double qmix_row(const QmixSide& s, long row, int A, int E, const QmixCols<G, VEC, PL>& cols) {

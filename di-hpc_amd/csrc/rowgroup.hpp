@@ -9,7 +9,7 @@
 // bb + k*(256/G) + gi, so for a fixed k the groups of a workgroup read consecutive rows: one contiguous span per load
 // instruction whatever G is.
 //
-// Device side: RowSlice, RowsPerIter, dpp_mov, group_all with its ops (AddOp, MaxOp, MinOp); for the softmax heads
+// Device side: RowSlice, RowsPerIter, dpp_mov, group_all with its ops (AddOp, MaxOp, MinOp), group_all_f64; for the softmax heads
 // row_max_finite (the clamped maximum), action_index (the column an action selects) and store_piece (a lane's piece of an
 // output row).
 // Host side: row_cfg (which G, VEC, E for an N), row_grid, the table of configurations the rule gives at kRow4Pieces pieces
@@ -37,6 +37,14 @@ template <int G, class Op> __device__ __forceinline__ float group_all(float x) {
     if (G >= 16) x = Op::f(x, dpp_mov<0x140>(x));  // row_mirror: lane i <-> 15-i
     if (G >= 32) x = Op::f(x, __shfl_xor(x, 16, 64));
     if (G >= 64) x = Op::f(x, __shfl_xor(x, 32, 64));
+    return x;
+}
+
+// the sum over the group in fp64, for the few per-row sums whose fp32 rounding would show (qmix.hip's q_tot, twohot.hip's
+// expectation): two 32-bit exchanges per step
+template <int G> __device__ __forceinline__ double group_all_f64(double x) {
+#pragma unroll
+    for (int m = 1; m < G; m <<= 1) x += __shfl_xor(x, m, 64);
     return x;
 }
 

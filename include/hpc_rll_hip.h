@@ -571,6 +571,66 @@ int hpc_rll_qmix_backward(const float* g_loss, const float* g_rows, const float*
                           float* grad_w2, float* grad_b2, int64_t rows, int A, int E, void* stream);
 int hpc_rll_qmix_last_config(int* out);
 
+/* Categorical value losses: value regression as classification (no reference counterpart; the semantics restate the scalar
+ * transforms and the two-hot of MuZero-style learners as LightZero writes them, DI-engine's symlog, DreamerV3's two-hot critic
+ * targets and the HL-Gauss histogram loss of Farebrother et al. 2024).  logits (rows,N) contiguous.  The support is N atoms
+ * v_i = v_min + i D, D = (v_max - v_min) / (N - 1); `transform` phi is HPC_RLL_TWOHOT_PHI_IDENTITY, _H (h of the n-step TD
+ * losses with `eps` > 0) or _SYMLOG (sign(x) log(1 + |x|)).  `target_kind` says what `target` holds:
+ *   HPC_RLL_TWOHOT_KIND_TWOHOT   target (rows) scalars y; c = clamp(phi(y), v_min, v_max), pos = (c - v_min) / D,
+ *                                lo = min(floor(pos), N - 2), w = pos - lo:  t_lo = 1 - w, t_{lo+1} = w, every other t_i = 0
+ *   HPC_RLL_TWOHOT_KIND_HLGAUSS  target (rows) scalars y; c as above, edges e_i = v_i - D/2 (i = 0..N), `sigma` > 0 in
+ *                                transformed units, F(e) = erf((e - c) / (sqrt(2) sigma)):
+ *                                t_i = (F(e_{i+1}) - F(e_i)) / (F(e_N) - F(e_0))
+ *   HPC_RLL_TWOHOT_KIND_DENSE    target (rows,N) rows of probabilities t; transform, eps, sigma, v_min, v_max are not read
+ * Per row, with p = softmax(x):  l = lse(x) - sum_i t_i x_i,  dl/dx_i = p_i - t_i.  A column with t_i == 0 adds exactly 0 to l
+ * also where x_i = -inf (a masked action).  weight (rows), NULL = ones:  loss[0] = scale sum_r w_r l_r.  A row with w_r == 0
+ * is dead: ell[r] = 0, its gradient row is zeros, and NaNs in its logits or target reach nothing.  A NaN scalar target of a
+ * live row gives a NaN ell[r], a NaN loss[0] and a NaN gradient row; a NaN in a dense target row a NaN ell[r] and loss[0] and
+ * a NaN gradient at its column; other rows are not affected.
+ * The scalars of a row (phi(y), pos, w, the HL-Gauss centre and normaliser, sum_i t_i x_i, the expectation and phi^-1) are
+ * formed in fp64 and rounded once; the row itself (maximum, exponentials, their sum, the logarithm, erff of the bin edges) is
+ * fp32.
+ * hpc_rll_twohot_ce_forward -- one launch: ell (rows), the unweighted per-row loss, and loss[0].
+ *   ws: hpc_rll_twohot_workspace_floats(rows) floats: lse (rows) | coef (rows), coef_r = scale w_r | the partial sums.
+ *   rows == 0 zeroes loss[0] and launches nothing.
+ * hpc_rll_twohot_ce_backward -- one launch without atomics: every float of grad_logits (rows,N) is written once, row r as
+ *   g_r (p - t) with p = exp(x - lse_r) and t rebuilt from the target;  g_r = g_rows[r] when g_rows (rows), the upstream
+ *   gradient of ell, is given, otherwise coef_r times g_loss[0], a device scalar (NULL = 1); dead rows (coef_r == 0) are zeros
+ *   in both forms.  `ws`, logits, target and the support are those of the forward.
+ * hpc_rll_twohot_decode -- one launch: value (rows) = phi^-1(E), E = sum_i p_i v_i, and expected (rows) = E unless NULL.
+ * hpc_rll_twohot_encode -- one launch: probs (rows,N), the two-hot or HL-Gauss rows of target (rows); a dense kind is
+ *   HPC_RLL_EINVAL.
+ * hpc_rll_twohot_last_config -- out[HPC_RLL_TWOHOT_CONFIG_INTS] = four parts of 7 ints, for the last forward, backward, decode
+ *   and encode: launches so far, G, VEC, E (lanes per row, floats per load, loads per lane and row), R (rows per group and
+ *   iteration), flags, workgroups.  flags: bits 1-2 target_kind, bits 3-4 transform (both 0 where not read); bit 0 weight
+ *   given (forward), g_rows given (backward), expected wanted (decode); bit 5 g_loss used (backward).  The encode uses no row
+ *   mapping: its G, E and R read 0.  Each part is {0, -1 ...} before its first launch; HPC_RLL_EINVAL for out == NULL.
+ * The 16-byte loads and stores (VEC = 4) need N % 4 == 0 and logits (a dense target too; in the backward grad_logits, in the
+ * encode probs) on 16 bytes; the per-row arrays restrict nothing.
+ * 2 <= N <= 1024 (1 <= N for a dense target).  Argument errors, before any HIP call and with nothing written: HPC_RLL_EINVAL
+ * (null operands, then negative rows, an unknown target_kind or transform, N below its minimum, v_max <= v_min, sigma <= 0 for
+ * HL-Gauss, eps <= 0 for h), HPC_RLL_EALIGN (a pointer off 4-byte alignment), then HPC_RLL_EUNSUPPORTED (N > 1024); then empty
+ * shapes return 0. */
+#define HPC_RLL_TWOHOT_KIND_TWOHOT (0)
+#define HPC_RLL_TWOHOT_KIND_HLGAUSS (1)
+#define HPC_RLL_TWOHOT_KIND_DENSE (2)
+#define HPC_RLL_TWOHOT_PHI_IDENTITY (0)
+#define HPC_RLL_TWOHOT_PHI_H (1)
+#define HPC_RLL_TWOHOT_PHI_SYMLOG (2)
+#define HPC_RLL_TWOHOT_CONFIG_INTS (28)
+int64_t hpc_rll_twohot_workspace_floats(int64_t rows);
+int hpc_rll_twohot_ce_forward(const float* logits, const float* target, const float* weight, float* loss, float* ell,
+                              float* ws, int64_t rows, int N, int target_kind, int transform, float eps, float sigma,
+                              float v_min, float v_max, float scale, void* stream);
+int hpc_rll_twohot_ce_backward(const float* g_loss, const float* g_rows, const float* ws, const float* logits,
+                               const float* target, float* grad_logits, int64_t rows, int N, int target_kind, int transform,
+                               float eps, float sigma, float v_min, float v_max, void* stream);
+int hpc_rll_twohot_decode(const float* logits, float* value, float* expected, int64_t rows, int N, int transform, float eps,
+                          float v_min, float v_max, void* stream);
+int hpc_rll_twohot_encode(const float* target, float* probs, int64_t rows, int N, int target_kind, int transform, float eps,
+                          float sigma, float v_min, float v_max, void* stream);
+int hpc_rll_twohot_last_config(int* out);
+
 /* Language-model policy losses: the per-token log-probability over a large vocabulary and GRPO's clipped-ratio + k3-KL token
  * loss with per-sequence masked means (no reference counterpart; the semantics restate DI-engine's grpo_policy_error /
  * rloo_policy_error and their log_prob_utils helper).  Logits are (rows, V) of element type HPC_RLL_ELEM_F32 or
