@@ -631,6 +631,79 @@ int hpc_rll_twohot_encode(const float* target, float* probs, int64_t rows, int N
                           float sigma, float v_min, float v_max, void* stream);
 int hpc_rll_twohot_last_config(int* out);
 
+/* Prioritized replay: a sum tree and a min tree over `capacity` leaves, fan-out 64, entirely in device memory (no reference
+ * counterpart; the semantics restate DI-engine's AdvancedReplayBuffer with its SumSegmentTree / MinSegmentTree).  Forward only.
+ * Every launching call runs on `stream`, never synchronises with the host and keeps nothing on the host that changes from
+ * call to call, so it can be captured in a hipGraph and replayed.
+ *
+ * STATE: one buffer of hpc_rll_per_state_bytes(capacity) bytes, addressed in 4-byte words.  depth = ceil(log64(capacity)), at
+ * least 1; level l (0 = root .. depth = leaves) has n_l = ceil(capacity / 64^(depth-l)) values and is padded to a multiple
+ * of 64 words with 0 (sum tree) or +inf (min tree), so that the 64 children of node i of level l are the words 64 i .. 64 i
+ * + 63 of level l + 1: one 256-byte read of a wave.  Order: the sum tree's levels 0..depth, the min tree's levels 0..depth,
+ * HPC_RLL_PER_SCALAR_WORDS scalars, `capacity` stamps (int32, 0 between calls).  Scalars: [0] max_priority (float, 1 after
+ * init), [1] the maximum the running update has seen (float bits), from [64] on the per-wave maxima of a batch-normalised
+ * sample.  hpc_rll_per_state_bytes is strictly increasing in capacity; hpc_rll_per_capacity_of inverts it (HPC_RLL_EINVAL for
+ * a size that is no state's).
+ * hpc_rll_per_layout -- host only: out[HPC_RLL_PER_LAYOUT_INTS] = depth, words of the state, then (offset, n_l) in words for
+ *   levels 0..4 of the sum tree, the same for the min tree ((-1, 0) for a level beyond depth), (offset, words) of the
+ *   scalars and of the stamps.
+ *
+ * LEAF: (p + eps)^alpha of a priority p, formed in fp64 and rounded to fp32, at most 1e30; alpha = 1 and alpha = 0 are exact
+ * (p + eps and 1).  A priority that is negative, NaN or infinite is replaced by max_priority as it was BEFORE the call.  After
+ * the call max_priority is the larger of its old value and the finite, non-negative priorities of the call's in-range
+ * entries (the losers of duplicates included).  A leaf never written is 0 in the sum tree; the min tree holds +inf for a
+ * leaf that is 0.
+ * NODE: recomputed from its 64 children c_0..c_63, never adjusted: the inclusive prefixes P_j are what the steps s = 1, 2, 4,
+ * 8, 16, 32 of `x_j += x_{j-s} for j >= s` (all j at once, fp32) leave in x_j, and the node is P_63, that is
+ * ((c_0+c_1)+(c_2+c_3))+... pairwise over neighbours, 6 roundings deep.  The min is exact in any order.  Integer leaves with a
+ * total below 2^24 make every node and prefix exact; otherwise a node or prefix is within 48 * 2^-24 of the total.
+ *
+ * hpc_rll_per_init -- one launch: every leaf unwritten, max_priority = 1.
+ * hpc_rll_per_update -- leaf idx[k] = leaf(priority[k]) for k < M, priority == NULL: leaf(max_priority).  Of several k with
+ *   one index the highest k wins; an index outside [0, capacity) is skipped.  2 + depth launches: stamps (integer atomicMax of
+ *   k + 1), leaves (written where the stamp is k + 1, which clears it), then levels depth-1 .. 0, in each of which a wave
+ *   recomputes the sum and min of one parent: the parents of the M entries (an entry whose predecessor has the same parent
+ *   leaves it to the predecessor), or every node of the level when it has no more than M.  No float atomics: same bits on
+ *   every run.
+ * hpc_rll_per_rebuild -- the whole index from priority (capacity): leaf i = leaf(priority[i]) for a finite priority >= 0,
+ *   unwritten otherwise; max_priority = max(1, those priorities).  2 + depth launches (init, leaves, one per level over all
+ *   its nodes).  The same bits as hpc_rll_per_init followed by updates that leave the same leaves.
+ * hpc_rll_per_sample -- one wave per sample.  u (B) in [0,1), NaN counts as 0.  total = the root.  Target mass m = ((k +
+ *   u_k) / B) total (stratified != 0) or u_k total, formed in fp64 and rounded to fp32.  At each node, from the root: j = the
+ *   smallest with m < P_j and c_j > 0, or the last with c_j > 0 if there is none; then m = m - P_{j-1} (P_{-1} = 0) clamped
+ *   into [0, c_j), and child j is the next node.  idx (B) int64 = the leaf reached, always one with a positive value; prob =
+ *   leaf / total; weight = (size prob)^-beta, where size = *size_dev when size_dev != NULL and `size` otherwise.  normalize
+ *   HPC_RLL_PER_NORM_BUFFER divides by (size min_leaf / total)^-beta with min_leaf the min tree's root, that is weight = (leaf
+ *   / min_leaf)^-beta <= 1, HPC_RLL_PER_NORM_BATCH by the batch's largest weight (a second launch over the per-wave maxima),
+ *   _NONE by nothing.  x^-beta is exp2(-beta log2 x) in fp32 (1 for beta = 0), within 4e-6 relative for |beta log2 x| <= 30.  A root
+ *   that is not a positive finite number gives idx = -1, prob = weight = 0.  weight and prob may each be NULL.
+ * hpc_rll_per_last_config -- out[HPC_RLL_PER_CONFIG_INTS] = two parts of 6 ints, for the last update (or rebuild) and the
+ *   last sample: calls that launched so far, kernel, depth, workgroups of the first tree launch, launches of the call, flags.
+ *   Update: kernel 0 = every level below the root through the touched parents, 1 = at least one of them recomputed in full,
+ *   2 = rebuild; flags = bit l set when level l was recomputed in full (bit 0, the root, always: it is one parent either way).  Sample: kernel = normalize, flags = bit 0 stratified, bit 1 weight
+ *   wanted, bit 2 prob wanted, bit 3 size read from the device.  {0, -1 ...} before the first launch.
+ * Argument errors, before any HIP call and with nothing written: HPC_RLL_EINVAL (null operands, then capacity < 1, M or B
+ * negative or past 2^31 - 2, alpha or eps negative or NaN, beta negative or NaN, a host size < 1, an unknown normalize),
+ * HPC_RLL_EALIGN (a pointer off 4-byte alignment, idx or size_dev off 8), then HPC_RLL_EUNSUPPORTED (capacity > 2^24); then
+ * M == 0 or B == 0 return 0 without a launch. */
+#define HPC_RLL_PER_NORM_NONE (0)
+#define HPC_RLL_PER_NORM_BUFFER (1)
+#define HPC_RLL_PER_NORM_BATCH (2)
+#define HPC_RLL_PER_MAX_CAPACITY (16777216)
+#define HPC_RLL_PER_SCALAR_WORDS (8256)
+#define HPC_RLL_PER_LAYOUT_INTS (26)
+#define HPC_RLL_PER_CONFIG_INTS (12)
+int64_t hpc_rll_per_state_bytes(int64_t capacity);
+int64_t hpc_rll_per_capacity_of(int64_t state_bytes);
+int hpc_rll_per_layout(int64_t capacity, int64_t* out);
+int hpc_rll_per_init(void* state, int64_t capacity, void* stream);
+int hpc_rll_per_update(void* state, int64_t capacity, const int64_t* idx, const float* priority, int64_t M, float alpha,
+                       float eps, void* stream);
+int hpc_rll_per_rebuild(void* state, int64_t capacity, const float* priority, float alpha, float eps, void* stream);
+int hpc_rll_per_sample(void* state, int64_t capacity, const float* u, int64_t* idx, float* weight, float* prob, int64_t B,
+                       int stratified, int normalize, float beta, int64_t size, const int64_t* size_dev, void* stream);
+int hpc_rll_per_last_config(int* out);
+
 /* Language-model policy losses: the per-token log-probability over a large vocabulary and GRPO's clipped-ratio + k3-KL token
  * loss with per-sequence masked means (no reference counterpart; the semantics restate DI-engine's grpo_policy_error /
  * rloo_policy_error and their log_prob_utils helper).  Logits are (rows, V) of element type HPC_RLL_ELEM_F32 or
