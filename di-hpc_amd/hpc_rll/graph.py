@@ -17,6 +17,14 @@ Constraints (those of stream capture): the module's forward must not synchronise
 python floats by default (``.tolist()``, reference rl_utils/ppo.py:148); construct it with ``PPO(B, N, sync_info=False)``
 (monitors stay device tensors) to capture it; shapes are fixed at capture time.
 The extension's own caches are capture-safe (a cold ``gae_coef`` table is filled inside the capture).
+Verified capturable, with replays on refilled buffers giving the bits of the eager call (tests/test_graphed_ops_gpu.py):
+``QNStepTD``, ``QNStepTDRescale``, ``DistNStepTD``, ``IQNNStepTDError`` (both layouts), ``QRDQNNStepTDError``, ``TDLambda``,
+``FQFNStepTDError`` with ``fqf_fractions`` and ``fqf_calculate_fraction_loss``, ``UPGO``, ``MaskedUPGO``, ``Retrace``,
+``ACERPolicy``, ``COMA``, ``SACDiscrete``, ``GRPO``, ``LMPPO`` with ``token_log_prob_entropy`` and ``lm_gae``, ``MuZeroLoss`` and
+``ScatterConnection``; the per-op test files cover GAE, V-trace, PPO, LSTM, R2D2, QMIX, the two-hot losses and PER.
+Tickets: each captured launch that finalises its loss sums in-launch takes one of 3072 per-process graph tickets, never handed
+out again; past that, or in a capture that is the process's first such launch, the finalisation is a second kernel node with
+identical results.
 """
 from typing import Any, List, Optional, Sequence, Tuple
 

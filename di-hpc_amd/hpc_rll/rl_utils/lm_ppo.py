@@ -47,12 +47,12 @@ Conventions (those of ``grpo``):
 * ``-inf`` logits are masked vocabulary entries of probability 0, they add exactly 0 to the entropy; NaN in the logits of a
   LIVE token is clamped like ``-inf``;
 * ``B``, ``S`` or ``V`` of size 0 gives zeros and launches nothing;
-* contiguous GPU tensors.
+* contiguous GPU tensors;
+* nothing in the op synchronises with the host, so a learner step can be captured with ``hpc_rll.graphed``.
 
 Out of scope: fusing the LM head's matrix product, a reference-policy KL inside the loss (it goes into the reward through
 ``kl``; ``grpo`` has the in-loss form), ``old`` given as logits, bootstrapping a truncated sequence with a nonzero
-``V_{L+1}``, whitening statistics across ranks (use ``whiten=False``), float16, vocabularies split over ranks, HIP-graph
-capture."""
+``V_{L+1}``, whitening statistics across ranks (use ``whiten=False``), float16, vocabularies split over ranks."""
 from collections import namedtuple
 
 import torch
