@@ -937,6 +937,11 @@ inline void launch_cell_fwd_scalar(int H, int B, hipStream_t st, Args... a) {
     else hipLaunchKernelGGL(lstm_cell_fwd_kernel<8>, dim3(B), dim3(256), 0, st, a..., H);
 }
 inline bool cell_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// The persistent small-batch kernels exchange {value, tag} pairs as ONE 8-byte atomic word (lstm_persist.hpp: xchg_put /
+// xchg_get); every workspace region starts a multiple of 16 bytes behind ws, so the words are whole only if ws itself lies
+// on an 8-byte boundary.  On a workspace 4 bytes off, value and tag of a word arrive separately and a reader can pair a
+// fresh tag with a stale value: the step kernels take such a call.
+inline bool xchg_al8(const void* ws) { return (reinterpret_cast<uintptr_t>(ws) & 7) == 0; }
 
 inline void launch_cell_fwd(int H, int B, hipStream_t st, const float* xw, const float* hw, int nsplit, long part_stride,
                             float* hw_out, const float* bias, const float* gamma, const float* beta, const float* c_prev,
@@ -1160,7 +1165,7 @@ int lstm_forward_impl(const float* x, const float* h0, const float* c0, const fl
     }
     size_t wx_off = 0;
     WaveCfg wc{};
-    const bool wave = S > 0 && wave_fwd_ok(S, B, H, L, &wc, st);
+    const bool wave = S > 0 && xchg_al8(ws) && wave_fwd_ok(S, B, H, L, &wc, st);
     g_lstm_path_both.store(wave ? 2 : 0, std::memory_order_relaxed);
     ws_pair_record(ws, y_hseq && !wave && S > 0 && y != w.layer[L - 1].hseq);
     // (the layer wavefront addresses every layer's buffers with one stride: it keeps its h sequences in the workspace and
@@ -1203,7 +1208,7 @@ int lstm_forward_impl(const float* x, const float* h0, const float* c0, const fl
         return last_error();
     }
     PersistCfg pc{};
-    const bool persist = S > 0 && persist_cfg(B, H, H, &pc) && persist_fwd_ok(pc, st);
+    const bool persist = S > 0 && xchg_al8(ws) && persist_cfg(B, H, H, &pc) && persist_fwd_ok(pc, st);
     const XchgLayout xl = xchg_layout(B, H);
     if (persist && hipMemsetAsync(w.xchg, 0, xl.total_words * sizeof(u64), st) != hipSuccess) return last_error();
     // Large batches keep xw / hw in the gate-interleaved layout (shape-only: the backward must agree) and, when the
@@ -1382,7 +1387,7 @@ int lstm_backward_impl(const float* dy, const float* dhn, const float* dcn, cons
     float* seq_bufs[2] = {w.dseq_a, w.dseq_b};
     int flip = 0;
     PersistCfg pc{};
-    const bool persist = persist_cfg(B, H, 4 * H, &pc) && persist_bwd_ok(pc, st);
+    const bool persist = xchg_al8(ws) && persist_cfg(B, H, 4 * H, &pc) && persist_bwd_ok(pc, st);
     const XchgLayout xl = xchg_layout(B, H);
     if (persist && hipMemsetAsync(w.xchg, 0, xl.total_words * sizeof(u64), st) != hipSuccess) return last_error();
     // gate-interleaved xw / hw (what the forward wrote at these shapes): dxw / dhw come out interleaved too, the products run
@@ -1470,7 +1475,7 @@ int lstm_backward_impl(const float* dy, const float* dhn, const float* dcn, cons
         }
     };
     WaveCfg wb{};
-    if (w.dwave && wave_bwd_ok(S, B, H, L, &wb, st)) {   // all layers in one launch (lstm_wave.hpp)
+    if (w.dwave && xchg_al8(ws) && wave_bwd_ok(S, B, H, L, &wb, st)) {   // all layers in one launch (lstm_wave.hpp)
         g_lstm_last_bwd_path.store(2, std::memory_order_relaxed);
         const size_t words = 2 * wb.hx_words + wb.sx_words;
         if (hipMemsetAsync(w.xchg, 0, words * sizeof(u64), st) != hipSuccess) return last_error();

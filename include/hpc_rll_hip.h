@@ -1168,7 +1168,9 @@ int hpc_rll_lstm_backward_y(const float* dy, const float* dhn, const float* dcn,
  * + one cell launch per step (what src/torch_utils/network/lstm.cu:145-161 does with three launches), 1 = per-layer
  * persistent kernels (B <= 4), 2 = layer wavefront (B <= 4, L >= 2), 3 = step kernels on gate-interleaved pre-activations
  * (large batch), 4 = persistent row-block kernel (large batch, tune key 26), 5 = persistent mid-batch kernel (5 <= B <= 256,
- * tune key 29); -1 = no forward yet. */
+ * tune key 29); -1 = no forward yet.  Operands off a 16-byte boundary are accepted everywhere but on the large-batch shapes
+ * of 3 / 4 (HPC_RLL_EALIGN): 1 and 2 need ws on an 8-byte boundary (their exchange words are 8-byte atomics), 5 needs ws and
+ * h0 (forward) or ws (backward) on a 16-byte one; a call that does not meet this runs on the step kernels, 0. */
 int hpc_rll_lstm_last_forward_path(void);
 int hpc_rll_lstm_last_backward_path(void);   /* the same for the most recent hpc_rll_lstm_backward* call (its last layer; 5 = mid-batch kernel, key 33) */
 /* Asynchronous status of the persistent small-batch LSTM kernels (B <= 4).  Their workgroups exchange data through
