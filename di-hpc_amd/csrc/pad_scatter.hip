@@ -1090,11 +1090,23 @@ int g_scatter_bwd_xcd = 1;   // key 38: 1 = XCD-major workgroup order of the bac
 constexpr int g_scatter_threads = 1024;     // threads per workgroup of the cells-per-thread kernel on maps of >= 4096 cells
 int g_scatter_bwd_tile = 0;                 // hpc_rll_tune_set key 40: scatter backward by spatial tiles: 0 = by rule, 1 = never, 2 = wherever it applies
 constexpr int g_scatter_bwd_lds_kb = 64;    // planes staged per backward workgroup (profiles/r04_scatter_bwd_lds.txt)
+
+namespace {
+// The dispatch records (hpc_rll_pad_scatter_last_config): one per op, noted beside every launch with the grid, the workgroup
+// size and the LDS bytes OF THAT LAUNCH, so that a record names what ran, not a second evaluation of the rule.
+LaunchRecord<HPC_RLL_PAD_SCATTER_CONFIG_INTS> g_padsc_last[HPC_RLL_PADSC_OPS];
+int padsc_note(int rc, int op, int kernel, dim3 grid, unsigned threads, size_t lds, int a, int b) {
+    if (!rc) g_padsc_last[op].note({kernel, (int)grid.x, (int)(grid.y * grid.z), (int)threads, (int)lds, a, b});
+    return rc;
+}
+int padsc_note_no_launch(int rc, int op, int kernel, int a, int b) { return padsc_note(rc, op, kernel, dim3(0, 0, 0), 0, 0, a, b); }
+}  // namespace
 }
 using namespace hpc_rll;
 
-extern "C" int hpc_rll_pad_forward(const int64_t* table, float* new_x, int32_t* mask, int64_t n, int m0, int m1,
-                                   int m2, int value, void* stream) {
+// handed: 1 = called by hpc_rll_pad1d_packed_forward in its own stead (noted in the record)
+static int pad_list_forward(const int64_t* table, float* new_x, int32_t* mask, int64_t n, int m0, int m1, int m2, int value,
+                            void* stream, int handed) {
     if (n < 0 || m0 < 0 || m1 < 0 || m2 < 0) return HPC_RLL_EINVAL;
     const long inner = (long)m0 * m1 * m2;
     if (inner >= (1L << 31)) return HPC_RLL_EUNSUPPORTED;
@@ -1105,20 +1117,30 @@ extern "C" int hpc_rll_pad_forward(const int64_t* table, float* new_x, int32_t* 
                     (reinterpret_cast<uintptr_t>(mask) & 15) == 0;
     long blocks = ((v4 ? total / 4 : total) + 255) / 256;
     if (blocks > 256L * 16) blocks = 256L * 16;
-    if (v4 && m0 == 1 && m1 == 1 && total < (1L << 32))
+    int kernel;
+    if (v4 && m0 == 1 && m1 == 1 && total < (1L << 32)) {
+        kernel = HPC_RLL_PADSC_KERNEL_PAD1D4;
         hipLaunchKernelGGL(pad1d4_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, table, new_x, mask,
                            (long)n, (unsigned)m2, 1.0 / (double)m2, (float)value, value);
-    else if (v4)
+    } else if (v4) {
+        kernel = HPC_RLL_PADSC_KERNEL_PAD4;
         hipLaunchKernelGGL(pad4_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, table, new_x, mask,
                            (long)n, (unsigned)m0, (unsigned)m1, (unsigned)m2, (float)value, value);
-    else
+    } else {
+        kernel = HPC_RLL_PADSC_KERNEL_PAD;
         hipLaunchKernelGGL(pad_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, table, new_x, mask,
                            (long)n, (unsigned)m0, (unsigned)m1, (unsigned)m2, (float)value, value);
-    return last_error();
+    }
+    return padsc_note(last_error(), HPC_RLL_PADSC_OP_PAD, kernel, dim3((unsigned)blocks), 256, 0, v4 ? 4 : 1, handed);
 }
 
-extern "C" int hpc_rll_unpad_forward(const float* padded, const int64_t* table, float* flat, int64_t n,
-                                     int64_t total, int m0, int m1, int m2, void* stream) {
+extern "C" int hpc_rll_pad_forward(const int64_t* table, float* new_x, int32_t* mask, int64_t n, int m0, int m1,
+                                   int m2, int value, void* stream) {
+    return pad_list_forward(table, new_x, mask, n, m0, m1, m2, value, stream, 0);
+}
+
+static int unpad_list_forward(const float* padded, const int64_t* table, float* flat, int64_t n, int64_t total, int m0, int m1,
+                              int m2, void* stream, int handed) {
     if (n < 0 || total < 0 || m0 < 0 || m1 < 0 || m2 < 0) return HPC_RLL_EINVAL;
     if (total == 0 || n == 0) return HPC_RLL_OK;
     if (!padded || !table || !flat) return HPC_RLL_EINVAL;
@@ -1129,13 +1151,18 @@ extern "C" int hpc_rll_unpad_forward(const float* padded, const int64_t* table, 
         if (b4 > 256L * 16) b4 = 256L * 16;
         hipLaunchKernelGGL(unpad1d4_kernel, dim3((unsigned)b4), dim3(256), 0, (hipStream_t)stream, padded, table, flat,
                            (long)n, (long)total, (unsigned)m2, 1.0 / (double)m2);
-        return last_error();
+        return padsc_note(last_error(), HPC_RLL_PADSC_OP_UNPAD, HPC_RLL_PADSC_KERNEL_UNPAD1D4, dim3((unsigned)b4), 256, 0, 4, handed);
     }
     long blocks = (total + 255) / 256;
     if (blocks > 256L * 16) blocks = 256L * 16;
     hipLaunchKernelGGL(unpad_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, padded, table, flat,
                        (long)n, (long)total, (unsigned)m0, (unsigned)m1, (unsigned)m2);
-    return last_error();
+    return padsc_note(last_error(), HPC_RLL_PADSC_OP_UNPAD, HPC_RLL_PADSC_KERNEL_UNPAD, dim3((unsigned)blocks), 256, 0, 1, handed);
+}
+
+extern "C" int hpc_rll_unpad_forward(const float* padded, const int64_t* table, float* flat, int64_t n,
+                                     int64_t total, int m0, int m1, int m2, void* stream) {
+    return unpad_list_forward(padded, table, flat, n, total, m0, m1, m2, stream, 0);
 }
 
 // rows per workgroup of the LDS-staged packed kernels: 16 (tests/tools/micro/padbw.hip at n = 2^20, L = 127: 16 rows and
@@ -1150,11 +1177,19 @@ extern "C" int hpc_rll_pad1d_packed_forward(const float* flat, const int64_t* ta
     if (n < 0 || max_len < 0) return HPC_RLL_EINVAL;
     if (n == 0 || max_len == 0) return HPC_RLL_OK;
     if (!flat || !table || !new_x || !mask) return HPC_RLL_EINVAL;
+    // Which kernel: new_x and mask 16-byte aligned (flat may start anywhere) and
+    //   32 <= max_len <= 16384 with key 28 = 1   the wave kernel (its tiles are 1024 elements whatever the row width: no RB);
+    //   otherwise, RB >= 1 (max_len <= 15200)     the workgroup kernel;
+    //   otherwise -- a misaligned output, or max_len > 15200 with key 28 = 0 or beyond 16384 -- the call is handed over to
+    //   hpc_rll_pad_forward (pad1d4_kernel / pad_kernel), which computes the same values.
     const int RB = packed_rows_per_wg(max_len);
-    const bool ok = RB >= 1 && (reinterpret_cast<uintptr_t>(new_x) & 15) == 0 && (reinterpret_cast<uintptr_t>(mask) & 15) == 0 &&
+    const bool al = (reinterpret_cast<uintptr_t>(new_x) & 15) == 0 && (reinterpret_cast<uintptr_t>(mask) & 15) == 0 &&
                     (reinterpret_cast<uintptr_t>(flat) & 3) == 0;
-    if (!ok) return hpc_rll_pad_forward(table, new_x, mask, n, 1, 1, max_len, value, stream);
-    if (max_len >= 32 && max_len <= 16384 && g_pad_wave) {   // wave tiles in output space (round 4)
+    const bool wave = al && max_len >= 32 && max_len <= 16384 && g_pad_wave;
+    if (!wave && !(al && RB >= 1))
+        return padsc_note_no_launch(pad_list_forward(table, new_x, mask, n, 1, 1, max_len, value, stream, 1),
+                                    HPC_RLL_PADSC_OP_PAD_PACKED, HPC_RLL_PADSC_KERNEL_HANDED_OVER, RB, 1);
+    if (wave) {   // wave tiles in output space (round 4)
         const long ntiles = (long)(((unsigned long)n * (unsigned long)max_len + 1023) / 1024);
         long wb = (ntiles + 3) / 4;
         // (fewer, persistent workgroups -- the shape that makes a pure fill fast, profiles/r04_writebw.txt -- are SLOWER here:
@@ -1163,14 +1198,14 @@ extern "C" int hpc_rll_pad1d_packed_forward(const float* flat, const int64_t* ta
         if (wb > (1L << 20)) wb = 1L << 20;   // (every wave ONE tile: the 8192-workgroup cap of the first version, four tiles per wave, was 2.5 % slower)
         hipLaunchKernelGGL(pad1d_packed_wave_kernel, dim3((unsigned)wb), dim3(256), 0, (hipStream_t)stream, flat, table, new_x, mask,
                            (long)n, (unsigned)max_len, 1.0f / (float)max_len, (float)value, value);
-        return last_error();
+        return padsc_note(last_error(), HPC_RLL_PADSC_OP_PAD_PACKED, HPC_RLL_PADSC_KERNEL_PAD1D_PACKED_WAVE, dim3((unsigned)wb), 256, 0, RB, 0);
     }
     long blocks = (n + RB - 1) / RB;
     if (blocks > (1L << 20)) blocks = 1L << 20;
     const size_t lds = ((((size_t)RB * max_len + 8 + 1) & ~(size_t)1)) * 4 + (size_t)(RB + 1) * 8;
     hipLaunchKernelGGL(pad1d_packed_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, flat, table, new_x, mask,
                        (long)n, (unsigned)max_len, 1.0 / (double)max_len, RB, (float)value, value);
-    return last_error();
+    return padsc_note(last_error(), HPC_RLL_PADSC_OP_PAD_PACKED, HPC_RLL_PADSC_KERNEL_PAD1D_PACKED, dim3((unsigned)blocks), 256, lds, RB, 0);
 }
 
 extern "C" int hpc_rll_unpad1d_packed_forward(const float* padded, const int64_t* table, float* flat, int64_t n, int64_t total,
@@ -1178,15 +1213,20 @@ extern "C" int hpc_rll_unpad1d_packed_forward(const float* padded, const int64_t
     if (n < 0 || total < 0 || max_len < 0) return HPC_RLL_EINVAL;
     if (n == 0 || total == 0 || max_len == 0) return HPC_RLL_OK;
     if (!padded || !table || !flat) return HPC_RLL_EINVAL;
+    // `padded` 16-byte aligned (flat may start anywhere) and RB >= 1 (max_len <= 15200: at least one row fits the LDS tile): the
+    // workgroup kernel.  Otherwise the call is handed over to hpc_rll_unpad_forward (unpad1d4_kernel where `padded` is aligned
+    // and n * max_len % 4 == 0, else unpad_kernel), which computes the same values; there is no wave kernel in this direction.
     const int RB = packed_rows_per_wg(max_len);
     const bool ok = RB >= 1 && (reinterpret_cast<uintptr_t>(padded) & 15) == 0 && (reinterpret_cast<uintptr_t>(flat) & 3) == 0;
-    if (!ok) return hpc_rll_unpad_forward(padded, table, flat, n, total, 1, 1, max_len, stream);
+    if (!ok)
+        return padsc_note_no_launch(unpad_list_forward(padded, table, flat, n, total, 1, 1, max_len, stream, 1),
+                                    HPC_RLL_PADSC_OP_UNPAD_PACKED, HPC_RLL_PADSC_KERNEL_HANDED_OVER, RB, 1);
     long blocks = (n + RB - 1) / RB;
     if (blocks > (1L << 20)) blocks = 1L << 20;
     const size_t lds = ((((size_t)RB * max_len + 8 + 1) & ~(size_t)1)) * 4 + (size_t)(RB + 1) * 8;
     hipLaunchKernelGGL(unpad1d_packed_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, padded, table, flat,
                        (long)n, (long)total, (unsigned)max_len, 1.0 / (double)max_len, RB);
-    return last_error();
+    return padsc_note(last_error(), HPC_RLL_PADSC_OP_UNPAD_PACKED, HPC_RLL_PADSC_KERNEL_UNPAD1D_PACKED, dim3((unsigned)blocks), 256, lds, RB, 0);
 }
 
 extern "C" int64_t hpc_rll_packed_table_scratch_int64(int64_t n) {
@@ -1414,13 +1454,15 @@ extern "C" int hpc_rll_scatter_connection_forward(const float* x, const int64_t*
     hipStream_t st = (hipStream_t)stream;
     int rc = HPC_RLL_OK;
     bool indexed = false;
+    int parts = 0;               // of the index launch of this call (0 = none), for the record
     auto build_index = [&]() {   // the paths that read the index from memory
         if (indexed) return;
-        const int parts = add ? (M > 256 ? 3 : 1) : 2;
+        parts = add ? (M > 256 ? 3 : 1) : 2;
         hipLaunchKernelGGL(scatter_index_kernel, dim3(B), dim3(256), 0, st, location, ws, M, H, W, parts);
         rc = last_error();
         indexed = true;
     };
+    auto flags = [&](bool built, bool vec) { return (add ? 1 : 0) | (built ? 2 : 0) | (parts << 2) | (vec ? 16 : 0); };
     const bool v4 = (HW % 4) == 0 && (N % 4) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
                     (reinterpret_cast<uintptr_t>(out) & 15) == 0;
     // LDS-staged streaming kernel: the owner table (HW ints) and an M x NPB tile of x must fit in LDS with room for
@@ -1482,7 +1524,10 @@ extern "C" int hpc_rll_scatter_connection_forward(const float* x, const int64_t*
             else if (add) hipLaunchKernelGGL((scatter_out_lds_kernel<true, false>), grid, dim3(1024), lds, st, x, ws, out, M, N, (int)HW, npb, location, W, pf_wgs);
             else if (build) hipLaunchKernelGGL((scatter_out_lds_kernel<false, true>), grid, dim3(1024), lds, st, x, ws, out, M, N, (int)HW, npb, location, W, pf_wgs);
             else hipLaunchKernelGGL((scatter_out_lds_kernel<false, false>), grid, dim3(1024), lds, st, x, ws, out, M, N, (int)HW, npb, location, W, pf_wgs);
-            return last_error();
+            // vec: every workgroup stages its x tile with 16-byte loads (stage_x: nn, N and n0 multiples of 4, x aligned)
+            const bool xvec = (N % 4) == 0 && (npb % 4) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+            return padsc_note(last_error(), HPC_RLL_PADSC_OP_SCATTER_FWD, HPC_RLL_PADSC_KERNEL_SCATTER_OUT_LDS, grid, 1024, lds, npb,
+                              flags(build, xvec));
         }
     }
     const int tpb = (v4 && HW >= 4096) ? g_scatter_threads : 256;   // threads per block of the 4-wide kernel
@@ -1496,14 +1541,16 @@ extern "C" int hpc_rll_scatter_connection_forward(const float* x, const int64_t*
         if (rc) return rc;
         if (add) hipLaunchKernelGGL(scatter_out4_kernel<true>, grid, dim3(tpb), 0, st, x, ws, out, M, N, (int)HW, n_per_block);
         else hipLaunchKernelGGL(scatter_out4_kernel<false>, grid, dim3(tpb), 0, st, x, ws, out, M, N, (int)HW, n_per_block);
-        return last_error();
+        return padsc_note(last_error(), HPC_RLL_PADSC_OP_SCATTER_FWD, HPC_RLL_PADSC_KERNEL_SCATTER_OUT4, grid, tpb, 0, n_per_block,
+                          flags(false, true));
     }
     build_index();
     if (rc) return rc;
     const bool vec = (N % 4) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
     if (add) hipLaunchKernelGGL(scatter_out_kernel<true>, grid, dim3(256), 0, st, x, ws, out, M, N, (int)HW, n_per_block, vec);
     else hipLaunchKernelGGL(scatter_out_kernel<false>, grid, dim3(256), 0, st, x, ws, out, M, N, (int)HW, n_per_block, vec);
-    return last_error();
+    return padsc_note(last_error(), HPC_RLL_PADSC_OP_SCATTER_FWD, HPC_RLL_PADSC_KERNEL_SCATTER_OUT, grid, 256, 0, n_per_block,
+                      flags(false, vec));
 }
 
 // Round 6: backward by SPATIAL tiles.  Workgroup = (batch element, TR map rows): it stages rows y0 .. y0+TR-1 of ALL N planes (N
@@ -1585,7 +1632,9 @@ extern "C" int hpc_rll_scatter_connection_backward(const float* grad_out, const 
     hipStream_t st = (hipStream_t)stream;
     const long HW = (long)H * W;
     // an empty map: every location is out of range, every gradient row is zero (grad_out has no elements and may be null)
-    if (HW == 0) return (int)hipMemsetAsync(grad_x, 0, sizeof(float) * (size_t)B * M * N, st);
+    if (HW == 0)
+        return padsc_note_no_launch((int)hipMemsetAsync(grad_x, 0, sizeof(float) * (size_t)B * M * N, st), HPC_RLL_PADSC_OP_SCATTER_BWD,
+                                    HPC_RLL_PADSC_KERNEL_SCATTER_BWD_MEMSET, 0, 0);
     if (!grad_out) return HPC_RLL_EINVAL;
     const long plane_bytes = HW * 4;
     // Which kernel (round 6, profiles/r06_scatter_bwd_probe.txt).  The plane kernel writes NG*4-byte pieces of every entity's row
@@ -1616,7 +1665,7 @@ extern "C" int hpc_rll_scatter_connection_backward(const float* grad_out, const 
                                                        (int)lds) != hipSuccess)
                 return last_error();
             hipLaunchKernelGGL(scatter_bwd_tile_kernel, grid, dim3(1024), lds, st, grad_out, location, grad_x, M, N, H, W, TR, swz, 0);
-            return last_error();
+            return padsc_note(last_error(), HPC_RLL_PADSC_OP_SCATTER_BWD, HPC_RLL_PADSC_KERNEL_SCATTER_BWD_TILE, grid, 1024, lds, TR, 0);
         }
     }
     if (plane_bytes <= 128 * 1024 && B <= 65535) {
@@ -1635,12 +1684,19 @@ extern "C" int hpc_rll_scatter_connection_backward(const float* grad_out, const 
         // (round 6) with B a multiple of 8 the XCDs take NEIGHBOURING batch elements (order 2: -1 % on every shape measured)
         const int xo2 = (xcd_order && B % 8 == 0) ? 2 : xcd_order;
         hipLaunchKernelGGL(scatter_bwd_lds_kernel, grid, dim3(1024), lds, st, grad_out, location, grad_x, M, N, H, W, NG, xo2);
-    } else {
-        const long total = (long)B * M * N;
-        long blocks = (total + 255) / 256;
-        if (blocks > 8192) blocks = 8192;
-        hipLaunchKernelGGL(scatter_bwd_direct_kernel, dim3((unsigned)blocks), dim3(256), 0, st, grad_out, location,
-                           grad_x, total, M, N, H, W);
+        return padsc_note(last_error(), HPC_RLL_PADSC_OP_SCATTER_BWD, HPC_RLL_PADSC_KERNEL_SCATTER_BWD_LDS, grid, 1024, lds, NG, xo2);
     }
-    return last_error();
+    const long total = (long)B * M * N;
+    long blocks = (total + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(scatter_bwd_direct_kernel, dim3((unsigned)blocks), dim3(256), 0, st, grad_out, location,
+                       grad_x, total, M, N, H, W);
+    return padsc_note(last_error(), HPC_RLL_PADSC_OP_SCATTER_BWD, HPC_RLL_PADSC_KERNEL_SCATTER_BWD_DIRECT, dim3((unsigned)blocks), 256, 0, 0, 0);
 }
+
+extern "C" int hpc_rll_pad_scatter_last_config(int op, int* out) {
+    if (op < 0 || op >= HPC_RLL_PADSC_OPS || !out) return HPC_RLL_EINVAL;
+    g_padsc_last[op].read(out);
+    return HPC_RLL_OK;
+}
+static_assert(HPC_RLL_PAD_SCATTER_CONFIG_INTS == 8, "the layout documented in hpc_rll_hip.h: count, kernel, grid.x, grid.y*z, threads, LDS, two by op");

@@ -1076,7 +1076,9 @@ int hpc_rll_packed_table(const int64_t* lengths, int64_t n, int64_t base, int64_
  * rows: the two directions with the rows' contiguity exploited (a workgroup's rows are ONE span of the flat buffer,
  * staged through LDS with 16-byte accesses).  `table` as built by hpc_rll_packed_table: pad -- base = address of `flat`,
  * stride 4; unpad -- base 0, stride 1.  Same results as hpc_rll_pad_forward / hpc_rll_unpad_forward with m0 = m1 = 1
- * (to which they fall back when a pointer is not aligned for 16-byte stores). */
+ * (to which they hand over when a pointer is not aligned for 16-byte accesses, or when max_len > 15200 so that not even one
+ * row fits the workgroup kernels' 60 KB of LDS -- except that the pad's wave kernel, tune key 28 = 1, needs no such room and
+ * takes every 32 <= max_len <= 16384). */
 int hpc_rll_pad1d_packed_forward(const float* flat, const int64_t* table, float* new_x, int32_t* mask, int64_t n,
                                  int max_len, int value, void* stream);
 int hpc_rll_unpad1d_packed_forward(const float* padded, const int64_t* table, float* flat, int64_t n, int64_t total,
@@ -1124,6 +1126,59 @@ int hpc_rll_scatter_connection_forward(const float* x, const int64_t* location, 
                                        int M, int N, int H, int W, int add, void* stream);
 int hpc_rll_scatter_connection_backward(const float* grad_out, const int64_t* location, float* grad_x, int B, int M,
                                         int N, int H, int W, void* stream);
+/* Diagnostic (no reference counterpart; read-only, modelled on hpc_rll_dist_last_config / hpc_rll_per_last_config): which
+ * kernel the most recent launching call of hpc_rll_pad_forward (op HPC_RLL_PADSC_OP_PAD), hpc_rll_unpad_forward (_UNPAD),
+ * hpc_rll_pad1d_packed_forward (_PAD_PACKED), hpc_rll_unpad1d_packed_forward (_UNPAD_PACKED),
+ * hpc_rll_scatter_connection_forward (_SCATTER_FWD) or hpc_rll_scatter_connection_backward (_SCATTER_BWD) ran in this
+ * process, noted on the host beside the launch with the values of that launch.  Each op keeps its own record.
+ * out[HPC_RLL_PAD_SCATTER_CONFIG_INTS] = {
+ *    [0] calls of this op that launched so far (0 = none yet: every other entry is then -1),
+ *    [1] the kernel, one of HPC_RLL_PADSC_KERNEL_*,
+ *    [2] grid.x, [3] grid.y * grid.z, [4] threads per workgroup, [5] dynamic LDS bytes of that launch (all 0 for _HANDED_OVER
+ *        and _SCATTER_BWD_MEMSET; the scatter forward's index launch, where there is one, is one workgroup of 256 threads per
+ *        batch element and shows in the flags only),
+ *    [6], [7] by op:
+ *        PAD, UNPAD          [6] output (pad) / padded (unpad) elements per thread step: 4 for the 16-byte kernels, 1 for the
+ *                                element-wise ones,  [7] 1 = called as the hand-over target of the packed entry point, else 0
+ *        PAD_PACKED,         [6] RB, the rows per workgroup that 60 KB of LDS hold: min(16, (15360 - 160) / max_len), 0 above
+ *        UNPAD_PACKED            max_len = 15200 (the wave kernel does not use it),  [7] 1 = handed over to the list entry point
+ *                                (kernel = _HANDED_OVER; the PAD / UNPAD record then names the kernel that ran), else 0
+ *        SCATTER_FWD         [6] channels per workgroup (npb of the LDS-staged kernel, n_per_block of the other two),
+ *                            [7] flags: bit 0 add, bit 1 owner table built inside the kernel (tune key 37), bits 2-3 the `parts`
+ *                                of the index launch before it (0 = no index launch, 1 = head + next, 2 = last, 3 = all three),
+ *                                bit 4 vec: x is read 16 bytes at a time (N % 4 == 0 and x 16-byte aligned; LDS-staged kernel:
+ *                                and npb % 4 == 0), else element-wise
+ *        SCATTER_BWD         [6] NG, the planes per workgroup (_SCATTER_BWD_LDS), TR, the map rows per tile (_TILE), else 0,
+ *                            [7] the XCD order of the launch: 0 launch order, 1 XCD-major, 2 neighbouring batch elements }.
+ * A packed call that hands over notes BOTH records.  Calls that return before launching (empty shapes, argument errors) leave
+ * every record as it was.  Plain ints of the host process, not synchronised.  HPC_RLL_EINVAL for an op outside the six or
+ * out == NULL (nothing written). */
+#define HPC_RLL_PADSC_OP_PAD (0)
+#define HPC_RLL_PADSC_OP_UNPAD (1)
+#define HPC_RLL_PADSC_OP_PAD_PACKED (2)
+#define HPC_RLL_PADSC_OP_UNPAD_PACKED (3)
+#define HPC_RLL_PADSC_OP_SCATTER_FWD (4)
+#define HPC_RLL_PADSC_OP_SCATTER_BWD (5)
+#define HPC_RLL_PADSC_OPS (6)
+#define HPC_RLL_PADSC_KERNEL_PAD (0)                 /* pad_kernel: one output element per thread, any rank, any alignment */
+#define HPC_RLL_PADSC_KERNEL_PAD4 (1)                /* pad4_kernel: four per thread (total % 4 == 0, new_x and mask 16-byte aligned) */
+#define HPC_RLL_PADSC_KERNEL_PAD1D4 (2)              /* pad1d4_kernel: pad4 for m0 = m1 = 1 and total < 2^32 */
+#define HPC_RLL_PADSC_KERNEL_UNPAD (3)               /* unpad_kernel: one flat element per thread, binary search for its tensor */
+#define HPC_RLL_PADSC_KERNEL_UNPAD1D4 (4)            /* unpad1d4_kernel: a quad of the padded tensor per thread (m0 = m1 = 1, n * m2 % 4 == 0, < 2^32, padded aligned) */
+#define HPC_RLL_PADSC_KERNEL_PAD1D_PACKED (5)        /* pad1d_packed_kernel: RB rows per workgroup through LDS */
+#define HPC_RLL_PADSC_KERNEL_PAD1D_PACKED_WAVE (6)   /* pad1d_packed_wave_kernel: 1024 output elements per wave (32 <= max_len <= 16384, key 28) */
+#define HPC_RLL_PADSC_KERNEL_UNPAD1D_PACKED (7)      /* unpad1d_packed_kernel: RB rows per workgroup through LDS */
+#define HPC_RLL_PADSC_KERNEL_HANDED_OVER (8)         /* a packed entry point that called the list entry point instead */
+#define HPC_RLL_PADSC_KERNEL_SCATTER_OUT (9)         /* scatter_out_kernel<ADD>: a cell per thread behind the index launch */
+#define HPC_RLL_PADSC_KERNEL_SCATTER_OUT4 (10)       /* scatter_out4_kernel<ADD>: four cells x four channels per step behind the index launch */
+#define HPC_RLL_PADSC_KERNEL_SCATTER_OUT_LDS (11)    /* scatter_out_lds_kernel<ADD, BUILD>: the LDS-staged streaming kernel */
+#define HPC_RLL_PADSC_KERNEL_SCATTER_BWD_LDS (12)    /* scatter_bwd_lds_kernel: whole planes of grad_out staged per workgroup */
+#define HPC_RLL_PADSC_KERNEL_SCATTER_BWD_TILE (13)   /* scatter_bwd_tile_kernel: map rows of all channels staged per workgroup (key 40) */
+#define HPC_RLL_PADSC_KERNEL_SCATTER_BWD_DIRECT (14) /* scatter_bwd_direct_kernel: planes above 128 KB, gathered from memory */
+#define HPC_RLL_PADSC_KERNEL_SCATTER_BWD_MEMSET (15) /* H * W == 0: grad_x is cleared by a memset, no kernel */
+#define HPC_RLL_PADSC_KERNELS (16)
+#define HPC_RLL_PAD_SCATTER_CONFIG_INTS (8)
+int hpc_rll_pad_scatter_last_config(int op, int* out);
 
 /* ------------------------------------------------------------------------------------------
  * LayerNorm-LSTM -- replaces LstmForward/LstmBackward (torch_utils/network/entry.h:11-19,

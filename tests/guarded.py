@@ -68,6 +68,47 @@ class GuardedU8:
         assert self.t.is_contiguous() and self.t.data_ptr() % 2 == off, "the mask lost its byte offset"
 
 
+UNWRITTEN32 = 0x7FC00000     # the int32 an output of GuardedI32 starts from: the bits of the NaN that GuardedF32 pre-fills with
+
+
+class GuardedI32:
+    """A flat int32 vector of ``n`` elements that starts ``off`` ints (0..3) past a 16-byte boundary, between two sentinel
+    bands: an int32 output (pre-filled with ``UNWRITTEN32``), an input (a copy of ``src``; ``check()`` then also asserts that
+    the values are still those of ``src``) or scratch (``scratch=True``: the contents are nobody's business, only the bands)."""
+
+    def __init__(self, n, off, dev, src=None, scratch=False):
+        assert 0 <= off <= 3
+        tail = GUARD + (-(off + n)) % 4
+        self.raw = torch.full((GUARD + off + n + tail,), SENTINEL32, dtype=torch.int32, device=dev)
+        assert self.raw.data_ptr() % 16 == 0
+        self.lo, self.hi = GUARD + off, GUARD + off + n
+        self.t = self.raw[self.lo:self.hi]
+        assert self.t.data_ptr() % 16 == 4 * off, "the view lost its misalignment"
+        self.src = None
+        if src is not None:
+            self.t.copy_(src.reshape(-1))
+            self.src = src.reshape(-1).cpu().clone()
+        elif not scratch:
+            self.t.fill_(UNWRITTEN32)
+
+    def check(self, what=""):
+        for name, band in (("below", self.raw[:self.lo]), ("above", self.raw[self.hi:])):
+            assert band.numel() >= GUARD
+            moved = (band != SENTINEL32).nonzero().flatten()
+            assert moved.numel() == 0, f"{what}: {moved.numel()} guard words {name} the int32 vector were overwritten, " \
+                                       f"first at band offset {int(moved[0])}"
+        if self.src is not None:
+            assert torch.equal(self.t.cpu(), self.src), f"{what}: an int32 input was overwritten"
+
+    def assert_written(self, what=""):
+        left = self.t == UNWRITTEN32
+        assert not bool(left.any()), f"{what}: {int(left.sum())} ints were never written, first at index " \
+                                     f"{int(left.nonzero()[0])}"
+
+    def assert_untouched(self, what=""):
+        assert bool((self.t == UNWRITTEN32).all()), f"{what}: a refused call wrote to its int32 output"
+
+
 SENTINEL64 = 0x5EED5EED5EED5EED
 
 

@@ -256,6 +256,9 @@ def test_packed_group_padding_sample_policy_and_errors():
                                              (1, 5, 6, 5), (70000, 0, 3, 4),
                                              # round 4, wave tiles of 1024 output elements (32 <= max_len <= 16384): the narrowest
                                              # rows (34 per tile), empty rows, widths around the tile size, the widest rows
+                                             # (16384 columns: no row fits the workgroup kernels' LDS tile -- the pad runs on
+                                             # the wave kernel all the same, pinned by tests/test_pad_scatter_direct_gpu.py; the
+                                             # unpad of that width is handed over to unpad1d4_kernel)
                                              (20011, 0, 33, 32), (9000, 20, 64, 63), (3000, 100, 300, 299), (700, 1000, 1030, 1029),
                                              (333, 0, 1025, 1024), (40, 5000, 16385, 16384), (1, 40, 41, 40), (7, 0, 1, 64)])
 def test_packed_padding_lds_kernels_bit_exact(n, lo, hi, max_len):
@@ -277,10 +280,20 @@ def test_packed_padding_lds_kernels_bit_exact(n, lo, hi, max_len):
         assert torch.equal(x, want) and torch.equal(m, torch.where(valid, 1, -7).to(torch.int32))
         back = P.UnPadding1DPacked(x, lens, total=total)
         assert torch.equal(back, flat)
-        out = torch.full((total + 8,), 3.0, device=DEV)                  # unpad into an unaligned view: neighbours untouched
         import hpc_rl_utils as U
         assert torch.equal(U.unpad1d_packed(x, lens, total), flat)
-        del out
+        if total:                                                        # unpad into an unaligned guarded view: neighbours untouched
+            import cabi as N
+            from guarded import GuardedF32
+            dst = GuardedF32(1, total, (shift + 1) % 4, DEV)
+            table = torch.empty(4 * n, dtype=torch.int64, device=DEV)
+            scratch = torch.empty(int(N.lib.hpc_rll_packed_table_scratch_int64(n)), dtype=torch.int64, device=DEV)
+            N.call("hpc_rll_packed_table", DEV, lens.data_ptr(), n, 0, 1, table.data_ptr(), scratch.data_ptr())
+            N.call("hpc_rll_unpad1d_packed_forward", DEV, x.data_ptr(), table.data_ptr(), dst.t.data_ptr(), n, total, max_len)
+            torch.cuda.synchronize()
+            dst.check("unaligned unpad")
+            dst.assert_written("unaligned unpad")
+            assert torch.equal(dst.t.view(-1), flat)
 
 
 def test_packed_padding_wave_tiles_equal_workgroup_kernel():
@@ -473,7 +486,7 @@ def test_packed_table_rows_through_the_c_abi(n, misalign):
                                        (6, 256, 8, 32, 32), (5, 240, 33, 32, 40), (4, 120, 64, 64, 64)])
 def test_scatter_in_kernel_index_build(B, M, N, H, W):
     """Round 4 (tune key 37): the LDS-staged forward kernel builds the owner table (cover: LDS atomic max; add: LDS atomic min for the
-    head + a broadcast search for the next entity of the chain, M <= 512) itself instead of reading the index launch's tables.
+    head + a broadcast search for the next entity of the chain, M <= 256 on maps of 1024 cells and more) itself instead of reading the index launch's tables.
     Against the CPU oracle and against key 37 = 0, bit for bit: heavy collisions (4 x 4 maps), M = 1, M % 4 != 0, the add
     fallback above 512 entities, cover with several entities per thread, and -- on / off only, the oracle has no such case --
     out-of-range locations (dropped).  Round 5: `add` gives a cell with several entities a row of its own in the staged tile (the
