@@ -233,7 +233,7 @@ __global__ __launch_bounds__(NW * 64) void gae_fwd_pf_kernel(const float* __rest
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     // (round 4 tried XCD-contiguous column tiles -- XCD x owning a contiguous eighth of the columns instead of every 8th tile:
-    // no gain at C2 (tests/tools/r04_gae_xcd_probe.py); removed in round 5)
+    // no gain at C2 (tests/tools/archive/r04_gae_xcd_probe.py); removed in round 5.  The same holds for gae_bwd_pf_kernel.)
     const long col = (long)blockIdx.x * TILE + (long)lane * V;
     const bool col_ok = FULLB || col < (long)B;
 
@@ -536,8 +536,6 @@ __global__ __launch_bounds__(NW * 64) void gae_bwd_pf_kernel(const float* __rest
 
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    // (round 4 tried XCD-contiguous column tiles -- XCD x owning a contiguous eighth of the columns instead of every 8th tile:
-    // no gain at C2 (tests/tools/r04_gae_xcd_probe.py); removed in round 5)
     const long col = (long)blockIdx.x * TILE + (long)lane * V;
     const bool col_ok = FULLB || col < (long)B;
 
@@ -819,111 +817,97 @@ inline Cfg choose_cfg(bool fwd, int T, int B, int vmax, int v, int lc, int nw, i
     return out;
 }
 
+// what hpc_rll_gae_last_config reports for direction `kind`
+inline void note_cfg(int kind, const Cfg& cfg) {
+    std::atomic<int>* r = g_kt.last_cfg[kind];
+    r[0] = cfg.v; r[1] = cfg.lc; r[2] = cfg.nw; r[3] = cfg.flags; r[4] = cfg.half; r[5] = cfg.pf;
+}
+
 template <int N> using I = std::integral_constant<int, N>;
 
-// (V, LC, NW) triples that are instantiated (each in 4 nontemporal flavours).
+// f(V, LC, NW) for every NW of one (V, LC) row of a table of instantiated triples
+template <int V, int LC, int NW, int... MORE, class F>
+inline void cfg_row(F& f) {
+    f(I<V>{}, I<LC>{}, I<NW>{});
+    if constexpr (sizeof...(MORE) > 0) cfg_row<V, LC, MORE...>(f);
+}
+
+// A direction's kernels and tables.  Plain kernels: the same (V, LC) x NW in {1,2,4,8,16} table for both directions, each
+// triple in 4 nontemporal flavours.  Pipelined kernels: (V, LC) x NW in {2,4,8}, nontemporal stores, both load flavours.
 template <class F>
-inline void for_each_cfg(F&& f) {
-#define HPC_RLL_NW_ROW(V, LC) \
-    f(I<V>{}, I<LC>{}, I<1>{}); f(I<V>{}, I<LC>{}, I<2>{}); f(I<V>{}, I<LC>{}, I<4>{}); \
-    f(I<V>{}, I<LC>{}, I<8>{}); f(I<V>{}, I<LC>{}, I<16>{});
-    HPC_RLL_NW_ROW(1, 4) HPC_RLL_NW_ROW(1, 8) HPC_RLL_NW_ROW(1, 16)
-    HPC_RLL_NW_ROW(2, 2) HPC_RLL_NW_ROW(2, 4) HPC_RLL_NW_ROW(2, 8) HPC_RLL_NW_ROW(2, 16)
-    HPC_RLL_NW_ROW(4, 2) HPC_RLL_NW_ROW(4, 4) HPC_RLL_NW_ROW(4, 8)
-#undef HPC_RLL_NW_ROW
+inline void for_each_cfg(F& f) {
+    cfg_row<1, 4, 1, 2, 4, 8, 16>(f); cfg_row<1, 8, 1, 2, 4, 8, 16>(f); cfg_row<1, 16, 1, 2, 4, 8, 16>(f);
+    cfg_row<2, 2, 1, 2, 4, 8, 16>(f); cfg_row<2, 4, 1, 2, 4, 8, 16>(f); cfg_row<2, 8, 1, 2, 4, 8, 16>(f);
+    cfg_row<2, 16, 1, 2, 4, 8, 16>(f);
+    cfg_row<4, 2, 1, 2, 4, 8, 16>(f); cfg_row<4, 4, 1, 2, 4, 8, 16>(f); cfg_row<4, 8, 1, 2, 4, 8, 16>(f);
 }
 
-#define HPC_RLL_GAE_DISPATCH(KERNEL, KIND, ...)                                                    \
-    do {                                                                                           \
-        bool hit = false;                                                                          \
-        {                                                                                          \
-            std::atomic<int>* lc_ = g_kt.last_cfg[KIND];                                           \
-            lc_[0] = cfg.v; lc_[1] = cfg.lc; lc_[2] = cfg.nw; lc_[3] = cfg.flags; lc_[4] = cfg.half; lc_[5] = cfg.pf; \
-        }                                                                                          \
-        if (cfg.half) {                                                                            \
-            const dim3 grid((unsigned)((B + 31) / 32)), block(1024);                               \
-            const bool ntl = cfg.flags & 1;                                                        \
-            if (cfg.lc == 16) {                                                                    \
-                if (ntl) launch(KERNEL<1, 16, 16, true, true, true>, grid, block, st, KIND, __VA_ARGS__);   \
-                else launch(KERNEL<1, 16, 16, false, true, true>, grid, block, st, KIND, __VA_ARGS__);      \
-            } else {                                                                               \
-                if (ntl) launch(KERNEL<1, 8, 16, true, true, true>, grid, block, st, KIND, __VA_ARGS__);    \
-                else launch(KERNEL<1, 8, 16, false, true, true>, grid, block, st, KIND, __VA_ARGS__);       \
-            }                                                                                      \
-            hit = true;                                                                            \
-        }                                                                                          \
-        auto go = [&](auto V_, auto LC_, auto NW_) {                                               \
-            constexpr int V = decltype(V_)::value, LC = decltype(LC_)::value,                      \
-                          NW = decltype(NW_)::value;                                               \
-            if (!hit && cfg.v == V && cfg.lc == LC && cfg.nw == NW) {                                \
-                const dim3 grid((unsigned)((B + 64 * V - 1) / (64 * V))), block(NW * 64);          \
-                switch (cfg.flags) {                                                               \
-                    case 0: launch(KERNEL<V, LC, NW, false, false>, grid, block, st, KIND, __VA_ARGS__); break; \
-                    case 1: launch(KERNEL<V, LC, NW, true, false>, grid, block, st, KIND, __VA_ARGS__); break;  \
-                    case 2: launch(KERNEL<V, LC, NW, false, true>, grid, block, st, KIND, __VA_ARGS__); break;  \
-                    default: launch(KERNEL<V, LC, NW, true, true>, grid, block, st, KIND, __VA_ARGS__); break;  \
-                }                                                                                  \
-                hit = true;                                                                        \
-            }                                                                                      \
-        };                                                                                         \
-        for_each_cfg(go);                                                                          \
-        if (!hit) return HPC_RLL_EUNSUPPORTED;                                                     \
-    } while (0)
+struct FwdKernels {
+    static constexpr int kind = 0;
+    template <int V, int LC, int NW, bool NTL, bool NTS, bool HALF>
+    static auto plain() { return gae_fwd_kernel<V, LC, NW, NTL, NTS, HALF>; }
+    template <int V, int LC, int NW, bool NTL, bool NTS, bool FULLB>
+    static auto pipelined() { return gae_fwd_pf_kernel<V, LC, NW, NTL, NTS, FULLB>; }
+    template <class F> static void for_each_pf_cfg(F& f) {
+        cfg_row<1, 8, 2, 4, 8>(f); cfg_row<1, 16, 2, 4, 8>(f);
+        cfg_row<2, 4, 2, 4, 8>(f); cfg_row<2, 8, 2, 4, 8>(f); cfg_row<2, 16, 2, 4, 8>(f);
+        cfg_row<4, 4, 2, 4, 8>(f); cfg_row<4, 8, 2, 4, 8>(f);
+    }
+};
+struct BwdKernels {
+    static constexpr int kind = 1;
+    template <int V, int LC, int NW, bool NTL, bool NTS, bool HALF>
+    static auto plain() { return gae_bwd_kernel<V, LC, NW, NTL, NTS, HALF>; }
+    template <int V, int LC, int NW, bool NTL, bool NTS, bool FULLB>
+    static auto pipelined() { return gae_bwd_pf_kernel<V, LC, NW, NTL, NTS, FULLB>; }
+    template <class F> static void for_each_pf_cfg(F& f) {
+        cfg_row<1, 8, 2, 4, 8>(f);
+        cfg_row<2, 2, 2, 4, 8>(f); cfg_row<2, 4, 2, 4, 8>(f); cfg_row<2, 8, 2, 4, 8>(f);
+        cfg_row<4, 2, 2, 4, 8>(f); cfg_row<4, 4, 2, 4, 8>(f); cfg_row<4, 8, 2, 4, 8>(f);
+    }
+};
 
-// the pipelined forward: (V, LC) x NW in {2,4,8}, nontemporal stores, both load flavours
-template <class... A>
-inline bool dispatch_fwd_pf(const Cfg& cfg, int B, hipStream_t st, A... args) {
+// The one launch site: records cfg, launches the instantiation of K's kernels it names with the kernel's arguments `args`,
+// and answers HPC_RLL_EUNSUPPORTED (nothing launched) when there is none.  The order in which the tables and the flag
+// tests below name the kernels is the order of the kernels in the code object: reorder them and every kernel moves to
+// another address (profiles/r28_gae_share.txt, 2: worth +-0.1 us on single shapes).
+template <class K, class... A>
+inline int dispatch(const Cfg& cfg, int B, hipStream_t st, A... args) {
+    note_cfg(K::kind, cfg);
     bool hit = false;
-    auto go = [&](auto V_, auto LC_, auto NW_) {
-        constexpr int V = decltype(V_)::value, LC = decltype(LC_)::value, NW = decltype(NW_)::value;
-        if (!hit && cfg.v == V && cfg.lc == LC && cfg.nw == NW) {
-            const dim3 grid((unsigned)((B + 64 * V - 1) / (64 * V))), block(NW * 64);
-            const bool full = (B % (64 * V)) == 0;
-            if (cfg.flags & 1) {
-                if (full) launch(gae_fwd_pf_kernel<V, LC, NW, true, true, true>, grid, block, st, 0, args...);
-                else launch(gae_fwd_pf_kernel<V, LC, NW, true, true, false>, grid, block, st, 0, args...);
-            } else {
-                if (full) launch(gae_fwd_pf_kernel<V, LC, NW, false, true, true>, grid, block, st, 0, args...);
-                else launch(gae_fwd_pf_kernel<V, LC, NW, false, true, false>, grid, block, st, 0, args...);
-            }
-            hit = true;
-        }
+    auto go = [&](auto kernel, int tile, int nw) {
+        launch(kernel, dim3((unsigned)((B + tile - 1) / tile)), dim3(nw * 64), st, K::kind, args...);
+        hit = true;
     };
-#define HPC_RLL_PF_ROW(V, LC) go(I<V>{}, I<LC>{}, I<2>{}); go(I<V>{}, I<LC>{}, I<4>{}); go(I<V>{}, I<LC>{}, I<8>{});
-    HPC_RLL_PF_ROW(1, 8) HPC_RLL_PF_ROW(1, 16) HPC_RLL_PF_ROW(2, 4) HPC_RLL_PF_ROW(2, 8) HPC_RLL_PF_ROW(2, 16)
-    HPC_RLL_PF_ROW(4, 4) HPC_RLL_PF_ROW(4, 8)
-#undef HPC_RLL_PF_ROW
-    return hit;
-}
-
-template <class... A>
-inline bool dispatch_bwd_pf(const Cfg& cfg, int B, hipStream_t st, A... args) {
-    bool hit = false;
-    auto go = [&](auto V_, auto LC_, auto NW_) {
-        constexpr int V = decltype(V_)::value, LC = decltype(LC_)::value, NW = decltype(NW_)::value;
-        if (!hit && cfg.v == V && cfg.lc == LC && cfg.nw == NW) {
-            const dim3 grid((unsigned)((B + 64 * V - 1) / (64 * V))), block(NW * 64);
-            const bool full = (B % (64 * V)) == 0;
-            if (cfg.flags & 1) {
-                if (full) launch(gae_bwd_pf_kernel<V, LC, NW, true, true, true>, grid, block, st, 1, args...);
-                else launch(gae_bwd_pf_kernel<V, LC, NW, true, true, false>, grid, block, st, 1, args...);
-            } else {
-                if (full) launch(gae_bwd_pf_kernel<V, LC, NW, false, true, true>, grid, block, st, 1, args...);
-                else launch(gae_bwd_pf_kernel<V, LC, NW, false, true, false>, grid, block, st, 1, args...);
+    auto flag = [](bool x, auto&& f) { if (x) f(std::true_type{}); else f(std::false_type{}); };
+    const bool ntl = cfg.flags & 1;
+    if (cfg.pf) {
+        auto f = [&](auto V_, auto LC_, auto NW_) {
+            constexpr int V = V_, LC = LC_, NW = NW_;
+            if (hit || cfg.v != V || cfg.lc != LC || cfg.nw != NW) return;
+            flag(ntl, [&](auto NTL) { flag(B % (64 * V) == 0, [&](auto FULLB) {
+                go(K::template pipelined<V, LC, NW, NTL(), true, FULLB()>(), 64 * V, NW);
+            }); });
+        };
+        K::for_each_pf_cfg(f);
+    } else if (cfg.half) {   // (1, 8 or 16, 16), nontemporal stores
+        flag(cfg.lc == 16, [&](auto LC16) { flag(ntl, [&](auto NTL) {
+            go(K::template plain<1, LC16() ? 16 : 8, 16, NTL(), true, true>(), 32, 16);
+        }); });
+    } else {
+        auto f = [&](auto V_, auto LC_, auto NW_) {
+            constexpr int V = V_, LC = LC_, NW = NW_;
+            if (hit || cfg.v != V || cfg.lc != LC || cfg.nw != NW) return;
+            switch (cfg.flags) {   // bit 0: nontemporal loads, bit 1: nontemporal stores
+                case 0: go(K::template plain<V, LC, NW, false, false, false>(), 64 * V, NW); break;
+                case 1: go(K::template plain<V, LC, NW, true, false, false>(), 64 * V, NW); break;
+                case 2: go(K::template plain<V, LC, NW, false, true, false>(), 64 * V, NW); break;
+                default: go(K::template plain<V, LC, NW, true, true, false>(), 64 * V, NW); break;
             }
-            hit = true;
-        }
-    };
-#define HPC_RLL_PF_ROW(V, LC) go(I<V>{}, I<LC>{}, I<2>{}); go(I<V>{}, I<LC>{}, I<4>{}); go(I<V>{}, I<LC>{}, I<8>{});
-    HPC_RLL_PF_ROW(1, 8) HPC_RLL_PF_ROW(2, 2) HPC_RLL_PF_ROW(2, 4) HPC_RLL_PF_ROW(2, 8)
-    HPC_RLL_PF_ROW(4, 2) HPC_RLL_PF_ROW(4, 4) HPC_RLL_PF_ROW(4, 8)
-#undef HPC_RLL_PF_ROW
-    return hit;
-}
-
-inline int check_launch() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? HPC_RLL_OK : (int)e;
+        };
+        for_each_cfg(f);
+    }
+    return hit ? last_error() : HPC_RLL_EUNSUPPORTED;
 }
 
 }  // namespace
@@ -937,7 +921,7 @@ extern "C" int hpc_rll_gae_coef(float* coef, int T, float gamma, float lambda, v
     if (!coef) return HPC_RLL_EINVAL;
     hipLaunchKernelGGL(gae_coef_kernel, dim3((T + 255) / 256), dim3(256), 0, (hipStream_t)stream, coef, T, gamma,
                        lambda);
-    return check_launch();
+    return last_error();
 }
 
 extern "C" int hpc_rll_gae_forward_ex(const float* value, const float* reward, float* adv, const float* coef,
@@ -949,15 +933,7 @@ extern "C" int hpc_rll_gae_forward_ex(const float* value, const float* reward, f
     if (flags >= 0 && (flags & ~15)) return HPC_RLL_EUNSUPPORTED;   // bits 4, 5: retired in round 5
     const Cfg cfg = choose_cfg(true, T, B, max_vec(B, {value, reward, adv}), vec, lc, nw, flags);
     if (cfg.pf_refused) return HPC_RLL_EUNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    if (cfg.pf) {
-        std::atomic<int>* lc_ = g_kt.last_cfg[0];
-        lc_[0] = cfg.v; lc_[1] = cfg.lc; lc_[2] = cfg.nw; lc_[3] = cfg.flags; lc_[4] = 0; lc_[5] = 1;
-        if (!dispatch_fwd_pf(cfg, B, st, value, reward, adv, coef, T, B, gamma)) return HPC_RLL_EUNSUPPORTED;
-        return check_launch();
-    }
-    HPC_RLL_GAE_DISPATCH(gae_fwd_kernel, 0, value, reward, adv, coef, T, B, gamma);
-    return check_launch();
+    return dispatch<FwdKernels>(cfg, B, (hipStream_t)stream, value, reward, adv, coef, T, B, gamma);
 }
 
 extern "C" int hpc_rll_gae_forward(const float* value, const float* reward, float* adv, const float* coef, int T,
@@ -985,15 +961,7 @@ extern "C" int hpc_rll_gae_backward_ex(const float* grad_adv, float* grad_value,
         cfg.pf = false;                               // it was asked for, and is reported
         cfg.flags = cfg.plain_flags;
     }
-    hipStream_t st = (hipStream_t)stream;
-    if (cfg.pf) {
-        std::atomic<int>* lc_ = g_kt.last_cfg[1];
-        lc_[0] = cfg.v; lc_[1] = cfg.lc; lc_[2] = cfg.nw; lc_[3] = cfg.flags; lc_[4] = 0; lc_[5] = 1;
-        if (!dispatch_bwd_pf(cfg, B, st, grad_adv, grad_value, grad_reward, coef, T, B, gamma)) return HPC_RLL_EUNSUPPORTED;
-        return check_launch();
-    }
-    HPC_RLL_GAE_DISPATCH(gae_bwd_kernel, 1, grad_adv, grad_value, grad_reward, coef, T, B, gamma);
-    return check_launch();
+    return dispatch<BwdKernels>(cfg, B, (hipStream_t)stream, grad_adv, grad_value, grad_reward, coef, T, B, gamma);
 }
 
 extern "C" int hpc_rll_gae_backward(const float* grad_adv, float* grad_value, float* grad_reward, const float* coef,

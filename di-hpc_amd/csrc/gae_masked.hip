@@ -266,11 +266,6 @@ inline void launch(const Op& op, int T, int B, hipStream_t st) {
     scan_note<Op, V, LC, NW, HALF ? 2 : 1>((long)grid);   // hpc_rll_scan_last_config: the instantiation just launched
 }
 
-inline int check_launch() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? HPC_RLL_OK : (int)e;
-}
-
 }  // namespace
 }  // namespace hpc_rll
 
@@ -297,7 +292,7 @@ extern "C" int hpc_rll_gae_masked_forward(const float* value, const float* next_
             launch<decltype(V_)::value, decltype(LC_)::value, decltype(NW_)::value, decltype(H_)::value != 0>(op, T, B, st);
         });
     });
-    return check_launch();
+    return last_error();
 }
 
 extern "C" int hpc_rll_gae_masked_backward(const float* grad_adv, const void* done, const void* traj_flag,
@@ -335,5 +330,5 @@ extern "C" int hpc_rll_gae_masked_backward(const float* grad_adv, const void* do
             scan_note_launch(HPC_RLL_SCAN_OP_GAE_MASKED_BWD, V, LC, NW, HALF ? 2 : 1, NTL, MT, MM, NVF, (long)grid);
         });
     });
-    return check_launch();
+    return last_error();
 }
