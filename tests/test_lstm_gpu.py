@@ -311,10 +311,23 @@ def test_lstm_input_without_grad(S, B, I, H, L):
         assert torch.equal(a, b)
 
 
-@pytest.mark.parametrize("B", [16, 4])          # mid-batch kernel / persistent path, each against the step kernels
-def test_lstm_dropout(B):
+# mid-batch kernel / persistent path, each against the step kernels; then the two small-batch paths by name, with the path
+# records asserted: the layer wavefront, and the per-layer persistent kernels with the wavefront switched off (key 8 = 0)
+@pytest.mark.parametrize("shape,key8,want", [((8, 16, 32, 64, 3), 1, None), ((8, 4, 32, 64, 3), 1, None),
+                                             ((4, 2, 12, 48, 3), 1, 2), ((4, 4, 12, 512, 2), 0, 1)],
+                         ids=["16", "4", "wavefront", "per-layer"])
+def test_lstm_dropout(shape, key8, want):
     from hpc_rll.torch_utils.network.rnn import LSTM
-    S, I, H, L = 8, 32, 64, 3
+    import hpc_torch_utils_network as N
+    S, B, I, H, L = shape
+    N.tune_set(8, key8)
+    try:
+        _lstm_dropout(LSTM, N, S, B, I, H, L, want)
+    finally:
+        N.tune_set(8, 1)
+
+
+def _lstm_dropout(LSTM, N, S, B, I, H, L, want):
     torch.manual_seed(1)
     m = LSTM(S, B, I, H, L, dropout=0.5).to(DEV)
     x = torch.randn(S, B, I, device=DEV)
@@ -330,7 +343,7 @@ def test_lstm_dropout(B):
     torch.manual_seed(5)
     y2, _ = m(x, None)
     assert torch.equal(y1, y2)                         # same seed -> same mask
-    import hpc_torch_utils_network as N
+    assert want is None or N.lstm_last_forward_path() == want, (N.lstm_last_forward_path(), want)
     try:                                               # every path draws the same stateless-hash mask
         N.tune_set(3, 0)
         torch.manual_seed(5)
@@ -349,10 +362,12 @@ def test_lstm_dropout(B):
         return [xg.grad.cpu().numpy()] + [p.grad.cpu().numpy() for p in m.parameters()]
 
     g1 = grads()
+    assert want is None or (N.lstm_last_forward_path(), N.lstm_last_backward_path()) == (want, want)
     assert np.isfinite(g1[0]).all() and np.abs(g1[0]).sum() > 0
     try:                                               # backward applies the same masks on every path
         N.tune_set(3, 0)
         g0 = grads()
+        assert want is None or (N.lstm_last_forward_path(), N.lstm_last_backward_path()) == (0, 0)
     finally:
         N.tune_set(3, 1)
     for a, b in zip(g0, g1):
