@@ -16,6 +16,19 @@ inline int last_error() {
 // an absent (null) optional pointer restricts nothing: it counts as aligned
 inline bool aligned(const void* p, size_t a) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
+inline int device_cus() {   // CU count of the current device (cached per device; 0 on error)
+    constexpr int kMax = 64;
+    static int cus[kMax] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMax) return 0;
+    if (cus[dev] == 0) {
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) v = 0;
+        cus[dev] = v > 0 ? v : -1;
+    }
+    return cus[dev] > 0 ? cus[dev] : 0;
+}
+
 // The dispatch record behind a hpc_rll_*_last_config: K plain ints of the host process, zero at load, not synchronised.
 // v[0] counts the launches so far, the rest describe the last one and read as -1 before the first.
 template <int K> struct LaunchRecord {

@@ -17,6 +17,11 @@
 // the caller must know the bucket shapes to allocate them (3 * group + 4 integers come back).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "hostutil.hpp"
 #include "hpc_rll_hip.h"
 #include "pad_group.hpp"
 
@@ -25,11 +30,6 @@ namespace {
 
 constexpr int kMaxBins = 16385;        // lengths 0..16384: the run DP is O(group * D^2) in one workgroup
 constexpr int kSortChunk = 1024;       // rows per workgroup of the radix passes: 4 slots x 256 threads
-
-inline int last_err() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? HPC_RLL_OK : (int)e;
-}
 
 // ------------------------------------------------------------------------------------------------ 1. histogram
 __global__ __launch_bounds__(256) void len_hist_kernel(const int64_t* __restrict__ lengths, long n, int max_len,
@@ -475,7 +475,7 @@ extern "C" int hpc_rll_pad1d_group_plan(const int64_t* lengths, int64_t n, int m
         kin = kout;
         kout = const_cast<int32_t*>(tmp);
     }
-    return last_err();
+    return last_error();
 }
 
 extern "C" int hpc_rll_pad1d_group_forward(const int64_t* table, const int64_t* order, const int64_t* plan, int group,
@@ -487,5 +487,187 @@ extern "C" int hpc_rll_pad1d_group_forward(const int64_t* table, const int64_t* 
     const int64_t blocks = 256 * 16;        // 16 workgroups of 4 waves per CU, rows dealt round robin
     hipLaunchKernelGGL(pad_groups_kernel<64>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, table, order, plan,
                        group, out, mask, (float)value);
-    return last_err();
+    return last_error();
+}
+
+// ---- group splitting policies (host logic; reference: padding.cu:8-108).  sizes: n x dim, row-major, the list is
+// already sorted by numel.  Outputs: group_shapes (<= group rows of dim ints), positions (<= group+1 ints).
+// Returns the number of groups (>= 1) or a negative error.
+namespace {
+// Lists sorted by element count: cost(k,i) = key[i-1] * (i-k) with key nondecreasing satisfies the quadrangle
+// inequality, so the smallest optimal split point is monotone in i and each DP layer is a divide-and-conquer in
+// O(n log n) instead of O(n^2) (the reference's O(group * n^2) DP with stack VLAs breaks long before
+// n ~ 1e6).  Ties resolve to the smallest split point, exactly like the quadratic DP.
+//   rank 1: key = the length                 -> the exact padded-element count (padding.cu:44-108)
+//   rank 2/3 (long lists only): key = numel  -> the cost model of hpc_rll/origin/padding.py:16-17 (arr[end] * count);
+//     the per-dimension maxima of padding.cu are not monotone in a numel-sorted list, their exact DP stays quadratic
+//     and is kept for n <= 512.  The group SHAPES are always the true per-dimension maxima.
+// E: element count of the first k items (E[k] = k for the element-level DP, the run boundaries for the run-level one)
+void dc_layer(const int64_t* key, const int64_t* E, const int64_t* prev, int64_t* cur, int32_t* arg, int lo, int hi, int klo,
+              int khi, int64_t INF) {
+    if (lo > hi) return;
+    const int mid = (lo + hi) >> 1;
+    int64_t best = INF;
+    int32_t bk = klo;
+    const int kend = khi < mid - 1 ? khi : mid - 1;
+    for (int k = klo; k <= kend; ++k) {
+        if (prev[k] >= INF) continue;
+        const int64_t c = prev[k] + key[mid - 1] * (E[mid] - E[k]);
+        if (c < best) { best = c; bk = k; }
+    }
+    cur[mid] = best;
+    arg[mid] = bk;
+    dc_layer(key, E, prev, cur, arg, lo, mid - 1, klo, best >= INF ? khi : bk, INF);
+    dc_layer(key, E, prev, cur, arg, mid + 1, hi, best >= INF ? klo : bk, khi, INF);
+}
+
+// monotone DP over m items (elements, or runs of equal keys) into M groups; ps[0..M] = item boundaries
+void dc_split(const int64_t* key, const int64_t* E, int m, int M, std::vector<int32_t>& ps) {
+    const int64_t INF = kSplitInf;
+    std::vector<int32_t> pos((size_t)(m + 1) * (M + 1), 0);
+    std::vector<int64_t> prev(m + 1, INF), cur(m + 1, INF);
+    std::vector<int32_t> arg(m + 1, 0);
+    prev[0] = 0;
+    for (int j = 1; j <= M; ++j) {
+        std::fill(cur.begin(), cur.end(), INF);
+        dc_layer(key, E, prev.data(), cur.data(), arg.data(), 1, m, 0, m - 1, INF);
+        for (int i = 1; i <= m; ++i) pos[(size_t)i * (M + 1) + j] = arg[i];
+        prev.swap(cur);
+    }
+    ps.assign(M + 1, 0);
+    int lp = m;
+    ps[M] = m;
+    for (int j = M; j >= 1; --j) { lp = pos[(size_t)lp * (M + 1) + j]; ps[j - 1] = lp; }
+}
+}  // namespace
+
+namespace hpc_rll { int g_split_algo = 0; }   // hpc_rll_tune_set key 22: 0 = runs of equal keys (default), 1 = the
+                                              // round-2 paths (quadratic element DP / divide-and-conquer over elements)
+
+extern "C" int hpc_rll_oracle_split_group(const int32_t* sizes, int n, int dim, int group, int32_t* group_shapes,
+                                          int32_t* positions) {
+    if (!sizes || n <= 0 || dim <= 0 || dim > 3 || group <= 0 || !group_shapes || !positions) return HPC_RLL_EINVAL;
+    const int M = group < n ? group : n;  // more groups than tensors is meaningless (the reference would walk off)
+    const int64_t INF = kSplitInf;
+    // lists sorted by element count (the documented precondition; hpc_rll/rl_utils/padding.py sorts): DP on the key
+    std::vector<int64_t> key(n);
+    bool sorted = true;
+    for (int i = 0; i < n; ++i) {
+        int64_t e = 1;
+        for (int d = 0; d < dim; ++d) e *= sizes[(size_t)i * dim + d];
+        key[i] = e;
+        if (i && key[i] < key[i - 1]) { sorted = false; break; }
+    }
+    // (which key and which DP by rank and n: above, at dc_layer)
+    const bool by_key = sorted && (dim == 1 || n > 512);
+    if (!by_key && n > 20000) return HPC_RLL_EUNSUPPORTED;   // the quadratic DP would take hours: sort the list first
+    std::vector<int32_t> ps;
+    if (by_key && g_split_algo == 0) {
+        // runs of equal keys (pad_group.hpp): O(n) + O(M D log D) for D distinct keys
+        std::vector<int64_t> val, E(1, 0);
+        for (int i = 0; i < n; ++i) {
+            if (val.empty() || key[i] != val.back()) { val.push_back(key[i]); E.push_back(E.back()); }
+            ++E.back();
+        }
+        const int D = (int)val.size();
+        std::vector<int64_t> pe(M + 1, 0);
+        if (D < M) {
+            std::vector<int32_t> gm(M);
+            split_runs_few(val.data(), E.data(), D, (int64_t)n, M, pe.data(), gm.data());
+        } else {
+            std::vector<int32_t> pr;
+            dc_split(val.data(), E.data(), D, M, pr);
+            for (int g = 0; g <= M; ++g) pe[g] = E[pr[g]];
+        }
+        ps.assign(pe.begin(), pe.end());
+    } else if (by_key && (dim > 1 || n > 512)) {
+        std::vector<int64_t> E(n + 1);
+        for (int i = 0; i <= n; ++i) E[i] = i;
+        dc_split(key.data(), E.data(), n, M, ps);
+    } else {
+        std::vector<int32_t> pos((size_t)(n + 1) * (M + 1), 0);
+        auto P = [&](int i, int j) -> int32_t& { return pos[(size_t)i * (M + 1) + j]; };
+        std::vector<int64_t> cost((size_t)(n + 1) * (M + 1), INF);
+        auto C = [&](int i, int j) -> int64_t& { return cost[(size_t)i * (M + 1) + j]; };
+        C(0, 0) = 0;
+        std::vector<int64_t> elems(n);  // elems[k] = prod_d max_{k<=t<=i-1} sizes[t][d]
+        for (int i = 1; i <= n; ++i) {
+            int32_t mx[3] = {0, 0, 0};
+            for (int k = i - 1; k >= 0; --k) {
+                int64_t e = 1;
+                for (int d = 0; d < dim; ++d) {
+                    mx[d] = std::max(mx[d], sizes[(size_t)k * dim + d]);
+                    e *= mx[d];
+                }
+                elems[k] = e;
+            }
+            for (int j = 1; j <= M; ++j) {
+                int64_t best = INF;
+                int32_t arg = 0;
+                for (int k = 0; k < i; ++k) {
+                    if (C(k, j - 1) >= INF) continue;
+                    const int64_t c = C(k, j - 1) + elems[k] * (i - k);
+                    if (c < best) { best = c; arg = k; }  // strict: the smallest k wins ties, like the reference
+                }
+                C(i, j) = best;
+                P(i, j) = arg;
+            }
+        }
+        int lp = n, lc = M;
+        ps.push_back(n);
+        while (lp > 0) { lp = P(lp, lc); --lc; ps.push_back(lp); }
+        std::reverse(ps.begin(), ps.end());
+    }
+    const int ng = (int)ps.size() - 1;
+    for (int g = 0; g < ng; ++g) {
+        for (int d = 0; d < dim; ++d) {
+            int32_t m = 0;
+            for (int t = ps[g]; t < ps[g + 1]; ++t) m = std::max(m, sizes[(size_t)t * dim + d]);
+            group_shapes[g * dim + d] = m;
+        }
+    }
+    for (int g = 0; g <= ng; ++g) positions[g] = ps[g];
+    return ng;
+}
+
+extern "C" int hpc_rll_sample_split_group(const int32_t* sizes, int n, int dim, int group, uint64_t seed,
+                                          int32_t* group_shapes, int32_t* positions) {
+    if (!sizes || n <= 0 || dim <= 0 || dim > 3 || group <= 0 || !group_shapes || !positions) return HPC_RLL_EINVAL;
+    auto next_rand = [&seed]() {  // splitmix64
+        uint64_t z = (seed += 0x9E3779B97F4A7C15ull);
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        return z ^ (z >> 31);
+    };
+    std::vector<int> cut;
+    if (n >= 3) {  // the reference draws from [1, n-2] and divides by zero for n = 2 (padding.cu:17)
+        int last = -1;
+        for (int i = 0; i < group - 1; ++i) {
+            int now = last;
+            if (n == 3) now = 1;
+            else while (now == last) now = (int)(next_rand() % (uint64_t)(n - 2)) + 1;
+            cut.push_back(now);
+            last = now;
+        }
+        std::sort(cut.begin(), cut.end());
+    }
+    cut.push_back(n - 1);
+    int ng = 0, last_idx = -1;
+    for (int idx : cut) {
+        if (idx <= last_idx) continue;
+        int32_t shape[3] = {-1, -1, -1};
+        for (int t = last_idx + 1; t <= idx; ++t)
+            for (int d = 0; d < dim; ++d) shape[d] = std::max(shape[d], sizes[(size_t)t * dim + d]);
+        // same padded shape as the previous group: the reference skips the cut WITHOUT moving last_idx (padding.cu:34-35),
+        // so these rows join the NEXT accepted group -- or, after the final cut, the previous one (its end is N).  Mirrored
+        // exactly.  What is not reproduced: a repeated cut position (idx <= last_idx) makes the reference emit an
+        // EMPTY group of shape -1 (its loop over last_idx+1 .. idx is empty), which GroupPad then cannot allocate; dropped.
+        if (ng > 0 && std::memcmp(shape, group_shapes + (ng - 1) * dim, sizeof(int32_t) * dim) == 0) continue;
+        for (int d = 0; d < dim; ++d) group_shapes[ng * dim + d] = shape[d];
+        positions[ng] = last_idx + 1;
+        ++ng;
+        last_idx = idx;
+    }
+    positions[ng] = n;
+    return ng;
 }

@@ -1,5 +1,5 @@
 // pad_group.hpp -- the group-split policy on RUNS of equal keys, shared by the host entry point
-// (hpc_rll_oracle_split_group, pad_scatter.hip) and the device plan kernel (pad_group.hip).
+// (hpc_rll_oracle_split_group) and the device plan kernel (split_plan_kernel), both in pad_group.hip.
 //
 // Reference: hpc_rll/origin/padding.py:11-50 (oracle_split_group: DP over ELEMENTS, O(group * n^2), exactly `group`
 // non-empty groups, cost of a group = its largest key x its element count, ties resolved to the smallest split point)

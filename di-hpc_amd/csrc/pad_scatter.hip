@@ -28,13 +28,11 @@
 
 #include <algorithm>
 #include <cstdlib>
-#include <cstring>
-#include <vector>
 
 #include "hostutil.hpp"
 #include "hpc_rll_hip.h"
+#include "padsc_plan.hpp"
 #include "wave.hpp"
-#include "pad_group.hpp"
 
 namespace hpc_rll {
 namespace {
@@ -169,7 +167,7 @@ __global__ __launch_bounds__(256) void pad1d_packed_kernel(const float* __restri
                                                            unsigned L, double inv, int RB, float fill, int ifill) {
     typedef int vint4 __attribute__((ext_vector_type(4)));
     extern __shared__ float tile[];                   // RB * L + 8 floats, then RB + 1 int64 offsets (8-byte aligned)
-    long* s_off = reinterpret_cast<long*>(tile + (((size_t)RB * L + 8 + 1) & ~(size_t)1));
+    long* s_off = reinterpret_cast<long*>(tile + packed_tile_floats(RB, L));
     const uintptr_t base = reinterpret_cast<uintptr_t>(flat);
     for (long r0 = (long)blockIdx.x * RB; r0 < n; r0 += (long)gridDim.x * RB) {
         const int nr = (int)(n - r0 < RB ? n - r0 : RB);
@@ -328,7 +326,7 @@ __global__ __launch_bounds__(256) void unpad1d_packed_kernel(const float* __rest
                                                              float* __restrict__ flat, long n, long total, unsigned L, double inv,
                                                              int RB) {
     extern __shared__ float tile[];
-    long* s_off = reinterpret_cast<long*>(tile + (((size_t)RB * L + 8 + 1) & ~(size_t)1));
+    long* s_off = reinterpret_cast<long*>(tile + packed_tile_floats(RB, L));
     const uintptr_t base = reinterpret_cast<uintptr_t>(flat);
     for (long r0 = (long)blockIdx.x * RB; r0 < n; r0 += (long)gridDim.x * RB) {
         const int nr = (int)(n - r0 < RB ? n - r0 : RB);
@@ -741,7 +739,6 @@ __global__ __launch_bounds__(1024) void scatter_out4_kernel(const float* __restr
 // min (empty = -1 = the largest unsigned), next[m] = the smallest later entity at the same cell, found with broadcast reads of
 // the cell list (M <= 1024; 1024 / M threads share an entity's walk over the M / 4 quads).  The same table scatter_index_kernel leaves in memory, so the
 // same output bits.  At C5 the index launch took 64 of the forward's 880 us; a workgroup spends ~1 us here.
-constexpr int kScatterCollRows = 32;   // extra x-tile rows for the cells with several entities (add, in-kernel tables)
 template <bool ADD, bool BUILD>
 __global__ __launch_bounds__(1024) void scatter_out_lds_kernel(const float* __restrict__ x,
                                                               const int32_t* __restrict__ idx,
@@ -753,10 +750,11 @@ __global__ __launch_bounds__(1024) void scatter_out_lds_kernel(const float* __re
     const int n0 = blockIdx.x * npb;
     const int nn = min(npb, N - n0);                       // channels of this workgroup
     const int ld = npb + 1;
-    float* xs = s_dyn;                                     // [M][ld]
-    const int tile_rows = M + (ADD && BUILD ? kScatterCollRows : 0);
-    int32_t* s_first = reinterpret_cast<int32_t*>(s_dyn + (((size_t)tile_rows * ld + 3) & ~(size_t)3));   // [HW] head (add) / last (cover), 16-byte aligned
-    int32_t* s_next = s_first + HW;                        // [M]   (add only)
+    const ScatterFwdCarve carve(M, HW, npb, ADD, BUILD);   // padsc_plan.hpp
+    int32_t* const s_int = reinterpret_cast<int32_t*>(s_dyn);
+    float* xs = s_dyn + carve.x;                           // [M][ld]
+    int32_t* s_first = s_int + carve.first;                // [HW] head (add) / last (cover), 16-byte aligned
+    int32_t* s_next = s_int + carve.next;                  // [M]   (add only)
     const float* __restrict__ xb = x + (size_t)b * M * N + n0;
     // the x tile (float4 along the channels when aligned)
     auto stage_x = [&]() {
@@ -779,11 +777,11 @@ __global__ __launch_bounds__(1024) void scatter_out_lds_kernel(const float* __re
     // map -- gets a row of its own in the x tile, the chain's sum per channel (ascending m, as everywhere), and points at it: the
     // stream loop then treats `add` like `cover`, ONE branch-free gather per cell.  Up to kScatterCollRows such cells per batch
     // element; a batch element with more keeps the chain walk in the loop.
-    int32_t* s_coll = s_next + 2 * ((M + 3) & ~3);         // [kScatterCollRows] cells, [kScatterCollRows] chain heads, then the counter
-    int32_t* s_ncoll = s_coll + 2 * kScatterCollRows;
+    int32_t* s_coll = s_int + carve.coll;                  // [kScatterCollRows] cells, [kScatterCollRows] chain heads, then the counter
+    int32_t* s_ncoll = s_int + carve.ncoll;
     if (ADD && BUILD && threadIdx.x == 0) *s_ncoll = 0;
     if (BUILD) {
-        int32_t* s_cell = s_next + ((M + 3) & ~3);         // [M rounded to 4]   (add only)
+        int32_t* s_cell = s_int + carve.cell;              // [M rounded to 4]   (add only)
         const int64_t* __restrict__ loc = location + (size_t)b * M * 2;
         const int H = HW / W;
         const int m4 = (M + 3) & ~3;
@@ -841,7 +839,7 @@ __global__ __launch_bounds__(1024) void scatter_out_lds_kernel(const float* __re
     __syncthreads();
     bool walk = ADD;                                        // the stream loop walks chains (uniform)
     if (ADD && BUILD) {
-        const int32_t* s_cell = s_next + ((M + 3) & ~3);
+        const int32_t* s_cell = s_int + carve.cell;
         for (int m = threadIdx.x; m < M; m += 1024) {
             const int32_t c = s_cell[m];
             if (c >= 0 && s_first[c] == m && s_next[m] >= 0) {   // m heads a chain of two or more
@@ -981,6 +979,25 @@ __global__ __launch_bounds__(1024) void scatter_out_lds_kernel(const float* __re
 // (Round 4 also tried WAVE tiles -- no LDS, no workgroup barrier, a wave owning 1024 cells x 16 channels with the owners in
 // registers, the structure that took the packed pad kernel from 5.0 to 6.2 TB/s: slower here on every shape; removed in round 5.)
 
+// The XCD-major workgroup orders of the two backward kernels: (bi, ci) = (batch element, piece inside it) of this workgroup,
+// on entry (blockIdx.y, blockIdx.x).  Workgroup i runs on XCD i % 8.
+//   order 1: L = (i % 8) * (total / 8) + i / 8 as the logical index -- the pieces of a batch element take consecutive slots of ONE XCD;
+//   order 2 (round 6): XCD x takes the batch elements b = 8 q + x -- the eight XCDs read EIGHT NEIGHBOURING batch elements at any
+//     time (one moving window of grad_out) instead of eight streams total/8 apart, whose relative placement in the memory
+//     channels made the plane kernel 12 % slower on some allocations of grad_out (profiles/r06_scatter_bwd_probe.txt).
+__device__ __forceinline__ void xcd_remap(int order, unsigned& bi, unsigned& ci) {
+    if (order == 2) {
+        const unsigned nx = gridDim.x, id = blockIdx.x + nx * blockIdx.y, slot = id >> 3;
+        bi = (slot / nx) * 8 + (id & 7u);
+        ci = slot % nx;
+    } else if (order) {
+        const unsigned nx = gridDim.x, total = nx * gridDim.y, id = blockIdx.x + nx * blockIdx.y;
+        const unsigned L = (id & 7u) * (total >> 3) + (id >> 3);
+        bi = L / nx;
+        ci = L - bi * nx;
+    }
+}
+
 // backward: workgroup = (b, group of NG channels); stage NG planes of grad_out in LDS, gather per entity.
 // The planes are one contiguous span of grad_out: staged with nontemporal float4 loads, 1024 threads and up to
 // 128 KB per workgroup so that every thread has several 16-byte loads in flight (a pure read streams at 7 TB/s on this
@@ -992,23 +1009,10 @@ __global__ __launch_bounds__(1024) void scatter_bwd_lds_kernel(const float* __re
     extern __shared__ __attribute__((aligned(16))) float s_plane[];  // NG * HW
     // xcd_order (round 4, tune key 38): the workgroups of ONE batch element write 16-byte pieces of the same 128-byte lines of
     // grad_x (an entity's row is N floats; a workgroup owns NG of them).  Dispatched in launch order they land on eight different
-    // XCDs -- eight L2s each holding a partial line, each written back masked.  Workgroup i runs on XCD i % 8: with
-    // L = (i % 8) * (total / 8) + i / 8 as the logical index, the channel groups of a batch element take consecutive slots of one
-    // XCD and their pieces meet in ONE L2 before the line leaves it.
+    // XCDs -- eight L2s each holding a partial line, each written back masked.  Remapped (xcd_remap), the channel groups of a batch
+    // element run on one XCD and their pieces meet in ONE L2 before the line leaves it.
     unsigned bi = blockIdx.y, ci = blockIdx.x;
-    if (xcd_order == 2) {
-        // round 6: XCD x takes the batch elements b = 8 q + x -- the eight XCDs read EIGHT NEIGHBOURING batch elements at any time
-        // (one moving window of grad_out) instead of eight streams total/8 apart, whose relative placement in the memory
-        // channels made the kernel 12 % slower on some allocations of grad_out (profiles/r06_scatter_bwd_probe.txt)
-        const unsigned nx = gridDim.x, id = blockIdx.x + nx * blockIdx.y, slot = id >> 3;
-        bi = (slot / nx) * 8 + (id & 7u);
-        ci = slot % nx;
-    } else if (xcd_order) {
-        const unsigned nx = gridDim.x, total = nx * gridDim.y, id = blockIdx.x + nx * blockIdx.y;
-        const unsigned L = (id & 7u) * (total >> 3) + (id >> 3);
-        bi = L / nx;
-        ci = L - bi * nx;
-    }
+    xcd_remap(xcd_order, bi, ci);
     const int b = (int)bi;
     const int n0 = (int)ci * NG;
     const int ng = min(NG, N - n0);
@@ -1058,501 +1062,6 @@ __global__ __launch_bounds__(1024) void scatter_bwd_lds_kernel(const float* __re
     }
 }
 
-// (Round 4 also tried this backward as a PERSISTENT software-pipelined kernel -- eight loader waves keeping four planes in
-// flight by LDS-DMA, four gathering waves, the gathered block written once: 1.25 ms against 0.865 at C5; removed in round 5.)
-
-// fallback for planes too large for LDS: direct gather
-__global__ __launch_bounds__(256) void scatter_bwd_direct_kernel(const float* __restrict__ grad_out,
-                                                                 const int64_t* __restrict__ location,
-                                                                 float* __restrict__ grad_x, long total, int M,
-                                                                 int N, int H, int W) {
-    const long HW = (long)H * W;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        const int n = (int)(i % N);
-        const long bm = i / N;
-        const long b = bm / M;
-        const long y = location[2 * bm], xx = location[2 * bm + 1];
-        const bool ok = y >= 0 && y < H && xx >= 0 && xx < W;
-        grad_x[i] = ok ? grad_out[(b * N + n) * HW + y * W + xx] : 0.f;
-    }
-}
-
-}  // namespace
-}  // namespace hpc_rll
-
-namespace hpc_rll { int g_pad_wave = 1; }   // hpc_rll_tune_set key 28: packed Pad1D on wave tiles in output space (0 = the round-3 workgroup kernel)
-namespace hpc_rll {
-// path switches that tests flip (hpc_rll_tune_set, tune.hip)
-int g_scatter_lds_fwd = 1;   // key 17: 1 = LDS-staged streaming forward kernel where it applies, 0 = cells-per-thread kernel everywhere
-int g_scatter_npb = 0;       // key 18: channels per workgroup of the LDS-staged kernel (0 = by LDS budget)
-int g_scatter_build = 1;     // key 37: 1 = owner table / chain links built inside the forward kernel, 0 = index launch
-int g_scatter_bwd_xcd = 1;   // key 38: 1 = XCD-major workgroup order of the backward where its pieces are below a sector pair, 0 = launch order
-constexpr int g_scatter_threads = 1024;     // threads per workgroup of the cells-per-thread kernel on maps of >= 4096 cells
-int g_scatter_bwd_tile = 0;                 // hpc_rll_tune_set key 40: scatter backward by spatial tiles: 0 = by rule, 1 = never, 2 = wherever it applies
-constexpr int g_scatter_bwd_lds_kb = 64;    // planes staged per backward workgroup (profiles/r04_scatter_bwd_lds.txt)
-
-namespace {
-// The dispatch records (hpc_rll_pad_scatter_last_config): one per op, noted beside every launch with the grid, the workgroup
-// size and the LDS bytes OF THAT LAUNCH, so that a record names what ran, not a second evaluation of the rule.
-LaunchRecord<HPC_RLL_PAD_SCATTER_CONFIG_INTS> g_padsc_last[HPC_RLL_PADSC_OPS];
-int padsc_note(int rc, int op, int kernel, dim3 grid, unsigned threads, size_t lds, int a, int b) {
-    if (!rc) g_padsc_last[op].note({kernel, (int)grid.x, (int)(grid.y * grid.z), (int)threads, (int)lds, a, b});
-    return rc;
-}
-int padsc_note_no_launch(int rc, int op, int kernel, int a, int b) { return padsc_note(rc, op, kernel, dim3(0, 0, 0), 0, 0, a, b); }
-}  // namespace
-}
-using namespace hpc_rll;
-
-// handed: 1 = called by hpc_rll_pad1d_packed_forward in its own stead (noted in the record)
-static int pad_list_forward(const int64_t* table, float* new_x, int32_t* mask, int64_t n, int m0, int m1, int m2, int value,
-                            void* stream, int handed) {
-    if (n < 0 || m0 < 0 || m1 < 0 || m2 < 0) return HPC_RLL_EINVAL;
-    const long inner = (long)m0 * m1 * m2;
-    if (inner >= (1L << 31)) return HPC_RLL_EUNSUPPORTED;
-    const long total = n * inner;
-    if (total == 0) return HPC_RLL_OK;
-    if (!table || !new_x || !mask) return HPC_RLL_EINVAL;
-    const bool v4 = (total % 4) == 0 && (reinterpret_cast<uintptr_t>(new_x) & 15) == 0 &&
-                    (reinterpret_cast<uintptr_t>(mask) & 15) == 0;
-    long blocks = ((v4 ? total / 4 : total) + 255) / 256;
-    if (blocks > 256L * 16) blocks = 256L * 16;
-    int kernel;
-    if (v4 && m0 == 1 && m1 == 1 && total < (1L << 32)) {
-        kernel = HPC_RLL_PADSC_KERNEL_PAD1D4;
-        hipLaunchKernelGGL(pad1d4_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, table, new_x, mask,
-                           (long)n, (unsigned)m2, 1.0 / (double)m2, (float)value, value);
-    } else if (v4) {
-        kernel = HPC_RLL_PADSC_KERNEL_PAD4;
-        hipLaunchKernelGGL(pad4_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, table, new_x, mask,
-                           (long)n, (unsigned)m0, (unsigned)m1, (unsigned)m2, (float)value, value);
-    } else {
-        kernel = HPC_RLL_PADSC_KERNEL_PAD;
-        hipLaunchKernelGGL(pad_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, table, new_x, mask,
-                           (long)n, (unsigned)m0, (unsigned)m1, (unsigned)m2, (float)value, value);
-    }
-    return padsc_note(last_error(), HPC_RLL_PADSC_OP_PAD, kernel, dim3((unsigned)blocks), 256, 0, v4 ? 4 : 1, handed);
-}
-
-extern "C" int hpc_rll_pad_forward(const int64_t* table, float* new_x, int32_t* mask, int64_t n, int m0, int m1,
-                                   int m2, int value, void* stream) {
-    return pad_list_forward(table, new_x, mask, n, m0, m1, m2, value, stream, 0);
-}
-
-static int unpad_list_forward(const float* padded, const int64_t* table, float* flat, int64_t n, int64_t total, int m0, int m1,
-                              int m2, void* stream, int handed) {
-    if (n < 0 || total < 0 || m0 < 0 || m1 < 0 || m2 < 0) return HPC_RLL_EINVAL;
-    if (total == 0 || n == 0) return HPC_RLL_OK;
-    if (!padded || !table || !flat) return HPC_RLL_EINVAL;
-    const long padded_total = (long)n * m0 * m1 * m2;
-    if (m0 == 1 && m1 == 1 && m2 > 0 && (padded_total % 4) == 0 && padded_total < (1L << 32) &&
-        (reinterpret_cast<uintptr_t>(padded) & 15) == 0) {
-        long b4 = (padded_total / 4 + 255) / 256;
-        if (b4 > 256L * 16) b4 = 256L * 16;
-        hipLaunchKernelGGL(unpad1d4_kernel, dim3((unsigned)b4), dim3(256), 0, (hipStream_t)stream, padded, table, flat,
-                           (long)n, (long)total, (unsigned)m2, 1.0 / (double)m2);
-        return padsc_note(last_error(), HPC_RLL_PADSC_OP_UNPAD, HPC_RLL_PADSC_KERNEL_UNPAD1D4, dim3((unsigned)b4), 256, 0, 4, handed);
-    }
-    long blocks = (total + 255) / 256;
-    if (blocks > 256L * 16) blocks = 256L * 16;
-    hipLaunchKernelGGL(unpad_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, padded, table, flat,
-                       (long)n, (long)total, (unsigned)m0, (unsigned)m1, (unsigned)m2);
-    return padsc_note(last_error(), HPC_RLL_PADSC_OP_UNPAD, HPC_RLL_PADSC_KERNEL_UNPAD, dim3((unsigned)blocks), 256, 0, 1, handed);
-}
-
-extern "C" int hpc_rll_unpad_forward(const float* padded, const int64_t* table, float* flat, int64_t n,
-                                     int64_t total, int m0, int m1, int m2, void* stream) {
-    return unpad_list_forward(padded, table, flat, n, total, m0, m1, m2, stream, 0);
-}
-
-// rows per workgroup of the LDS-staged packed kernels: 16 (tests/tools/micro/padbw.hip at n = 2^20, L = 127: 16 rows and
-// one workgroup per 16 rows 270 us, 64 rows 303 us, the per-thread kernel 328 us), fewer when 60 KB of LDS hold fewer
-static inline int packed_rows_per_wg(int L) {
-    const long cap = (60L * 1024 / 4 - 160) / (L > 0 ? L : 1);
-    return (int)(cap > 16 ? 16 : cap);
-}
-
-extern "C" int hpc_rll_pad1d_packed_forward(const float* flat, const int64_t* table, float* new_x, int32_t* mask, int64_t n,
-                                            int max_len, int value, void* stream) {
-    if (n < 0 || max_len < 0) return HPC_RLL_EINVAL;
-    if (n == 0 || max_len == 0) return HPC_RLL_OK;
-    if (!flat || !table || !new_x || !mask) return HPC_RLL_EINVAL;
-    // Which kernel: new_x and mask 16-byte aligned (flat may start anywhere) and
-    //   32 <= max_len <= 16384 with key 28 = 1   the wave kernel (its tiles are 1024 elements whatever the row width: no RB);
-    //   otherwise, RB >= 1 (max_len <= 15200)     the workgroup kernel;
-    //   otherwise -- a misaligned output, or max_len > 15200 with key 28 = 0 or beyond 16384 -- the call is handed over to
-    //   hpc_rll_pad_forward (pad1d4_kernel / pad_kernel), which computes the same values.
-    const int RB = packed_rows_per_wg(max_len);
-    const bool al = (reinterpret_cast<uintptr_t>(new_x) & 15) == 0 && (reinterpret_cast<uintptr_t>(mask) & 15) == 0 &&
-                    (reinterpret_cast<uintptr_t>(flat) & 3) == 0;
-    const bool wave = al && max_len >= 32 && max_len <= 16384 && g_pad_wave;
-    if (!wave && !(al && RB >= 1))
-        return padsc_note_no_launch(pad_list_forward(table, new_x, mask, n, 1, 1, max_len, value, stream, 1),
-                                    HPC_RLL_PADSC_OP_PAD_PACKED, HPC_RLL_PADSC_KERNEL_HANDED_OVER, RB, 1);
-    if (wave) {   // wave tiles in output space (round 4)
-        const long ntiles = (long)(((unsigned long)n * (unsigned long)max_len + 1023) / 1024);
-        long wb = (ntiles + 3) / 4;
-        // (fewer, persistent workgroups -- the shape that makes a pure fill fast, profiles/r04_writebw.txt -- are SLOWER here:
-        // 1 / 2 / 4 / 8 workgroups per CU 612 / 466 / 324 / 315 us against 270 for the API call: a tile is a chain of table
-        // lookups, source loads, LDS and stores that needs many tiles in flight per CU)
-        if (wb > (1L << 20)) wb = 1L << 20;   // (every wave ONE tile: the 8192-workgroup cap of the first version, four tiles per wave, was 2.5 % slower)
-        hipLaunchKernelGGL(pad1d_packed_wave_kernel, dim3((unsigned)wb), dim3(256), 0, (hipStream_t)stream, flat, table, new_x, mask,
-                           (long)n, (unsigned)max_len, 1.0f / (float)max_len, (float)value, value);
-        return padsc_note(last_error(), HPC_RLL_PADSC_OP_PAD_PACKED, HPC_RLL_PADSC_KERNEL_PAD1D_PACKED_WAVE, dim3((unsigned)wb), 256, 0, RB, 0);
-    }
-    long blocks = (n + RB - 1) / RB;
-    if (blocks > (1L << 20)) blocks = 1L << 20;
-    const size_t lds = ((((size_t)RB * max_len + 8 + 1) & ~(size_t)1)) * 4 + (size_t)(RB + 1) * 8;
-    hipLaunchKernelGGL(pad1d_packed_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, flat, table, new_x, mask,
-                       (long)n, (unsigned)max_len, 1.0 / (double)max_len, RB, (float)value, value);
-    return padsc_note(last_error(), HPC_RLL_PADSC_OP_PAD_PACKED, HPC_RLL_PADSC_KERNEL_PAD1D_PACKED, dim3((unsigned)blocks), 256, lds, RB, 0);
-}
-
-extern "C" int hpc_rll_unpad1d_packed_forward(const float* padded, const int64_t* table, float* flat, int64_t n, int64_t total,
-                                              int max_len, void* stream) {
-    if (n < 0 || total < 0 || max_len < 0) return HPC_RLL_EINVAL;
-    if (n == 0 || total == 0 || max_len == 0) return HPC_RLL_OK;
-    if (!padded || !table || !flat) return HPC_RLL_EINVAL;
-    // `padded` 16-byte aligned (flat may start anywhere) and RB >= 1 (max_len <= 15200: at least one row fits the LDS tile): the
-    // workgroup kernel.  Otherwise the call is handed over to hpc_rll_unpad_forward (unpad1d4_kernel where `padded` is aligned
-    // and n * max_len % 4 == 0, else unpad_kernel), which computes the same values; there is no wave kernel in this direction.
-    const int RB = packed_rows_per_wg(max_len);
-    const bool ok = RB >= 1 && (reinterpret_cast<uintptr_t>(padded) & 15) == 0 && (reinterpret_cast<uintptr_t>(flat) & 3) == 0;
-    if (!ok)
-        return padsc_note_no_launch(unpad_list_forward(padded, table, flat, n, total, 1, 1, max_len, stream, 1),
-                                    HPC_RLL_PADSC_OP_UNPAD_PACKED, HPC_RLL_PADSC_KERNEL_HANDED_OVER, RB, 1);
-    long blocks = (n + RB - 1) / RB;
-    if (blocks > (1L << 20)) blocks = 1L << 20;
-    const size_t lds = ((((size_t)RB * max_len + 8 + 1) & ~(size_t)1)) * 4 + (size_t)(RB + 1) * 8;
-    hipLaunchKernelGGL(unpad1d_packed_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, padded, table, flat,
-                       (long)n, (long)total, (unsigned)max_len, 1.0 / (double)max_len, RB);
-    return padsc_note(last_error(), HPC_RLL_PADSC_OP_UNPAD_PACKED, HPC_RLL_PADSC_KERNEL_UNPAD1D_PACKED, dim3((unsigned)blocks), 256, lds, RB, 0);
-}
-
-extern "C" int64_t hpc_rll_packed_table_scratch_int64(int64_t n) {
-    return n <= 0 ? 1 : (n + kScanChunk - 1) / kScanChunk;
-}
-
-extern "C" int hpc_rll_packed_table(const int64_t* lengths, int64_t n, int64_t base, int64_t stride, int64_t* table,
-                                    int64_t* scratch, void* stream) {
-    if (n < 0) return HPC_RLL_EINVAL;
-    if (n == 0) return HPC_RLL_OK;
-    if (!lengths || !table || !scratch) return HPC_RLL_EINVAL;
-    const long nchunks = (long)((n + kScanChunk - 1) / kScanChunk);
-    if (nchunks > 0x7fffffffL) return HPC_RLL_EUNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(packed_chunk_sums_kernel, dim3((unsigned)nchunks), dim3(256), 0, st, lengths, (long)n, scratch);
-    if (nchunks <= 1024) {
-        hipLaunchKernelGGL(packed_table_kernel<true>, dim3((unsigned)nchunks), dim3(256), 0, st, lengths, (long)n, scratch, base,
-                           stride, table);
-        return last_error();
-    }
-    hipLaunchKernelGGL(packed_scan_sums_kernel, dim3(1), dim3(256), 0, st, scratch, nchunks);
-    hipLaunchKernelGGL(packed_table_kernel<false>, dim3((unsigned)nchunks), dim3(256), 0, st, lengths, (long)n, scratch, base,
-                       stride, table);
-    return last_error();
-}
-
-// ---- group splitting policies (host logic; reference: padding.cu:8-108).  sizes: n x dim, row-major, the list is
-// already sorted by numel.  Outputs: group_shapes (<= group rows of dim ints), positions (<= group+1 ints).
-// Returns the number of groups (>= 1) or a negative error.
-namespace {
-// Lists sorted by element count: cost(k,i) = key[i-1] * (i-k) with key nondecreasing satisfies the quadrangle
-// inequality, so the smallest optimal split point is monotone in i and each DP layer is a divide-and-conquer in
-// O(n log n) instead of O(n^2) (the reference's O(group * n^2) DP with stack VLAs breaks long before
-// n ~ 1e6).  Ties resolve to the smallest split point, exactly like the quadratic DP.
-//   rank 1: key = the length                 -> the exact padded-element count (padding.cu:44-108)
-//   rank 2/3 (long lists only): key = numel  -> the cost model of hpc_rll/origin/padding.py:16-17 (arr[end] * count);
-//     the per-dimension maxima of padding.cu are not monotone in a numel-sorted list, their exact DP stays quadratic
-//     and is kept for n <= 512.  The group SHAPES are always the true per-dimension maxima.
-// E: element count of the first k items (E[k] = k for the element-level DP, the run boundaries for the run-level one)
-void dc_layer(const int64_t* key, const int64_t* E, const int64_t* prev, int64_t* cur, int32_t* arg, int lo, int hi, int klo,
-              int khi, int64_t INF) {
-    if (lo > hi) return;
-    const int mid = (lo + hi) >> 1;
-    int64_t best = INF;
-    int32_t bk = klo;
-    const int kend = khi < mid - 1 ? khi : mid - 1;
-    for (int k = klo; k <= kend; ++k) {
-        if (prev[k] >= INF) continue;
-        const int64_t c = prev[k] + key[mid - 1] * (E[mid] - E[k]);
-        if (c < best) { best = c; bk = k; }
-    }
-    cur[mid] = best;
-    arg[mid] = bk;
-    dc_layer(key, E, prev, cur, arg, lo, mid - 1, klo, best >= INF ? khi : bk, INF);
-    dc_layer(key, E, prev, cur, arg, mid + 1, hi, best >= INF ? klo : bk, khi, INF);
-}
-
-// monotone DP over m items (elements, or runs of equal keys) into M groups; ps[0..M] = item boundaries
-void dc_split(const int64_t* key, const int64_t* E, int m, int M, std::vector<int32_t>& ps) {
-    const int64_t INF = kSplitInf;
-    std::vector<int32_t> pos((size_t)(m + 1) * (M + 1), 0);
-    std::vector<int64_t> prev(m + 1, INF), cur(m + 1, INF);
-    std::vector<int32_t> arg(m + 1, 0);
-    prev[0] = 0;
-    for (int j = 1; j <= M; ++j) {
-        std::fill(cur.begin(), cur.end(), INF);
-        dc_layer(key, E, prev.data(), cur.data(), arg.data(), 1, m, 0, m - 1, INF);
-        for (int i = 1; i <= m; ++i) pos[(size_t)i * (M + 1) + j] = arg[i];
-        prev.swap(cur);
-    }
-    ps.assign(M + 1, 0);
-    int lp = m;
-    ps[M] = m;
-    for (int j = M; j >= 1; --j) { lp = pos[(size_t)lp * (M + 1) + j]; ps[j - 1] = lp; }
-}
-}  // namespace
-
-namespace hpc_rll { int g_split_algo = 0; }   // hpc_rll_tune_set key 22: 0 = runs of equal keys (default), 1 = the
-                                              // round-2 paths (quadratic element DP / divide-and-conquer over elements)
-
-extern "C" int hpc_rll_oracle_split_group(const int32_t* sizes, int n, int dim, int group, int32_t* group_shapes,
-                                          int32_t* positions) {
-    if (!sizes || n <= 0 || dim <= 0 || dim > 3 || group <= 0 || !group_shapes || !positions) return HPC_RLL_EINVAL;
-    const int M = group < n ? group : n;  // more groups than tensors is meaningless (the reference would walk off)
-    const int64_t INF = kSplitInf;
-    // lists sorted by element count (the documented precondition; hpc_rll/rl_utils/padding.py sorts): DP on the key
-    std::vector<int64_t> key(n);
-    bool sorted = true;
-    for (int i = 0; i < n; ++i) {
-        int64_t e = 1;
-        for (int d = 0; d < dim; ++d) e *= sizes[(size_t)i * dim + d];
-        key[i] = e;
-        if (i && key[i] < key[i - 1]) { sorted = false; break; }
-    }
-    // rank 1: key = the length, the DP cost is the exact padded-element count of padding.cu:44-108 for any n.
-    // rank 2/3: key = numel is the cost model of hpc_rll/origin/padding.py:16-17 (arr[end] * count); padding.cu's
-    // per-dimension maxima are not monotone in a numel-sorted list, their exact DP stays quadratic and is kept for
-    // n <= 512.  The group SHAPES are always the true per-dimension maxima.
-    const bool by_key = sorted && (dim == 1 || n > 512);
-    if (!by_key && n > 20000) return HPC_RLL_EUNSUPPORTED;   // the quadratic DP would take hours: sort the list first
-    std::vector<int32_t> ps;
-    if (by_key && g_split_algo == 0) {
-        // runs of equal keys (pad_group.hpp): O(n) + O(M D log D) for D distinct keys
-        std::vector<int64_t> val, E(1, 0);
-        for (int i = 0; i < n; ++i) {
-            if (val.empty() || key[i] != val.back()) { val.push_back(key[i]); E.push_back(E.back()); }
-            ++E.back();
-        }
-        const int D = (int)val.size();
-        std::vector<int64_t> pe(M + 1, 0);
-        if (D < M) {
-            std::vector<int32_t> gm(M);
-            split_runs_few(val.data(), E.data(), D, (int64_t)n, M, pe.data(), gm.data());
-        } else {
-            std::vector<int32_t> pr;
-            dc_split(val.data(), E.data(), D, M, pr);
-            for (int g = 0; g <= M; ++g) pe[g] = E[pr[g]];
-        }
-        ps.assign(pe.begin(), pe.end());
-    } else if (by_key && (dim > 1 || n > 512)) {
-        std::vector<int64_t> E(n + 1);
-        for (int i = 0; i <= n; ++i) E[i] = i;
-        dc_split(key.data(), E.data(), n, M, ps);
-    } else {
-        std::vector<int32_t> pos((size_t)(n + 1) * (M + 1), 0);
-        auto P = [&](int i, int j) -> int32_t& { return pos[(size_t)i * (M + 1) + j]; };
-        std::vector<int64_t> cost((size_t)(n + 1) * (M + 1), INF);
-        auto C = [&](int i, int j) -> int64_t& { return cost[(size_t)i * (M + 1) + j]; };
-        C(0, 0) = 0;
-        std::vector<int64_t> elems(n);  // elems[k] = prod_d max_{k<=t<=i-1} sizes[t][d]
-        for (int i = 1; i <= n; ++i) {
-            int32_t mx[3] = {0, 0, 0};
-            for (int k = i - 1; k >= 0; --k) {
-                int64_t e = 1;
-                for (int d = 0; d < dim; ++d) {
-                    mx[d] = std::max(mx[d], sizes[(size_t)k * dim + d]);
-                    e *= mx[d];
-                }
-                elems[k] = e;
-            }
-            for (int j = 1; j <= M; ++j) {
-                int64_t best = INF;
-                int32_t arg = 0;
-                for (int k = 0; k < i; ++k) {
-                    if (C(k, j - 1) >= INF) continue;
-                    const int64_t c = C(k, j - 1) + elems[k] * (i - k);
-                    if (c < best) { best = c; arg = k; }  // strict: the smallest k wins ties, like the reference
-                }
-                C(i, j) = best;
-                P(i, j) = arg;
-            }
-        }
-        int lp = n, lc = M;
-        ps.push_back(n);
-        while (lp > 0) { lp = P(lp, lc); --lc; ps.push_back(lp); }
-        std::reverse(ps.begin(), ps.end());
-    }
-    const int ng = (int)ps.size() - 1;
-    for (int g = 0; g < ng; ++g) {
-        for (int d = 0; d < dim; ++d) {
-            int32_t m = 0;
-            for (int t = ps[g]; t < ps[g + 1]; ++t) m = std::max(m, sizes[(size_t)t * dim + d]);
-            group_shapes[g * dim + d] = m;
-        }
-    }
-    for (int g = 0; g <= ng; ++g) positions[g] = ps[g];
-    return ng;
-}
-
-extern "C" int hpc_rll_sample_split_group(const int32_t* sizes, int n, int dim, int group, uint64_t seed,
-                                          int32_t* group_shapes, int32_t* positions) {
-    if (!sizes || n <= 0 || dim <= 0 || dim > 3 || group <= 0 || !group_shapes || !positions) return HPC_RLL_EINVAL;
-    auto next_rand = [&seed]() {  // splitmix64
-        uint64_t z = (seed += 0x9E3779B97F4A7C15ull);
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        return z ^ (z >> 31);
-    };
-    std::vector<int> cut;
-    if (n >= 3) {  // the reference draws from [1, n-2] and divides by zero for n = 2 (padding.cu:17)
-        int last = -1;
-        for (int i = 0; i < group - 1; ++i) {
-            int now = last;
-            if (n == 3) now = 1;
-            else while (now == last) now = (int)(next_rand() % (uint64_t)(n - 2)) + 1;
-            cut.push_back(now);
-            last = now;
-        }
-        std::sort(cut.begin(), cut.end());
-    }
-    cut.push_back(n - 1);
-    int ng = 0, last_idx = -1;
-    for (int idx : cut) {
-        if (idx <= last_idx) continue;
-        int32_t shape[3] = {-1, -1, -1};
-        for (int t = last_idx + 1; t <= idx; ++t)
-            for (int d = 0; d < dim; ++d) shape[d] = std::max(shape[d], sizes[(size_t)t * dim + d]);
-        // same padded shape as the previous group: the reference skips the cut WITHOUT moving last_idx (padding.cu:34-35),
-        // so these rows join the NEXT accepted group -- or, after the final cut, the previous one (its end is N).  Mirrored
-        // exactly.  What is not reproduced: a repeated cut position (idx <= last_idx) makes the reference emit an
-        // EMPTY group of shape -1 (its loop over last_idx+1 .. idx is empty), which GroupPad then cannot allocate; dropped.
-        if (ng > 0 && std::memcmp(shape, group_shapes + (ng - 1) * dim, sizeof(int32_t) * dim) == 0) continue;
-        for (int d = 0; d < dim; ++d) group_shapes[ng * dim + d] = shape[d];
-        positions[ng] = last_idx + 1;
-        ++ng;
-        last_idx = idx;
-    }
-    positions[ng] = n;
-    return ng;
-}
-
-// ---- ScatterConnection
-extern "C" int64_t hpc_rll_scatter_workspace_ints(int B, int M, int H, int W) {
-    return (int64_t)B * (2 * (int64_t)H * W + M);
-}
-
-extern "C" int hpc_rll_scatter_connection_forward(const float* x, const int64_t* location, float* out,
-                                                  int32_t* ws, int B, int M, int N, int H, int W, int add,
-                                                  void* stream) {
-    if (B < 0 || M < 0 || N < 0 || H < 0 || W < 0) return HPC_RLL_EINVAL;
-    const long HW = (long)H * W;
-    if ((size_t)B * N * HW == 0) return HPC_RLL_OK;
-    if (!out || !ws || (M > 0 && (!x || !location))) return HPC_RLL_EINVAL;
-    if (HW >= (1L << 31) || B > 65535) return HPC_RLL_EUNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    int rc = HPC_RLL_OK;
-    bool indexed = false;
-    int parts = 0;               // of the index launch of this call (0 = none), for the record
-    auto build_index = [&]() {   // the paths that read the index from memory
-        if (indexed) return;
-        parts = add ? (M > 256 ? 3 : 1) : 2;
-        hipLaunchKernelGGL(scatter_index_kernel, dim3(B), dim3(256), 0, st, location, ws, M, H, W, parts);
-        rc = last_error();
-        indexed = true;
-    };
-    auto flags = [&](bool built, bool vec) { return (add ? 1 : 0) | (built ? 2 : 0) | (parts << 2) | (vec ? 16 : 0); };
-    const bool v4 = (HW % 4) == 0 && (N % 4) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
-                    (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-    // LDS-staged streaming kernel: the owner table (HW ints) and an M x NPB tile of x must fit in LDS with room for
-    // three workgroups per CU (so that one workgroup's staging overlaps the others' stores).  In-process A/B
-    // (tests/tools/r02_scatter_probe.py, profiles/r02_scatter_probe.json): configs[4] cover 0.953 -> 0.919 ms (4.81 ->
-    // 4.99 TB/s), reference test shape (16x16 maps) cover 51 -> 46 us, add 68 -> 53 us; `add` on large maps is a tie at
-    // 64 channels per workgroup (0.893 ms, 5.13 TB/s) and a loss at 32, so it keeps the cells-per-thread kernel there.
-    // in-kernel index build (round 4, key 37): cover for every M (an LDS atomic per entity); add where the LDS kernel is taken
-    // anyway (maps up to 8 KB) and the quadratic chain search is small against the workgroup's output
-    // (add: measured -13 % at 32 x 32 maps with 128 entities, +15 % at the reference's 16 x 16 test shape with 256, where four
-    // workgroups per batch element each repeat a build that outweighs their 64 KB of output)
-    const bool build = g_scatter_build && W > 0 && (!add || (M <= 256 && HW >= 1024));
-    // (`add` on large maps, rounds 4-5 before the prefetch: the LDS kernel + build at 32 / 64 channels per workgroup lost to the
-    // cells-per-thread kernel behind the index launch, 0.837 / 0.89 against 0.828 ms -- DESIGN.md 4.5)
-    // (round 5, with the staging prefetch: at C5 the LDS kernel + build at 32 channels per workgroup runs `add` in 0.811 ms against
-    // 0.823 for the cells-per-thread kernel behind its index launch -- and has no second launch: taken wherever the tables are built
-    // in the kernel)
-    const bool lds_pays = !add || HW * 4 <= 8 * 1024 || g_scatter_npb != 0 || build;
-    if (g_scatter_lds_fwd && lds_pays && (HW % 4) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && M > 0 && B <= 65535 &&
-        (size_t)HW * 4 <= 32 * 1024) {
-        const size_t fixed = (size_t)HW * 4 + (add ? (size_t)M * 4 : 0) +
-                             (add && build ? (size_t)((M + 3) & ~3) * 4 + 16 + ((size_t)2 * kScatterCollRows + 2) * 4 : 0);   // + cell list, collision list
-        const size_t rows = (size_t)M + (add && build ? kScatterCollRows : 0);   // x tile rows (+ the rows of the cells with several entities)
-        const bool big = g_scatter_npb != 0;
-        const size_t cap = (size_t)(big ? 100 : add && build ? 60 : 52) * 1024;   // two workgroups per CU
-        int npb = 0;
-        static const int kNpb[5] = {64, 32, 16, 8, 4};
-        for (int i = 0; i < 5 && !npb; ++i) {
-            const int c = g_scatter_npb ? g_scatter_npb : kNpb[i];
-            if (c <= 64 && c >= 1 && rows * (c + 1) * 4 + 16 + fixed <= cap) npb = c;
-            if (g_scatter_npb) break;
-        }
-        if (npb > N) npb = (N + 3) / 4 * 4;
-        if (npb >= 1 && rows * (npb + 1) * 4 + 16 + fixed <= cap) {
-            const size_t lds = ((rows * (npb + 1) + 3) & ~(size_t)3) * 4 + fixed;
-            const void* k = add ? (build ? (const void*)scatter_out_lds_kernel<true, true> : (const void*)scatter_out_lds_kernel<true, false>)
-                                : (build ? (const void*)scatter_out_lds_kernel<false, true> : (const void*)scatter_out_lds_kernel<false, false>);
-            if (lds > 64 * 1024 && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return last_error();
-            if (!build) {
-                build_index();
-                if (rc) return rc;
-            }
-            const dim3 grid((N + npb - 1) / npb, B);
-            // staging prefetch distance (see the kernel): half of the workgroups the chip holds -- two 1024-thread workgroups per
-            // CU, fewer when LDS limits -- rounded to a multiple of 8
-            static const int pf_env = getenv("HPC_RLL_SCATTER_PF") ? atoi(getenv("HPC_RLL_SCATTER_PF")) : -1;
-            const int per_cu = lds * 2 <= 160 * 1024 ? 2 : 1;
-            // CU count of the device the launch goes to (was the literal 256), read once per device
-            static int cu_cache[16] = {0};
-            int devid = 0;
-            (void)hipGetDevice(&devid);
-            int cus = devid >= 0 && devid < 16 ? cu_cache[devid] : 0;
-            if (cus <= 0) {
-                if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, devid) != hipSuccess || cus <= 0) cus = 256;
-                if (devid >= 0 && devid < 16) cu_cache[devid] = cus;
-            }
-            const int pf_wgs = pf_env >= 0 ? pf_env : (cus * per_cu / 2) & ~7;
-            if (add && build) hipLaunchKernelGGL((scatter_out_lds_kernel<true, true>), grid, dim3(1024), lds, st, x, ws, out, M, N, (int)HW, npb, location, W, pf_wgs);
-            else if (add) hipLaunchKernelGGL((scatter_out_lds_kernel<true, false>), grid, dim3(1024), lds, st, x, ws, out, M, N, (int)HW, npb, location, W, pf_wgs);
-            else if (build) hipLaunchKernelGGL((scatter_out_lds_kernel<false, true>), grid, dim3(1024), lds, st, x, ws, out, M, N, (int)HW, npb, location, W, pf_wgs);
-            else hipLaunchKernelGGL((scatter_out_lds_kernel<false, false>), grid, dim3(1024), lds, st, x, ws, out, M, N, (int)HW, npb, location, W, pf_wgs);
-            // vec: every workgroup stages its x tile with 16-byte loads (stage_x: nn, N and n0 multiples of 4, x aligned)
-            const bool xvec = (N % 4) == 0 && (npb % 4) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-            return padsc_note(last_error(), HPC_RLL_PADSC_OP_SCATTER_FWD, HPC_RLL_PADSC_KERNEL_SCATTER_OUT_LDS, grid, 1024, lds, npb,
-                              flags(build, xvec));
-        }
-    }
-    const int tpb = (v4 && HW >= 4096) ? g_scatter_threads : 256;   // threads per block of the 4-wide kernel
-    const int cell_blocks = (int)((HW + (v4 ? 4 * tpb - 1 : 255)) / (v4 ? 4 * tpb : 256));
-    // enough workgroups to cover the chip: split the channel axis when B * cell_blocks is small
-    int n_per_block = N;
-    while (n_per_block > 4 && (long)B * cell_blocks * ((N + n_per_block - 1) / n_per_block) < 2048) n_per_block = (n_per_block / 2 + 3) / 4 * 4;
-    const dim3 grid(cell_blocks, (N + n_per_block - 1) / n_per_block, B);
-    if (v4) {
-        build_index();
-        if (rc) return rc;
-        if (add) hipLaunchKernelGGL(scatter_out4_kernel<true>, grid, dim3(tpb), 0, st, x, ws, out, M, N, (int)HW, n_per_block);
-        else hipLaunchKernelGGL(scatter_out4_kernel<false>, grid, dim3(tpb), 0, st, x, ws, out, M, N, (int)HW, n_per_block);
-        return padsc_note(last_error(), HPC_RLL_PADSC_OP_SCATTER_FWD, HPC_RLL_PADSC_KERNEL_SCATTER_OUT4, grid, tpb, 0, n_per_block,
-                          flags(false, true));
-    }
-    build_index();
-    if (rc) return rc;
-    const bool vec = (N % 4) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-    if (add) hipLaunchKernelGGL(scatter_out_kernel<true>, grid, dim3(256), 0, st, x, ws, out, M, N, (int)HW, n_per_block, vec);
-    else hipLaunchKernelGGL(scatter_out_kernel<false>, grid, dim3(256), 0, st, x, ws, out, M, N, (int)HW, n_per_block, vec);
-    return padsc_note(last_error(), HPC_RLL_PADSC_OP_SCATTER_FWD, HPC_RLL_PADSC_KERNEL_SCATTER_OUT, grid, 256, 0, n_per_block,
-                      flags(false, vec));
-}
-
 // Round 6: backward by SPATIAL tiles.  Workgroup = (batch element, TR map rows): it stages rows y0 .. y0+TR-1 of ALL N planes (N
 // contiguous pieces of TR*W floats, 1 KB each at C5) and owns every entity whose location falls into those rows -- it writes
 // their whole N-float rows of grad_x (256 contiguous bytes at C5: full lines, one writer per line) instead of a 16-byte
@@ -1566,21 +1075,13 @@ __global__ __launch_bounds__(1024) void scatter_bwd_tile_kernel(const float* __r
                                                                 int TR, int swz, int xcd_order) {
     extern __shared__ __attribute__((aligned(16))) float s_tile[];   // [N][cells], then the entity list (int32 x 2 per entry) and its counter
     unsigned bi = blockIdx.y, ti = blockIdx.x;
-    if (xcd_order == 2) {   // the tiles of a batch element on one XCD, neighbouring batch elements on the eight XCDs
-        const unsigned nx = gridDim.x, id = blockIdx.x + nx * blockIdx.y, slot = id >> 3;
-        bi = (slot / nx) * 8 + (id & 7u);
-        ti = slot % nx;
-    } else if (xcd_order) {   // the tiles of a batch element on one XCD (they read neighbouring 1 KB pieces of the same planes)
-        const unsigned nx = gridDim.x, total = nx * gridDim.y, id = blockIdx.x + nx * blockIdx.y;
-        const unsigned L = (id & 7u) * (total >> 3) + (id >> 3);
-        bi = L / nx;
-        ti = L - bi * nx;
-    }
+    xcd_remap(xcd_order, bi, ti);   // the tiles of a batch element on one XCD (they read neighbouring 1 KB pieces of the same planes)
     const int b = (int)bi, y0 = (int)ti * TR;
     const int rows = min(TR, H - y0), cells = TR * W, live = rows * W;
     const int HW = H * W;
-    int* const s_cnt = reinterpret_cast<int*>(s_tile + (size_t)N * cells);
-    int* const s_list = s_cnt + 4;                       // [M][2]: entity, cell inside the tile (-1: write zeros)
+    const ScatterBwdTileCarve carve(M, N, cells);        // padsc_plan.hpp
+    int* const s_cnt = reinterpret_cast<int*>(s_tile) + carve.cnt;
+    int* const s_list = reinterpret_cast<int*>(s_tile) + carve.list;   // [M][2]: entity, cell inside the tile (-1: write zeros)
     if (threadIdx.x == 0) *s_cnt = 0;
     const int64_t* __restrict__ loc = location + (size_t)b * M * 2;
     // locations first (raw), planes next: nothing waits before every request is out
@@ -1624,74 +1125,258 @@ __global__ __launch_bounds__(1024) void scatter_bwd_tile_kernel(const float* __r
     }
 }
 
+// (Round 4 also tried this backward as a PERSISTENT software-pipelined kernel -- eight loader waves keeping four planes in
+// flight by LDS-DMA, four gathering waves, the gathered block written once: 1.25 ms against 0.865 at C5; removed in round 5.)
+
+// fallback for planes too large for LDS: direct gather
+__global__ __launch_bounds__(256) void scatter_bwd_direct_kernel(const float* __restrict__ grad_out,
+                                                                 const int64_t* __restrict__ location,
+                                                                 float* __restrict__ grad_x, long total, int M,
+                                                                 int N, int H, int W) {
+    const long HW = (long)H * W;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int n = (int)(i % N);
+        const long bm = i / N;
+        const long b = bm / M;
+        const long y = location[2 * bm], xx = location[2 * bm + 1];
+        const bool ok = y >= 0 && y < H && xx >= 0 && xx < W;
+        grad_x[i] = ok ? grad_out[(b * N + n) * HW + y * W + xx] : 0.f;
+    }
+}
+
+}  // namespace
+}  // namespace hpc_rll
+
+// ================================================================================================ host
+// Every entry point: the argument checks, the plan (padsc_plan.hpp: which kernel, grid, LDS bytes, from the sizes, the addresses,
+// the tune keys and the CU count), the launcher of that kernel family, and the dispatch record noted from the plan.
+namespace hpc_rll {
+// path switches that tests flip (hpc_rll_tune_set, tune.hip)
+int g_pad_wave = 1;          // key 28: packed Pad1D on wave tiles in output space (0 = the round-3 workgroup kernel)
+int g_scatter_lds_fwd = 1;   // key 17: 1 = LDS-staged streaming forward kernel where it applies, 0 = cells-per-thread kernel everywhere
+int g_scatter_npb = 0;       // key 18: channels per workgroup of the LDS-staged kernel (0 = by LDS budget)
+int g_scatter_build = 1;     // key 37: 1 = owner table / chain links built inside the forward kernel, 0 = index launch
+int g_scatter_bwd_xcd = 1;   // key 38: 1 = XCD-major workgroup order of the backward where its pieces are below a sector pair, 0 = launch order
+int g_scatter_bwd_tile = 0;  // key 40: scatter backward by spatial tiles: 0 = by rule, 1 = never, 2 = wherever it applies
+
+namespace {
+PadscKeys tune_keys() { return {g_pad_wave, g_scatter_lds_fwd, g_scatter_npb, g_scatter_build, g_scatter_bwd_xcd, g_scatter_bwd_tile}; }
+uintptr_t addr(const void* p) { return reinterpret_cast<uintptr_t>(p); }
+dim3 grid_of(const PadscLaunch& p) { return dim3(p.gx, p.gy, p.gz); }
+
+// The dispatch records (hpc_rll_pad_scatter_last_config): one per op, noted after the launch that the plan describes went out
+// without an error -- a refused or failed call notes nothing.
+LaunchRecord<HPC_RLL_PAD_SCATTER_CONFIG_INTS> g_padsc_last[HPC_RLL_PADSC_OPS];
+int padsc_note(int rc, int op, const PadscLaunch& p) {
+    if (!rc) g_padsc_last[op].note({p.kernel, (int)p.gx, (int)(p.gy * p.gz), p.threads, (int)p.lds, p.a, p.b});
+    return rc;
+}
+
+// dynamic LDS above the 64 KB a kernel may use without asking
+int allow_lds(const void* kernel, uint64_t lds) {
+    if (lds > 64 * 1024 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return last_error();
+    return HPC_RLL_OK;
+}
+
+int launch_pad(const PadscLaunch& p, const int64_t* table, float* new_x, int32_t* mask, int64_t n, int m0, int m1, int m2, int value,
+               hipStream_t st) {
+    if (p.kernel == HPC_RLL_PADSC_KERNEL_PAD1D4)
+        hipLaunchKernelGGL(pad1d4_kernel, grid_of(p), dim3(p.threads), 0, st, table, new_x, mask, (long)n, (unsigned)m2, 1.0 / (double)m2,
+                           (float)value, value);
+    else
+        hipLaunchKernelGGL(p.v4 ? pad4_kernel : pad_kernel, grid_of(p), dim3(p.threads), 0, st, table, new_x, mask, (long)n, (unsigned)m0,
+                           (unsigned)m1, (unsigned)m2, (float)value, value);
+    return last_error();
+}
+
+int launch_unpad(const PadscLaunch& p, const float* padded, const int64_t* table, float* flat, int64_t n, int64_t total, int m0, int m1,
+                 int m2, hipStream_t st) {
+    if (p.kernel == HPC_RLL_PADSC_KERNEL_UNPAD1D4)
+        hipLaunchKernelGGL(unpad1d4_kernel, grid_of(p), dim3(p.threads), 0, st, padded, table, flat, (long)n, (long)total, (unsigned)m2,
+                           1.0 / (double)m2);
+    else
+        hipLaunchKernelGGL(unpad_kernel, grid_of(p), dim3(p.threads), 0, st, padded, table, flat, (long)n, (long)total, (unsigned)m0,
+                           (unsigned)m1, (unsigned)m2);
+    return last_error();
+}
+
+int launch_pad_packed(const PadscLaunch& p, const float* flat, const int64_t* table, float* new_x, int32_t* mask, int64_t n, int max_len,
+                      int value, hipStream_t st) {
+    if (p.kernel == HPC_RLL_PADSC_KERNEL_PAD1D_PACKED_WAVE)
+        hipLaunchKernelGGL(pad1d_packed_wave_kernel, grid_of(p), dim3(p.threads), 0, st, flat, table, new_x, mask, (long)n,
+                           (unsigned)max_len, 1.0f / (float)max_len, (float)value, value);
+    else
+        hipLaunchKernelGGL(pad1d_packed_kernel, grid_of(p), dim3(p.threads), p.lds, st, flat, table, new_x, mask, (long)n,
+                           (unsigned)max_len, 1.0 / (double)max_len, p.RB, (float)value, value);
+    return last_error();
+}
+
+int launch_unpad_packed(const PadscLaunch& p, const float* padded, const int64_t* table, float* flat, int64_t n, int64_t total,
+                        int max_len, hipStream_t st) {
+    hipLaunchKernelGGL(unpad1d_packed_kernel, grid_of(p), dim3(p.threads), p.lds, st, padded, table, flat, (long)n, (long)total,
+                       (unsigned)max_len, 1.0 / (double)max_len, p.RB);
+    return last_error();
+}
+
+// the instantiations of the forward kernels, by [add] and [build]: one pointer serves hipFuncSetAttribute and the launch
+using ScatterLdsFn = void (*)(const float*, const int32_t*, float*, int, int, int, int, const int64_t*, int, int);
+using ScatterOut4Fn = void (*)(const float*, const int32_t*, float*, int, int, int, int);
+using ScatterOutFn = void (*)(const float*, const int32_t*, float*, int, int, int, int, bool);
+const ScatterLdsFn kScatterLds[2][2] = {{scatter_out_lds_kernel<false, false>, scatter_out_lds_kernel<false, true>},
+                                        {scatter_out_lds_kernel<true, false>, scatter_out_lds_kernel<true, true>}};
+const ScatterOut4Fn kScatterOut4[2] = {scatter_out4_kernel<false>, scatter_out4_kernel<true>};
+const ScatterOutFn kScatterOut[2] = {scatter_out_kernel<false>, scatter_out_kernel<true>};
+
+// the owner table / chain links in memory (ws), for the kernels that read them from there
+int build_index(const int64_t* location, int32_t* ws, int B, int M, int H, int W, int parts, hipStream_t st) {
+    hipLaunchKernelGGL(scatter_index_kernel, dim3(B), dim3(256), 0, st, location, ws, M, H, W, parts);
+    return last_error();
+}
+
+// attribute (LDS above 64 KB), index launch (where the plan has one), kernel: the first failure returns, nothing is issued after it
+int launch_scatter_fwd(const PadscLaunch& p, const float* x, const int64_t* location, float* out, int32_t* ws, int B, int M, int N, int H,
+                       int W, hipStream_t st) {
+    const int HW = H * W;
+    if (p.kernel == HPC_RLL_PADSC_KERNEL_SCATTER_OUT_LDS) {
+        const ScatterLdsFn k = kScatterLds[p.add][p.build];
+        if (const int rc = allow_lds((const void*)k, p.lds)) return rc;
+        if (p.index_parts)
+            if (const int rc = build_index(location, ws, B, M, H, W, p.index_parts, st)) return rc;
+        static const int pf_env = getenv("HPC_RLL_SCATTER_PF") ? atoi(getenv("HPC_RLL_SCATTER_PF")) : -1;
+        hipLaunchKernelGGL(k, grid_of(p), dim3(p.threads), p.lds, st, x, ws, out, M, N, HW, p.npb, location, W, pf_env >= 0 ? pf_env : p.pf_wgs);
+        return last_error();
+    }
+    if (const int rc = build_index(location, ws, B, M, H, W, p.index_parts, st)) return rc;
+    if (p.kernel == HPC_RLL_PADSC_KERNEL_SCATTER_OUT4)
+        hipLaunchKernelGGL(kScatterOut4[p.add], grid_of(p), dim3(p.threads), 0, st, x, ws, out, M, N, HW, p.npb);
+    else
+        hipLaunchKernelGGL(kScatterOut[p.add], grid_of(p), dim3(p.threads), 0, st, x, ws, out, M, N, HW, p.npb, (bool)p.vec);
+    return last_error();
+}
+
+int launch_scatter_bwd(const PadscLaunch& p, const float* grad_out, const int64_t* location, float* grad_x, int B, int M, int N, int H,
+                       int W, hipStream_t st) {
+    switch (p.kernel) {
+    case HPC_RLL_PADSC_KERNEL_SCATTER_BWD_MEMSET:   // an empty map: every location is out of range, every gradient row is zero
+        return (int)hipMemsetAsync(grad_x, 0, sizeof(float) * (size_t)B * M * N, st);
+    case HPC_RLL_PADSC_KERNEL_SCATTER_BWD_TILE:
+        if (const int rc = allow_lds((const void*)scatter_bwd_tile_kernel, p.lds)) return rc;
+        hipLaunchKernelGGL(scatter_bwd_tile_kernel, grid_of(p), dim3(p.threads), p.lds, st, grad_out, location, grad_x, M, N, H, W, p.TR,
+                           p.swz, p.xcd);
+        return last_error();
+    case HPC_RLL_PADSC_KERNEL_SCATTER_BWD_LDS:
+        if (const int rc = allow_lds((const void*)scatter_bwd_lds_kernel, p.lds)) return rc;
+        hipLaunchKernelGGL(scatter_bwd_lds_kernel, grid_of(p), dim3(p.threads), p.lds, st, grad_out, location, grad_x, M, N, H, W, p.NG,
+                           p.xcd);
+        return last_error();
+    default:
+        hipLaunchKernelGGL(scatter_bwd_direct_kernel, grid_of(p), dim3(p.threads), 0, st, grad_out, location, grad_x, (long)B * M * N, M,
+                           N, H, W);
+        return last_error();
+    }
+}
+}  // namespace
+}  // namespace hpc_rll
+using namespace hpc_rll;
+
+extern "C" int hpc_rll_pad_forward(const int64_t* table, float* new_x, int32_t* mask, int64_t n, int m0, int m1,
+                                   int m2, int value, void* stream) {
+    if (n < 0 || m0 < 0 || m1 < 0 || m2 < 0) return HPC_RLL_EINVAL;
+    const long inner = (long)m0 * m1 * m2;
+    if (inner >= (1L << 31)) return HPC_RLL_EUNSUPPORTED;
+    if (n * inner == 0) return HPC_RLL_OK;
+    if (!table || !new_x || !mask) return HPC_RLL_EINVAL;
+    const PadscLaunch p = plan_pad(n, m0, m1, m2, addr(new_x), addr(mask));
+    return padsc_note(launch_pad(p, table, new_x, mask, n, m0, m1, m2, value, (hipStream_t)stream), HPC_RLL_PADSC_OP_PAD, p);
+}
+
+extern "C" int hpc_rll_unpad_forward(const float* padded, const int64_t* table, float* flat, int64_t n,
+                                     int64_t total, int m0, int m1, int m2, void* stream) {
+    if (n < 0 || total < 0 || m0 < 0 || m1 < 0 || m2 < 0) return HPC_RLL_EINVAL;
+    if (total == 0 || n == 0) return HPC_RLL_OK;
+    if (!padded || !table || !flat) return HPC_RLL_EINVAL;
+    const PadscLaunch p = plan_unpad(n, total, m0, m1, m2, addr(padded));
+    return padsc_note(launch_unpad(p, padded, table, flat, n, total, m0, m1, m2, (hipStream_t)stream), HPC_RLL_PADSC_OP_UNPAD, p);
+}
+
+extern "C" int hpc_rll_pad1d_packed_forward(const float* flat, const int64_t* table, float* new_x, int32_t* mask, int64_t n,
+                                            int max_len, int value, void* stream) {
+    if (n < 0 || max_len < 0) return HPC_RLL_EINVAL;
+    if (n == 0 || max_len == 0) return HPC_RLL_OK;
+    if (!flat || !table || !new_x || !mask) return HPC_RLL_EINVAL;
+    const PadscPacked p = plan_pad_packed(n, max_len, addr(flat), addr(new_x), addr(mask), tune_keys());
+    hipStream_t st = (hipStream_t)stream;
+    if (p.own.kernel != HPC_RLL_PADSC_KERNEL_HANDED_OVER)
+        return padsc_note(launch_pad_packed(p.own, flat, table, new_x, mask, n, max_len, value, st), HPC_RLL_PADSC_OP_PAD_PACKED, p.own);
+    // handed over: the list op's launch and record first, this op's record only behind a launch that went out
+    const int rc = padsc_note(launch_pad(p.list, table, new_x, mask, n, 1, 1, max_len, value, st), HPC_RLL_PADSC_OP_PAD, p.list);
+    return padsc_note(rc, HPC_RLL_PADSC_OP_PAD_PACKED, p.own);
+}
+
+extern "C" int hpc_rll_unpad1d_packed_forward(const float* padded, const int64_t* table, float* flat, int64_t n, int64_t total,
+                                              int max_len, void* stream) {
+    if (n < 0 || total < 0 || max_len < 0) return HPC_RLL_EINVAL;
+    if (n == 0 || total == 0 || max_len == 0) return HPC_RLL_OK;
+    if (!padded || !table || !flat) return HPC_RLL_EINVAL;
+    const PadscPacked p = plan_unpad_packed(n, total, max_len, addr(padded), addr(flat));
+    hipStream_t st = (hipStream_t)stream;
+    if (p.own.kernel != HPC_RLL_PADSC_KERNEL_HANDED_OVER)
+        return padsc_note(launch_unpad_packed(p.own, padded, table, flat, n, total, max_len, st), HPC_RLL_PADSC_OP_UNPAD_PACKED, p.own);
+    const int rc = padsc_note(launch_unpad(p.list, padded, table, flat, n, total, 1, 1, max_len, st), HPC_RLL_PADSC_OP_UNPAD, p.list);
+    return padsc_note(rc, HPC_RLL_PADSC_OP_UNPAD_PACKED, p.own);
+}
+
+extern "C" int64_t hpc_rll_packed_table_scratch_int64(int64_t n) {
+    return n <= 0 ? 1 : (n + kScanChunk - 1) / kScanChunk;
+}
+
+extern "C" int hpc_rll_packed_table(const int64_t* lengths, int64_t n, int64_t base, int64_t stride, int64_t* table,
+                                    int64_t* scratch, void* stream) {
+    if (n < 0) return HPC_RLL_EINVAL;
+    if (n == 0) return HPC_RLL_OK;
+    if (!lengths || !table || !scratch) return HPC_RLL_EINVAL;
+    const long nchunks = (long)((n + kScanChunk - 1) / kScanChunk);
+    if (nchunks > 0x7fffffffL) return HPC_RLL_EUNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(packed_chunk_sums_kernel, dim3((unsigned)nchunks), dim3(256), 0, st, lengths, (long)n, scratch);
+    if (nchunks <= 1024) {
+        hipLaunchKernelGGL(packed_table_kernel<true>, dim3((unsigned)nchunks), dim3(256), 0, st, lengths, (long)n, scratch, base,
+                           stride, table);
+        return last_error();
+    }
+    hipLaunchKernelGGL(packed_scan_sums_kernel, dim3(1), dim3(256), 0, st, scratch, nchunks);
+    hipLaunchKernelGGL(packed_table_kernel<false>, dim3((unsigned)nchunks), dim3(256), 0, st, lengths, (long)n, scratch, base,
+                       stride, table);
+    return last_error();
+}
+
+// ---- ScatterConnection
+extern "C" int64_t hpc_rll_scatter_workspace_ints(int B, int M, int H, int W) {
+    return (int64_t)B * (2 * (int64_t)H * W + M);
+}
+
+extern "C" int hpc_rll_scatter_connection_forward(const float* x, const int64_t* location, float* out,
+                                                  int32_t* ws, int B, int M, int N, int H, int W, int add,
+                                                  void* stream) {
+    if (B < 0 || M < 0 || N < 0 || H < 0 || W < 0) return HPC_RLL_EINVAL;
+    const long HW = (long)H * W;
+    if ((size_t)B * N * HW == 0) return HPC_RLL_OK;
+    if (!out || !ws || (M > 0 && (!x || !location))) return HPC_RLL_EINVAL;
+    if (HW >= (1L << 31) || B > 65535) return HPC_RLL_EUNSUPPORTED;
+    int cus = device_cus();   // of the device the launch goes to
+    if (cus <= 0) cus = 256;
+    const PadscLaunch p = plan_scatter_fwd(B, M, N, H, W, add, addr(x), addr(out), tune_keys(), cus);
+    return padsc_note(launch_scatter_fwd(p, x, location, out, ws, B, M, N, H, W, (hipStream_t)stream), HPC_RLL_PADSC_OP_SCATTER_FWD, p);
+}
+
 extern "C" int hpc_rll_scatter_connection_backward(const float* grad_out, const int64_t* location, float* grad_x,
                                                    int B, int M, int N, int H, int W, void* stream) {
     if (B < 0 || M < 0 || N < 0 || H < 0 || W < 0) return HPC_RLL_EINVAL;
     if ((size_t)B * M * N == 0) return HPC_RLL_OK;
     if (!location || !grad_x) return HPC_RLL_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const long HW = (long)H * W;
-    // an empty map: every location is out of range, every gradient row is zero (grad_out has no elements and may be null)
-    if (HW == 0)
-        return padsc_note_no_launch((int)hipMemsetAsync(grad_x, 0, sizeof(float) * (size_t)B * M * N, st), HPC_RLL_PADSC_OP_SCATTER_BWD,
-                                    HPC_RLL_PADSC_KERNEL_SCATTER_BWD_MEMSET, 0, 0);
-    if (!grad_out) return HPC_RLL_EINVAL;
-    const long plane_bytes = HW * 4;
-    // Which kernel (round 6, profiles/r06_scatter_bwd_probe.txt).  The plane kernel writes NG*4-byte pieces of every entity's row
-    // from N/NG workgroups; where those pieces are 16 bytes or less (maps of 4096 cells and more) AND the entity rows are a
-    // sizeable part of the traffic (M*16 >= H*W: C5 exactly), the spatial-tile kernel -- full rows from one writer -- is faster
-    // (M = 1024, N = 128: 1086 -> 946 us; C5: 741 -> 724 us mean of 50 buffer sets on five boxes) and half as sensitive to where
-    // grad_out and grad_x lie relative to each other (C5: +5 % instead of +12 % on an unlucky pair).  Few entities per map
-    // (B = 8192, M = 64: 656 vs 710 us) and small maps (32 x 32: 249 vs 288) keep the plane kernel.  Key 40 forces either.
-    const long pieces = std::min<long>(N, std::max<long>(1, (long)g_scatter_bwd_lds_kb * 1024 / std::max<long>(plane_bytes, 1))) * 4;
-    const bool tile_rule = g_scatter_bwd_tile == 2 || (g_scatter_bwd_tile == 0 && pieces <= 16 && (long)M * 16 >= HW);
-    if (tile_rule && (W % 4) == 0 && M <= 4096 && B <= 65535 && (reinterpret_cast<uintptr_t>(grad_out) & 15) == 0 &&
-        (long)N * W * 4 <= 64 * 1024) {
-        int TR = (int)(64L * 1024 / ((long)N * W * 4));
-        if (TR > H) TR = H;
-        int p2 = 1;
-        while (p2 * 2 <= TR) p2 *= 2;                    // a power of two (the swizzle XORs inside a plane piece)
-        TR = p2;
-        const int cells = TR * W;
-        int swz = 0;
-        if ((cells & (cells - 1)) == 0 && cells >= 8) { swz = cells / 4 - 1; if (swz > 63) swz = 63; }
-        const size_t lds = (size_t)N * cells * 4 + 16 + (size_t)M * 8;
-        // plane pieces of a tile: 1 KB and more where entity rows are a sixteenth of the planes (C5), 512 bytes only where they are a
-        // quarter (N = 128, M = 1024: 1070 -> 945 us; N = 128, M = 256 keeps the plane kernel: 714 vs 747)
-        const bool pays = ((long)cells * 4 >= 1024 && (long)M * 16 >= HW) || ((long)cells * 4 >= 512 && (long)M * 4 >= HW);
-        if (pays || g_scatter_bwd_tile == 2) {
-            const dim3 grid((H + TR - 1) / TR, B);
-            if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)scatter_bwd_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       (int)lds) != hipSuccess)
-                return last_error();
-            hipLaunchKernelGGL(scatter_bwd_tile_kernel, grid, dim3(1024), lds, st, grad_out, location, grad_x, M, N, H, W, TR, swz, 0);
-            return padsc_note(last_error(), HPC_RLL_PADSC_OP_SCATTER_BWD, HPC_RLL_PADSC_KERNEL_SCATTER_BWD_TILE, grid, 1024, lds, TR, 0);
-        }
-    }
-    if (plane_bytes <= 128 * 1024 && B <= 65535) {
-        int NG = (int)std::min<long>(N, std::max<long>(1, (long)g_scatter_bwd_lds_kb * 1024 / plane_bytes));
-        if (NG > 32) NG = 32;
-        const dim3 grid((N + NG - 1) / NG, B);
-        const size_t lds = (size_t)NG * plane_bytes;
-        if (lds > 64 * 1024 &&
-            hipFuncSetAttribute((const void*)scatter_bwd_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-                hipSuccess)
-            return last_error();
-        // measured (profiles/r04_scatter_bwd_xcd.txt): 16-byte pieces (64 x 64 maps, NG = 4) -8 % at C5 and -31 % at M = 1024, N = 128;
-        // 64-byte pieces (32 x 32 maps) +6 %, whole lines (16 x 16) +4 % -- only pieces below a 64-byte sector pair profit
-        const int xcd_order = (g_scatter_bwd_xcd == 2 || (g_scatter_bwd_xcd == 1 && NG * 4 <= 32)) &&
-                              ((long)grid.x * grid.y) % 8 == 0 && grid.x > 1;
-        // (round 6) with B a multiple of 8 the XCDs take NEIGHBOURING batch elements (order 2: -1 % on every shape measured)
-        const int xo2 = (xcd_order && B % 8 == 0) ? 2 : xcd_order;
-        hipLaunchKernelGGL(scatter_bwd_lds_kernel, grid, dim3(1024), lds, st, grad_out, location, grad_x, M, N, H, W, NG, xo2);
-        return padsc_note(last_error(), HPC_RLL_PADSC_OP_SCATTER_BWD, HPC_RLL_PADSC_KERNEL_SCATTER_BWD_LDS, grid, 1024, lds, NG, xo2);
-    }
-    const long total = (long)B * M * N;
-    long blocks = (total + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(scatter_bwd_direct_kernel, dim3((unsigned)blocks), dim3(256), 0, st, grad_out, location,
-                       grad_x, total, M, N, H, W);
-    return padsc_note(last_error(), HPC_RLL_PADSC_OP_SCATTER_BWD, HPC_RLL_PADSC_KERNEL_SCATTER_BWD_DIRECT, dim3((unsigned)blocks), 256, 0, 0, 0);
+    if (!grad_out && (long)H * W != 0) return HPC_RLL_EINVAL;   // (of an empty map grad_out has no elements and may be null)
+    const PadscLaunch p = plan_scatter_bwd(B, M, N, H, W, addr(grad_out), tune_keys());
+    return padsc_note(launch_scatter_bwd(p, grad_out, location, grad_x, B, M, N, H, W, (hipStream_t)stream), HPC_RLL_PADSC_OP_SCATTER_BWD, p);
 }
 
 extern "C" int hpc_rll_pad_scatter_last_config(int op, int* out) {

@@ -13,22 +13,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hostutil.hpp"
 #include "wave.hpp"
 
 namespace hpc_rll {
-
-inline int device_cus() {   // CU count of the current device (cached per device; 0 on error)
-    constexpr int kMax = 64;
-    static int cus[kMax] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMax) return 0;
-    if (cus[dev] == 0) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) v = 0;
-        cus[dev] = v > 0 ? v : -1;
-    }
-    return cus[dev] > 0 ? cus[dev] : 0;
-}
 
 // `shift` = 16-byte elements between the 4 KiB boundary below y and y: the loop runs over indices from that boundary, so that
 // every workgroup's 256 x 16 bytes are ONE 4 KiB-aligned block (the same loop on a base 512 bytes off such a boundary:

@@ -1,7 +1,9 @@
 """TEST-ONLY: the dispatch rules of csrc/pad_scatter.hip restated in Python, for tests/test_pad_scatter_direct_gpu.py and
 tests/test_pad_scatter_cpu.py.  Every function returns the seven ints ``hpc_rll_pad_scatter_last_config`` must show after
 the launch count -- {kernel, grid.x, grid.y * grid.z, threads, dynamic LDS bytes, two ints by op} -- computed from the shapes,
-the ADDRESSES and the tune keys alone, by the rules the comments of the six entry points and include/hpc_rll_hip.h state.
+the ADDRESSES and the tune keys alone, by the rules the planners of csrc/padsc_plan.hpp and include/hpc_rll_hip.h state.  The rules are also checked against the C++
+on the CPU: tests/test_pad_scatter_cpu.py compiles the planners alone (tests/padsc_plan_main.cpp) and compares them with
+these functions over a sweep of shapes, addresses and keys.
 The constants are read from the header, so they cannot drift from it."""
 import ctypes
 import os

@@ -2,7 +2,8 @@
 ``hpc_rll_pad_scatter_last_config`` is declared and exported with its constants, refuses a NULL output and an unknown op, and
 reads {0, -1 ...} for each of the six ops in a fresh process; the six launching entry points answer argument errors and empty
 shapes with statuses before any HIP call and leave every record as it was; the float32 row formula of
-``pad1d_packed_wave_kernel`` is exact on its whole domain; ``packed_rows_per_wg`` restated at the widths where it changes.
+``pad1d_packed_wave_kernel`` is exact on its whole domain; ``packed_rows_per_wg`` restated at the widths where it changes; the
+planners of csrc/padsc_plan.hpp, compiled alone by the host compiler, against tests/padsc.py over a sweep, with every LDS carve.
 Everything that launches is in tests/test_pad_scatter_direct_gpu.py."""
 import ctypes
 import os
@@ -127,6 +128,95 @@ def test_wave_kernel_row_formula_is_exact_on_its_whole_domain():
         assert rr.dtype == np.float32
         bad += int((rr.astype(np.uint32) != t // L).sum())
     assert bad == 0, bad
+
+
+BASE = 1 << 20                                                          # a 16-byte aligned address for the sweep's pointers
+OFFS = (0, 4, 8)
+CUS = (256, 304, 64, 8)
+
+
+def plan_sweep():
+    """-> [(input line of tests/padsc_plan_main.cpp, the record by tests/padsc.py, the list op's record or None)].
+    Scatter: every (B, M, N, map, add) of the sets below; the 108 / 27 combinations of pointer offsets and tune keys are dealt
+    over them in turn, six / four per shape, so that the sweep stays at some 60 000 lines and every combination occurs many
+    times; the CU count takes 256, 304, 64 and 8 in turn.  Pad: the whole cross product."""
+    import itertools as it
+    out = []
+    Bs, Ms, Ns = (1, 3, 4, 8, 65535), (0, 5, 256, 257, 300, 3000, 4096, 4097), (1, 3, 4, 7, 8, 64, 70, 128)
+    maps = ((0, 4), (3, 5), (4, 4), (16, 16), (32, 32), (45, 46), (64, 64), (96, 96), (128, 64), (136, 136), (184, 184))
+    fwd_opts = list(it.product(OFFS, OFFS, (0, 1), (0, 4, 64), (0, 1)))          # x, out, key 17, key 18, key 37
+    bwd_opts = list(it.product(OFFS, (0, 1, 2), (0, 1, 2)))                      # grad_out, key 38, key 40
+    i = j = 0
+    for B, M, N, (H, W) in it.product(Bs, Ms, Ns, maps):
+        for add in (0, 1):
+            for _ in range(6):
+                xo, oo, k17, k18, k37 = fwd_opts[i % len(fwd_opts)]
+                i += 1
+                out.append((f"fwd {B} {M} {N} {H} {W} {add} {BASE + xo} {BASE + oo} {k17} {k18} {k37} {CUS[(i // 7) % len(CUS)]}",
+                            padsc.scatter_fwd_rule(B, M, N, H, W, add, BASE + xo, BASE + oo, k17, k18, k37), None))
+        for _ in range(4):
+            go, k38, k40 = bwd_opts[j % len(bwd_opts)]
+            j += 1
+            out.append((f"bwd {B} {M} {N} {H} {W} {BASE + go} {k38} {k40}", padsc.scatter_bwd_rule(B, M, N, H, W, BASE + go, k38, k40), None))
+    Ls = (1, 5, 31, 32, 33, 950, 951, 7600, 7601, 15200, 15201, 16384, 16385)
+    for n, L in it.product((1, 3, 4, 50, 70000), Ls):
+        for m0, m1 in ((1, 1), (1, 2), (2, 3)):
+            total = max(1, n * m0 * m1 * L // 2)                                 # flat elements of the unpad
+            for a, b in it.product(OFFS, OFFS):
+                out.append((f"pad {n} {m0} {m1} {L} {BASE + a} {BASE + b}", padsc.pad_rule(n, m0, m1, L, BASE + a, BASE + b), None))
+            for a in OFFS:
+                out.append((f"unpad {n} {total} {m0} {m1} {L} {BASE + a}", padsc.unpad_rule(n, total, m0, m1, L, BASE + a), None))
+        total = max(1, n * L // 2)
+        for f, a, b, k28 in it.product(OFFS, OFFS, OFFS, (0, 1)):
+            out.append((f"ppad {n} {L} {BASE + f} {BASE + a} {BASE + b} {k28}",) + padsc.pad_packed_rule(n, L, BASE + a, BASE + b, k28))
+        for a, f in it.product(OFFS, OFFS):
+            out.append((f"punpad {n} {total} {L} {BASE + a} {BASE + f}",) + padsc.unpad_packed_rule(n, total, L, BASE + a))
+    return out
+
+
+def build_plan_program(tmp_path):
+    """tests/padsc_plan_main.cpp by the host compiler: c++, else the clang++ the library itself was built with."""
+    import shutil
+    here = os.path.dirname(os.path.abspath(__file__))
+    root = os.path.dirname(here)
+    cxx = shutil.which("c++") or "/opt/rocm/llvm/bin/clang++"
+    exe = os.path.join(str(tmp_path), "padsc_plan")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(root, "include"), "-I" + os.path.join(root, "di-hpc_amd", "csrc"),
+                    os.path.join(here, "padsc_plan_main.cpp"), "-o", exe], check=True, timeout=300)
+    return exe
+
+
+def test_the_planners_agree_with_the_restated_rules_and_every_carve_fits(tmp_path):
+    """csrc/padsc_plan.hpp, compiled without HIP, against tests/padsc.py on the sweep above: every record, both records of a
+    hand-over, for every plan with dynamic LDS the end of the kernel's carve within the bytes the plan requests, and the
+    staging prefetch distance of the forward's LDS kernel: half of the workgroups the chip holds (two per CU, one where a
+    workgroup's LDS is above 80 KB), rounded down to a multiple of 8."""
+    sweep = plan_sweep()
+    exe = build_plan_program(tmp_path)
+    r = subprocess.run([exe], input="".join(s[0] + "\n" for s in sweep), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    got = r.stdout.splitlines()
+    assert len(got) == len(sweep)
+    print(f"{len(sweep)} sweep lines")
+    kernels, with_lds = set(), 0
+    for (line, own, handed), g in zip(sweep, got):
+        t = g.split()
+        assert [int(v) for v in t[:7]] == own, (line, g, own)
+        kernels.add(own[0])
+        rest = t[7:]
+        if handed is not None:
+            assert rest[0] == "H" and [int(v) for v in rest[1:8]] == handed, (line, g, handed)
+            rest = rest[8:]
+        if own[4]:
+            assert rest[0] == "E" and 0 < int(rest[1]) <= own[4], (line, g)
+            with_lds += 1
+            rest = rest[2:]
+        if own[0] == padsc.K["SCATTER_OUT_LDS"]:
+            cus = int(line.split()[-1])
+            assert rest[0] == "P" and int(rest[1]) == (cus * (2 if own[4] * 2 <= 160 * 1024 else 1) // 2) & ~7, (line, g)
+            rest = rest[2:]
+        assert not rest, (line, g)
+    assert kernels == set(range(padsc.KERNELS)) and with_lds > 1000
 
 
 def test_rows_per_workgroup_of_the_packed_kernels():

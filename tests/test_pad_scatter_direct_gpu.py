@@ -473,6 +473,20 @@ def test_scatter_forward_lds_stream_loops(dev, N, npb):
     assert with_key[5] == 4 and with_key[1] == 4
 
 
+def test_scatter_forward_lds_kernel_above_64_kb_of_lds(dev):
+    """Key 18 = 64 channels per workgroup: every <ADD, BUILD> instantiation with more dynamic LDS than a kernel may use without
+    hipFuncSetAttribute (which the launcher then calls on the pointer it launches).  With 3000 entities 64 channels of the x
+    tile do not fit 100 KB, and a forced width tries no other: the quad kernel."""
+    for shape, add, k37, build, parts, lds, flags in (((1, 300, 64, 4, 4), 0, 1, 1, 0, 78064, 18), ((1, 300, 64, 4, 4), 0, 0, 0, 2, None, None),
+                                                      ((1, 300, 64, 4, 4), 1, 1, 0, 3, 79264, 29), ((1, 200, 64, 32, 32), 1, 1, 1, 0, 66296, 19)):
+        rec = run_fwd(dev, *shape, add, k18=64, k37=k37)
+        f = flags_of(rec)
+        assert rec[0] == K["SCATTER_OUT_LDS"] and rec[4] > 65536 and rec[5] == 64, rec
+        assert (f["add"], f["build"], f["parts"], f["vec"]) == (add, build, parts, 1), rec
+        assert lds is None or (rec[4], rec[6]) == (lds, flags), rec
+    assert run_fwd(dev, 1, 3000, 64, 4, 4, 0, k18=64)[0] == K["SCATTER_OUT4"]
+
+
 def test_scatter_forward_add_build_collisions_on_both_sides_of_the_limit(dev):
     """add with in-kernel tables gives up to 32 colliding cells per batch element a row of their own in the x tile and walks the
     chains in the stream loop beyond that.  Batch element 0: 128 cells of two entities each (the walk); batch element 1: three
@@ -593,6 +607,13 @@ def test_scatter_backward_plane_kernel_in_every_xcd_order(dev, shape, k38, order
     for gx_off in range(4):
         rec = run_bwd(dev, *shape, gx_off=gx_off, k38=k38)
         assert rec[0] == K["SCATTER_BWD_LDS"] and rec[6] == order, rec
+
+
+def test_scatter_backward_plane_kernel_with_one_plane_above_64_kb(dev):
+    """136 x 136 maps: one plane is 73984 bytes, more dynamic LDS than a kernel may use without hipFuncSetAttribute; one plane per
+    workgroup, launch order; grad_x at every offset."""
+    for gx_off in range(4):
+        assert run_bwd(dev, 1, 9, 3, 136, 136, gx_off=gx_off) == [K["SCATTER_BWD_LDS"], 3, 1, 1024, 73984, 1, 0]
 
 
 def test_scatter_backward_misaligned_grad_out_keeps_the_plane_kernel(dev):
