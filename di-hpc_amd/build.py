@@ -6,8 +6,8 @@
 1. libhpc_rll_hip.so -- the C-ABI HIP library: one translation unit per op under csrc/*.hip, compiled with
    hipcc --offload-arch=gfx950 and linked into di-hpc_amd/hpc_rll/_lib/.  hipcc cross-compiles without a GPU.
 2. hpc_rl_utils.so, hpc_torch_utils_network.so, hpc_models.so -- the PyTorch-ROCm extension modules (the reference's
-   three pybind modules, setup.py:19-49), hpc_marl.so, hpc_twohot.so and hpc_replay.so, the multi-agent ops, the categorical value
-   losses and the prioritized-replay index the reference lacks: HOST-ONLY C++ under ext/*.cpp compiled with g++ against torch's headers and
+   three pybind modules, setup.py:19-49), hpc_marl.so, hpc_twohot.so, hpc_replay.so and hpc_sac.so, the multi-agent ops, the categorical value
+   losses, the prioritized-replay index and continuous SAC, which the reference lacks: HOST-ONLY C++ under ext/*.cpp compiled with g++ against torch's headers and
    linked to libtorch + libhpc_rll_hip.so (rpath $ORIGIN/hpc_rll/_lib).  No device code, no hipify.
 The object files and the .so files are git-ignored but travel to the GPU box with the tree.
 """
@@ -39,6 +39,7 @@ EXT_MODULES = {
     "hpc_marl": ["marl.cpp"],
     "hpc_twohot": ["twohot.cpp"],
     "hpc_replay": ["replay.cpp"],
+    "hpc_sac": ["sac_continuous.cpp"],
 }
 
 

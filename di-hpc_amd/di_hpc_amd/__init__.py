@@ -2,8 +2,8 @@
 
 The drop-in API lives under the reference's own module names, which is the point of a drop-in:
 ``hpc_rll.rl_utils.*``, ``hpc_rll.torch_utils.network.*`` (Python) and the compiled extension modules ``hpc_rl_utils``,
-``hpc_torch_utils_network``, ``hpc_models``, and ``hpc_marl``, ``hpc_twohot`` and ``hpc_replay`` (the multi-agent ops, the categorical value losses and the
-prioritized-replay index, which the reference lacks).  This module
+``hpc_torch_utils_network``, ``hpc_models``, and ``hpc_marl``, ``hpc_twohot``, ``hpc_replay`` and ``hpc_sac`` (the multi-agent ops, the categorical value losses, the
+prioritized-replay index and continuous SAC, which the reference lacks).  This module
 only answers "where is the native code":
 
     di_hpc_amd.get_library()   path of libhpc_rll_hip.so (the torch-free C ABI)

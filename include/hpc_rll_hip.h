@@ -519,6 +519,67 @@ int hpc_rll_sac_discrete_backward(const float* g_policy, const float* g_critic, 
                                   int64_t rows, int N, void* stream);
 int hpc_rll_sac_discrete_last_config(int* out);
 
+/* Soft Actor-Critic for continuous actions: the tanh-squashed Gaussian head and the SAC losses (no reference counterpart; the
+ * semantics restate DI-engine's SACPolicy._forward_learn with q_v_1step_td_error).
+ * The head.  mu, sigma, eps: `rows` rows of A floats; eps is standard-normal noise and a constant of the op (there is no RNG in
+ * the kernel); sigma > 0 is the caller's contract.  Per row:
+ *   u_j  = mu_j + sigma_j eps_j,   a_j = tanh(u_j)                                                      -> action (rows,A)
+ *   logp = sum_j [ -eps_j^2/2 - log sigma_j - log(2 pi)/2 + 2|u_j| + 2 log1p(exp(-2|u_j|)) - 2 log 2 ]  -> log_prob (rows)
+ * The last three terms are -log(1 - tanh^2 u_j) exactly: log_prob is formed from u, never from the rounded a (in fp32 a is
+ * exactly +-1 from |u| ~ 9).  DI-engine takes log(1 - a^2 + 1e-6) there; the two agree to 1e-6 / (1 - tanh^2 u) per dimension.
+ *   gu_j = g_a_j (1 - a_j^2) + 2 g_l a_j,   grad_mu_j = gu_j,   grad_sigma_j = gu_j eps_j - g_l / sigma_j
+ * hpc_rll_tanh_gaussian_rsample_forward -- one launch; action (rows,A) and log_prob (rows) are written once.
+ * hpc_rll_tanh_gaussian_rsample_backward -- one streaming launch without reductions or atomics.  g_action (rows,A) and
+ *   g_log_prob (rows) may each be NULL (zero, not read); grad_mu and grad_sigma may each be NULL (not formed; sigma and eps are
+ *   read for grad_sigma alone and may be NULL without it); with both NULL nothing is launched.  `action` is the forward's.
+ *   Where a = +-1 exactly the g_action part of the gradient is exactly 0.
+ * 16-byte loads and stores need A % 4 == 0 and every (rows,A) pointer the launch touches on 16 bytes, outputs included.
+ * The losses.  One float per sample in every operand (`rows` floats); done (rows) of `mask_dtype` (HPC_RLL_MASK_U8 /
+ * HPC_RLL_MASK_F32; NULL = no episode ends), k = 1 - done; weight (rows) (NULL = ones: an exact 1 is multiplied).  The
+ * temperature is alpha_dev[0], a device scalar, when alpha_dev is given, otherwise `alpha`.
+ *   m' = min(target_q1, target_q2),  G = reward + gamma k (m' - alpha next_log_prob)  (a constant),  target_q = G
+ *   d_i = q_i - G,   td_error = mean_i d_i^2 (unweighted),   m = min(new_q1, new_q2)
+ *   out4 = { scale sum (alpha log_prob - m),  scale sum w d_1^2,  scale sum w d_2^2 (0 for a single critic),  -scale sum log_prob }
+ *   grad_q_i = g_i 2 scale w d_i,   grad_log_prob = g_policy alpha scale,   grad_new_q_i = -g_policy scale s_i
+ * s_i is 1 for the strictly smaller of new_q1, new_q2, 0 for the other and 1/2 each at a tie (torch.minimum's rule); both
+ * minima propagate a NaN from either side, and 0 * NaN = NaN: a NaN target critic poisons G of its row even when done = 1.
+ * The critic half (q1, q2, target_q1, target_q2, next_log_prob, reward, done, weight, td_error, target_q) is absent when q1
+ * is NULL and the actor half (log_prob, new_q1, new_q2) when log_prob is NULL; the sums of an absent half are 0.  The second
+ * critics q2, target_q2, new_q2 of the halves that are given are all given or all NULL (a single critic).
+ * hpc_rll_sac_continuous_forward -- one launch.  ws: hpc_rll_sac_continuous_workspace_floats(rows) floats: 2 scale w d_1 |
+ *   2 scale w d_2 | s_1 (rows each) | the partial sums and (alpha scale, scale).  rows == 0 zeroes out4 and launches nothing.
+ * hpc_rll_sac_continuous_backward -- one streaming launch, each given output (rows) written once; any may be NULL, with all
+ *   NULL nothing is launched.  g_policy, g_critic, g_twin are device scalars (NULL = 1).  `ws` is the forward's.
+ * hpc_rll_sac_continuous_last_config -- out[HPC_RLL_SAC_CONTINUOUS_CONFIG_INTS] = four parts of {launches so far, G, VEC, E
+ *   (lanes per row, floats per load, loads per lane and row), R (rows per group and iteration), flags, workgroups}:
+ *    [0..6]   the head forward: flags 0,
+ *    [7..13]  the head backward: flags bit 0 g_action given, bit 1 g_log_prob given, bit 2 grad_mu, bit 3 grad_sigma written,
+ *    [14..20] the loss forward (G, VEC, E, R read 0): flags bit 0 weight given; bits 1-2 done: 0 none, 1 bytes, 2 floats;
+ *             bit 3 twin critics; bit 4 the critic half, bit 5 the actor half given; bit 6 alpha read from the device,
+ *    [21..27] the loss backward (G, VEC, E, R read 0): flags bit 0 grad_q1, bit 1 grad_q2, bit 2 grad_log_prob,
+ *             bit 3 grad_new_q1, bit 4 grad_new_q2 written;
+ *   each part is {0, -1 ...} before its first launch; HPC_RLL_EINVAL for out == NULL.
+ * 1 <= A <= 1024, beyond that HPC_RLL_EUNSUPPORTED.  Argument errors, before any HIP call and with nothing written:
+ * HPC_RLL_EINVAL (null operands, one of a twin set without the others, both halves absent, then negative sizes, A <= 0 or an
+ * unknown mask_dtype), HPC_RLL_EALIGN (a float pointer off 4-byte alignment; a byte mask has none), then
+ * HPC_RLL_EUNSUPPORTED (A > 1024); then empty shapes return 0. */
+#define HPC_RLL_SAC_CONTINUOUS_CONFIG_INTS (28)
+int hpc_rll_tanh_gaussian_rsample_forward(const float* mu, const float* sigma, const float* eps, float* action,
+                                          float* log_prob, int64_t rows, int A, void* stream);
+int hpc_rll_tanh_gaussian_rsample_backward(const float* g_action, const float* g_log_prob, const float* sigma,
+                                           const float* eps, const float* action, float* grad_mu, float* grad_sigma,
+                                           int64_t rows, int A, void* stream);
+int64_t hpc_rll_sac_continuous_workspace_floats(int64_t rows);
+int hpc_rll_sac_continuous_forward(const float* q1, const float* q2, const float* target_q1, const float* target_q2,
+                                   const float* next_log_prob, const float* reward, const void* done, int mask_dtype,
+                                   const float* weight, const float* log_prob, const float* new_q1, const float* new_q2,
+                                   const float* alpha_dev, float alpha, float* out4, float* td_error, float* target_q,
+                                   float* ws, int64_t rows, float gamma, float scale, void* stream);
+int hpc_rll_sac_continuous_backward(const float* g_policy, const float* g_critic, const float* g_twin, const float* ws,
+                                    float* grad_q1, float* grad_q2, float* grad_log_prob, float* grad_new_q1,
+                                    float* grad_new_q2, int64_t rows, void* stream);
+int hpc_rll_sac_continuous_last_config(int* out);
+
 /* QMIX: the monotonic mixing network from the hypernetworks' outputs on, and the mixed one-step TD loss of a learner (no
  * reference counterpart; the semantics restate DI-engine's Mixer.forward and v_1step_td_error on the mixed values).  Per
  * sample (row): agent_q (A) the agents' chosen-action values; w1 (A,E) row-major, element [a,e] at a*E + e; b1 (E); w2 (E);

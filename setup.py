@@ -10,7 +10,7 @@ from setuptools.command.build_ext import build_ext
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.join(ROOT, "di-hpc_amd")
-MODULES = ["hpc_rl_utils", "hpc_torch_utils_network", "hpc_models", "hpc_marl", "hpc_twohot", "hpc_replay"]
+MODULES = ["hpc_rl_utils", "hpc_torch_utils_network", "hpc_models", "hpc_marl", "hpc_twohot", "hpc_replay", "hpc_sac"]
 
 
 class BuildNative(build_ext):
