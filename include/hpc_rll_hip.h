@@ -580,6 +580,60 @@ int hpc_rll_sac_continuous_backward(const float* g_policy, const float* g_critic
                                     float* grad_new_q2, int64_t rows, void* stream);
 int hpc_rll_sac_continuous_last_config(int* out);
 
+/* Truncated Quantile Critics (Kuznetsov et al. 2020): SAC whose critics are ensembles of quantile heads (no reference
+ * counterpart; the semantics restate the authors' implementation, the mean over all four axes).  The head and the temperature
+ * loss are those of continuous SAC above.
+ * The critic loss.  z (rows,M,N) the online critics' quantiles at the replayed action; target_z (rows,Mt,Nt) the target
+ * critics' at the next state's sampled action, n = Mt Nt pooled atoms per row; next_log_prob, reward (rows); done (rows) of
+ * `mask_dtype` (HPC_RLL_MASK_U8 / HPC_RLL_MASK_F32; NULL = no episode ends), k = 1 - done; weight (rows) (NULL = ones: an exact
+ * 1 is multiplied); the temperature is alpha_dev[0], a device scalar, when alpha_dev is given, otherwise `alpha`; `drop` atoms
+ * are cut from the top of the pooled row, K = n - drop are kept.  Per row:
+ *   s_(0) <= ... <= s_(n-1)   the row's n target atoms in ascending order
+ *   y_j   = reward + gamma k (s_(j) - alpha next_log_prob)      j < K   (a constant)          -> target_atoms (rows,K)
+ *   tau_i = (2 i + 1) / (2 N),   e = y_j - z[m,i],   rho = |tau_i - 1{e < 0}| huber_kappa(e) / kappa
+ *   td    = sum_{m,i,j} rho / (M N K)                                   (unweighted)          -> td_error (rows)
+ *   loss[0] = scale sum_rows w td
+ *   grad_z[m,i] = -g scale w / (M N K) sum_j |tau_i - 1{e < 0}| clamp(e, -kappa, kappa) / kappa
+ * The selection acts on the raw atoms, not on y (the map is monotone, and collapses where done = 1).  The order is that of the
+ * floats' bits made sortable: -0 < +0, every NaN above +inf (NaNs are the first atoms cut), ties by pooled index; the loss does
+ * not depend on the tie-break.  A row with more NaN atoms than `drop` gets a NaN td_error and poisons the loss.
+ * hpc_rll_tqc_critic_forward -- one launch: a wave per row ranks the atoms by counting in LDS, scatters the kept ones in order
+ *   and runs the M N K pair loop.  ws: hpc_rll_tqc_workspace_floats(rows, M N) floats: the partial sums | the unit gradient
+ *   (rows,M,N), grad_z without g.  rows == 0 zeroes loss and launches nothing.  The 16-byte variant loads the pooled row in
+ *   16-byte pieces; it needs n % 4 == 0 and every float operand of the launch on 16 bytes.
+ * hpc_rll_tqc_critic_backward -- one streaming launch, grad_z = g_loss[0] x the unit gradient; grad_z NULL launches nothing.
+ * The actor loss.  log_prob (rows); new_z (rows,MN) the online critics' quantiles at the action the head has just sampled:
+ *   out2 = { scale sum_rows (alpha log_prob - mean_{m,i} new_z),  -scale sum_rows log_prob }
+ *   grad_log_prob = g alpha scale,   grad_new_z = -g scale / MN
+ * hpc_rll_tqc_policy_forward -- one launch, a wave per row; ws: hpc_rll_tqc_workspace_floats(0, 0) floats (the partial sums
+ *   and (alpha scale, scale / MN)).  rows == 0 zeroes out2 and launches nothing.
+ * hpc_rll_tqc_policy_backward -- one streaming launch that fills the gradients that are given; with both NULL nothing is
+ *   launched.  g_policy is a device scalar (NULL = 1).  `ws` is the forward's.
+ * hpc_rll_tqc_last_config -- out[HPC_RLL_TQC_CONFIG_INTS] = four parts of {launches so far, kernel id, R (atoms per lane of
+ *   the ranking, 1 2 4 8 16; 0 elsewhere), load width in floats (4 or 1), workgroups, flags}:
+ *    [0..5]   the critic forward, id 1: flags bit 0 weight given; bits 1-2 done: 0 none, 1 bytes, 2 floats; bit 6 alpha read
+ *             from the device,
+ *    [6..11]  the critic backward, id 2: flags 0,
+ *    [12..17] the actor forward, id 3: flags bit 6 alpha read from the device,
+ *    [18..23] the actor backward, id 4: flags bit 0 grad_log_prob, bit 1 grad_new_z written;
+ *   each part is {0, -1 ...} before its first launch; HPC_RLL_EINVAL for out == NULL.
+ * 1 <= M N <= 1024 and 1 <= n <= 1024, beyond that HPC_RLL_EUNSUPPORTED.  Argument errors, before any HIP call and with nothing
+ * written: HPC_RLL_EINVAL (null operands, negative rows, a size <= 0, kappa <= 0, an unknown mask_dtype), HPC_RLL_EALIGN (a
+ * float pointer off 4-byte alignment), HPC_RLL_EUNSUPPORTED (the limits), HPC_RLL_EINVAL (drop < 0 or drop >= n); then empty
+ * shapes return 0. */
+#define HPC_RLL_TQC_CONFIG_INTS (24)
+int64_t hpc_rll_tqc_workspace_floats(int64_t rows, int MN);
+int hpc_rll_tqc_critic_forward(const float* z, const float* target_z, const float* next_log_prob, const float* reward,
+                               const void* done, int mask_dtype, const float* weight, const float* alpha_dev, float alpha,
+                               float* loss, float* td_error, float* target_atoms, float* ws, int64_t rows, int M, int N, int Mt,
+                               int Nt, int drop, float gamma, float kappa, float scale, void* stream);
+int hpc_rll_tqc_critic_backward(const float* g_loss, const float* ws, float* grad_z, int64_t rows, int M, int N, void* stream);
+int hpc_rll_tqc_policy_forward(const float* log_prob, const float* new_z, const float* alpha_dev, float alpha, float* out2,
+                               float* ws, int64_t rows, int MN, float scale, void* stream);
+int hpc_rll_tqc_policy_backward(const float* g_policy, const float* ws, float* grad_log_prob, float* grad_new_z, int64_t rows,
+                                int MN, void* stream);
+int hpc_rll_tqc_last_config(int* out);
+
 /* QMIX: the monotonic mixing network from the hypernetworks' outputs on, and the mixed one-step TD loss of a learner (no
  * reference counterpart; the semantics restate DI-engine's Mixer.forward and v_1step_td_error on the mixed values).  Per
  * sample (row): agent_q (A) the agents' chosen-action values; w1 (A,E) row-major, element [a,e] at a*E + e; b1 (E); w2 (E);
