@@ -1199,9 +1199,6 @@ at::ScalarType logits_dtype(const Tensor& t, const char* name) {
     return st;
 }
 int elem_code(at::ScalarType st) { return st == at::kBFloat16 ? HPC_RLL_ELEM_BF16 : HPC_RLL_ELEM_F32; }
-void grpo_check_v(const char* op, int64_t V) {
-    TORCH_CHECK(V <= 262144, op, ": V = ", V, " is not supported (1 <= V <= 262144)");
-}
 
 // logp = logits[..., a] - logsumexp(logits); saves the logits, action and lse (4 bytes per token)
 struct TokenLogpFn : public ag::Function<TokenLogpFn> {

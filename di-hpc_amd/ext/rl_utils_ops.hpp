@@ -22,6 +22,11 @@ inline int mask_code(const Tensor& m, const char* name) {
     return -1;
 }
 
+// the vocabulary limit of the language-model ops (rl_utils.cpp, lm_linear.cpp)
+inline void grpo_check_v(const char* op, int64_t V) {
+    TORCH_CHECK(V <= 262144, op, ": V = ", V, " is not supported (1 <= V <= 262144)");
+}
+
 // The argument checks of the ops that name a wrong argument even on host tensors.  They run in two phases: dtype and
 // shape of every tensor first, GPU / contiguous / device afterwards.  An op declares each tensor ONCE, with add(): the
 // dtype and shape messages are raised there, in declaration order.  One later on_device_of(lead) raises req()'s

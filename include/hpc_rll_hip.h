@@ -949,6 +949,39 @@ int hpc_rll_lm_ppo_backward(const float* g_policy, const float* g_entropy, const
                             float* grad_value, int B, int S, int V, int use_den, void* stream);
 int hpc_rll_lm_ppo_last_config(int* out);
 
+/* The language-model head fused with its bf16 matrix product (no reference counterpart): the log-probability and the entropy
+ * of given tokens straight from the hidden states and the head's weight, for the operands a step evaluates WITHOUT gradient
+ * (the old and the reference policy).  hidden (rows, H) bf16; w (V, H) bf16, nn.Linear.weight's own layout; action (rows)
+ * int64; weight (rows) fp32 or NULL (= ones).  With x = (hidden w^T) inv_temperature held in the fp32 accumulators of the
+ * matrix instructions (no logit is rounded to bf16 or written to memory):
+ *     logp = x[a] - logsumexp(x),   entropy = logsumexp(x) - sum_v p_v x_v   (entropy may be NULL: not formed).
+ * 32 <= H <= 16384 with H % 32 == 0, 1 <= V <= 262144, inv_temperature > 0 and finite, any rows; offsets are 64-bit.  hidden,
+ * w and ws lie on 16 bytes.  A row whose action is outside [0,V), or whose weight is 0, is DROPPED: logp = entropy = 0, and
+ * whatever its hidden holds (NaN included) touches no other row.  NaN among the logits of a live row counts with probability
+ * 0, as in the entry points above.
+ * hpc_rll_lm_linear_forward -- two launches.  The first has a grid of ceil(rows / 128) row tiles x `splits` vocabulary
+ *   splits (0 = by rule: the grid fills two workgroup slots per CU, capped by the column tiles and by 64); a workgroup walks
+ *   the 128-wide column tiles of its split, keeps RowStat's online (m, s, u) per lane on the accumulators and writes one
+ *   partial (m, s, u, x[a]) per (row, split) to ws; a row tile without a live row is skipped.  The second merges a row's
+ *   partials in split order.  No float atomics: the same bits on every run for the same split count.  What is written:
+ *   logp (rows), entropy (rows), and the first rows * splits-used * 16 bytes of ws (nothing for the rows of a skipped tile).
+ * hpc_rll_lm_linear_workspace_bytes -- rows * splits * 16; splits == 0 answers for 64, which covers any count the rule picks.
+ *   HPC_RLL_EINVAL for rows < 0 or splits outside 0 .. 64.
+ * hpc_rll_lm_linear_last_config -- out[HPC_RLL_LM_LINEAR_CONFIG_INTS] = { launches so far, tile rows BM (128), tile columns
+ *   BN (128), K step BK (64), splits used, grid x (row tiles), grid y (splits), threads per workgroup, LDS bytes, 1 when the
+ *   entropy moment was carried, row tiles skipped as all-dropped };  {0, -1 ...} before the first launch.  The last entry is
+ *   counted on the device: this call waits for the stream of the last launch to read it.  HPC_RLL_EINVAL for out == NULL.
+ * Argument errors, before any HIP call and with nothing written: HPC_RLL_EINVAL (negative rows, H <= 0, V <= 0, splits outside
+ * 0 .. 64, inv_temperature not in (0, FLT_MAX], then null operands when rows > 0), HPC_RLL_EALIGN (hidden, w or ws off 16
+ * bytes, action off 8, a float array off 4), then HPC_RLL_EUNSUPPORTED (H < 32, H > 16384, H % 32 != 0, V > 262144); then
+ * rows == 0 returns 0. */
+#define HPC_RLL_LM_LINEAR_CONFIG_INTS (11)
+int64_t hpc_rll_lm_linear_workspace_bytes(int64_t rows, int splits);
+int hpc_rll_lm_linear_forward(const void* hidden, const void* w, const int64_t* action, const float* weight, int64_t rows,
+                              int H, int V, float inv_temperature, int splits, void* ws, float* logp, float* entropy,
+                              void* stream);
+int hpc_rll_lm_linear_last_config(int* out);
+
 /* PPO -- replaces PPOForward/Backward (rl_utils/entry.h:158-165, src/rl_utils/ppo.cu:8-111).
  * logits (B,N), action (B,), value_new/old, adv, ret, weight (B,) (weight NULL = ones).
  * out5 = policy_loss, value_loss, entropy_loss, approx_kl, clipfrac.  dual_clip < 1 disables dual clip
