@@ -950,8 +950,8 @@ int hpc_rll_lm_ppo_backward(const float* g_policy, const float* g_entropy, const
 int hpc_rll_lm_ppo_last_config(int* out);
 
 /* The language-model head fused with its bf16 matrix product (no reference counterpart): the log-probability and the entropy
- * of given tokens straight from the hidden states and the head's weight, for the operands a step evaluates WITHOUT gradient
- * (the old and the reference policy).  hidden (rows, H) bf16; w (V, H) bf16, nn.Linear.weight's own layout; action (rows)
+ * of given tokens straight from the hidden states and the head's weight.  hpc_rll_lm_linear_forward serves the operands a step
+ * evaluates WITHOUT gradient (the old and the reference policy); the block below has the gradient.  hidden (rows, H) bf16; w (V, H) bf16, nn.Linear.weight's own layout; action (rows)
  * int64; weight (rows) fp32 or NULL (= ones).  With x = (hidden w^T) inv_temperature held in the fp32 accumulators of the
  * matrix instructions (no logit is rounded to bf16 or written to memory):
  *     logp = x[a] - logsumexp(x),   entropy = logsumexp(x) - sum_v p_v x_v   (entropy may be NULL: not formed).
@@ -981,6 +981,59 @@ int hpc_rll_lm_linear_forward(const void* hidden, const void* w, const int64_t* 
                               int H, int V, float inv_temperature, int splits, void* ws, float* logp, float* entropy,
                               void* stream);
 int hpc_rll_lm_linear_last_config(int* out);
+
+/* The gradient of the fused head, for the policy being trained: dhidden (rows, H) and dW (V, H), bf16 like the operands,
+ * without a (rows, V) tensor.  hpc_rll_lm_linear_forward_lse is the forward above with one more output, lse (rows) fp32
+ * (0 for a dropped row; lse == NULL is exactly hpc_rll_lm_linear_forward: the same kernels, the same bits); the backward
+ * takes it and, when the entropy has a gradient, the entropy.  Per live row, with x and p_v = exp(x_v - lse) as above,
+ * H_r the entropy and the upstream gl = g_logp[r], ge = g_entropy[r] (each NULL = zeros):
+ *     g_v = inv_temperature ( gl (1[v = a] - p_v) - ge p_v (log p_v + H_r) ),   dhidden = G w,   dW = G^T hidden;
+ * a p_v that underflows to 0 contributes exactly 0, by selection.  Dropped rows have g = 0 and dhidden exactly 0, and
+ * whatever their hidden holds (NaN included) reaches neither another row nor dW: 0 * NaN is never formed, the dW product
+ * loads the hidden of a dropped row as zeros.
+ * hpc_rll_lm_linear_backward -- walks the vocabulary in chunks of VC columns, VC a multiple of 128 (`chunk`, or 0 = by rule:
+ *   the largest multiple of 128 for which G and G^T together stay within 256 MiB -- a constant nobody has measured -- at
+ *   least 128, at most 128 ceil(V / 128)).  lse makes the chunks independent.  Per chunk: (1) the grad-logits launch
+ *   recomputes the chunk's logits with the forward's product loop, forms g on the fp32 accumulators, rounds once to bf16 and
+ *   writes G (Rp x VC row-major, Rp = 128 ceil(rows / 128); only when grad_hidden is wanted) and G^T (VC x Rp; only when
+ *   grad_w is), zeros explicitly for rows past `rows`, columns past V and dropped rows; a row tile without a live row is
+ *   zero-filled without the product.  (2) hpc_rll_lm_linear_gemm twice: dhidden (+)= G w[chunk], accumulated in fp32
+ *   (rows x H, in ws) across chunks in chunk order, the last chunk writing bf16 -- a single chunk writes bf16 directly and
+ *   has no accumulator; dW[chunk] = G^T hidden, the chunk's rows of grad_w written once.  grad_hidden or grad_w NULL = not
+ *   wanted: no product, no workspace for it (both NULL: nothing is launched).  No split-K, no atomics: the same bits on
+ *   every run for the same chunk size.
+ * hpc_rll_lm_linear_backward_workspace_bytes -- Rp * VC * 2 * (want_dhidden + want_dw) + (want_dhidden and more than one
+ *   chunk ? rows * H * 4 : 0), in this order: G, G^T, the accumulator.  HPC_RLL_EINVAL for rows < 0, H <= 0, V <= 0, or a
+ *   chunk that is negative or no multiple of 128.
+ * hpc_rll_lm_linear_gemm -- the product alone: C (M x N) = A (M x K) B (K x N), A bf16 row-major (pitch lda, contiguous
+ *   along K), B bf16 row-major (pitch ldb, contiguous along N), fp32 accumulation in v_mfma_f32_32x32x16_bf16, 128 x 128 x 64
+ *   tiles, B staged transposed.  Rows of B at k >= K_valid are zeros without being read, and so are, with live_action given,
+ *   the rows k whose live_action[k] is outside [0, live_V) or whose live_weight[k] (NULL = ones) is 0.  mode 0: C_bf16 = AB;
+ *   1: C_f32 = AB; 2: C_f32 += AB; 3: C_bf16 = C_f32 + AB (C_f32 is read only); pitch ldc, exactly M x N outputs in 16-byte
+ *   pieces.  N, K and the pitches are multiples of 8, A, B and C lie on 16 bytes.
+ * hpc_rll_lm_linear_backward_last_config -- out[HPC_RLL_LM_LINEAR_BACKWARD_CONFIG_INTS] = { backward calls that launched,
+ *   chunk columns VC, chunks, dhidden products, dW products, grad-logits launches of the last call;  product launches so
+ *   far (hpc_rll_lm_linear_gemm's included), its tile rows BM (128), tile columns BN (128), K step BK (64), threads per
+ *   workgroup, LDS bytes };  each half {0, -1 ...} before its first launch.  HPC_RLL_EINVAL for out == NULL.
+ * Argument errors, before any HIP call and with nothing written, in the forward's order: HPC_RLL_EINVAL (backward: negative
+ *   rows, H <= 0, V <= 0, a bad chunk, inv_temperature not in (0, FLT_MAX], then null hidden, w, action, lse or ws when
+ *   rows > 0, g_entropy without entropy; gemm: a negative size, K_valid > K, a mode outside 0 .. 3, a pitch below its row,
+ *   live_weight without live_action, then a null operand that would be read or written), HPC_RLL_EALIGN (an operand, ws or a
+ *   result off 16 bytes, action off 8, a float array off 4), then HPC_RLL_EUNSUPPORTED (backward: H and V as in the
+ *   forward; gemm: N, K or a pitch no multiple of 8); then rows == 0 (gemm: M == 0 or N == 0) returns 0. */
+#define HPC_RLL_LM_LINEAR_BACKWARD_CONFIG_INTS (12)
+int hpc_rll_lm_linear_forward_lse(const void* hidden, const void* w, const int64_t* action, const float* weight, int64_t rows,
+                                  int H, int V, float inv_temperature, int splits, void* ws, float* logp, float* entropy,
+                                  float* lse, void* stream);
+int64_t hpc_rll_lm_linear_backward_workspace_bytes(int64_t rows, int H, int V, int chunk, int want_dhidden, int want_dw);
+int hpc_rll_lm_linear_backward(const float* g_logp, const float* g_entropy, const void* hidden, const void* w,
+                               const int64_t* action, const float* weight, const float* lse, const float* entropy,
+                               int64_t rows, int H, int V, float inv_temperature, int chunk, void* ws, void* grad_hidden,
+                               void* grad_w, void* stream);
+int hpc_rll_lm_linear_gemm(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M, int N, int64_t K,
+                           int64_t K_valid, const int64_t* live_action, const float* live_weight, int live_V, int mode,
+                           void* C_bf16, float* C_f32, int64_t ldc, void* stream);
+int hpc_rll_lm_linear_backward_last_config(int* out);
 
 /* PPO -- replaces PPOForward/Backward (rl_utils/entry.h:158-165, src/rl_utils/ppo.cu:8-111).
  * logits (B,N), action (B,), value_new/old, adv, ret, weight (B,) (weight NULL = ones).
