@@ -3,7 +3,8 @@
 //   * RowStat<ENT>: the online softmax statistic of a lane, with the entropy moment only when ENT, its merge, wave
 //     butterfly and batch update, and row_stats, the walk of one row (unaligned peel, kInFlight loads in flight, guarded tail);
 //   * lm_head_kernel<Elem, ALIGNED, NT, ENT> and its launcher: GRPO instantiates ENT = false, LM-PPO ENT = true;
-//   * zero_row / stream_row: the row-streaming body of the two gradient kernels, around the unit's own element formula;
+//   * zero_row / stream_row: the row-streaming body of the two gradient kernels, around the unit's own element formula, and
+//     stream_row2, the same with two input rows (lm_kl.hip);
 //   * seq_weight_sum: the first pass of the token-loss kernels over a sequence;
 //   * with_elem / with_row_kernel: the element type and the two-by-two kernel choice of a row launch as types;
 //   * lm_shape_status: the argument checks the C entry points repeat.
@@ -297,6 +298,52 @@ __device__ __forceinline__ void stream_row(const Elem* p, Elem* o, int V, int ti
 #pragma unroll
             for (int k = 0; k < kInFlight; ++k)
                 if (i + k * NT < V) IO::put(o + i + k * NT, f(xx[k], ai == i + k * NT));
+        }
+    }
+}
+
+// o[v] = f(p[v], q[v]): stream_row with a second input row and no chosen column (lm_kl.hip).  WIDE needs all three bases and
+// the row pitch on 16 bytes; kInFlight loads of EACH row are issued before the first is used.
+template <class Elem, bool WIDE, int NT, class F>
+__device__ __forceinline__ void stream_row2(const Elem* p, const Elem* q, Elem* o, int V, int tid, F&& f) {
+    using IO = ElemIO<Elem>;
+    constexpr int P = IO::P;
+    if (WIDE) {
+        const int nvec = V / P;
+        const vuint4* __restrict__ pv = reinterpret_cast<const vuint4*>(p);
+        const vuint4* __restrict__ qv = reinterpret_cast<const vuint4*>(q);
+        vuint4* ov = reinterpret_cast<vuint4*>(o);
+        for (int v = tid; v < nvec; v += kInFlight * NT) {
+            vuint4 rp[kInFlight], rq[kInFlight];
+#pragma unroll
+            for (int k = 0; k < kInFlight; ++k)
+                if (v + k * NT < nvec) {
+                    rp[k] = __builtin_nontemporal_load(pv + v + k * NT);
+                    rq[k] = __builtin_nontemporal_load(qv + v + k * NT);
+                }
+#pragma unroll
+            for (int k = 0; k < kInFlight; ++k)
+                if (v + k * NT < nvec) {
+                    float xx[P], yy[P];
+                    IO::unpack(rp[k], xx);
+                    IO::unpack(rq[k], yy);
+#pragma unroll
+                    for (int j = 0; j < P; ++j) xx[j] = f(xx[j], yy[j]);
+                    __builtin_nontemporal_store(IO::pack(xx), ov + v + k * NT);
+                }
+        }
+    } else {
+        for (int i = tid; i < V; i += kInFlight * NT) {
+            float xx[kInFlight], yy[kInFlight];
+#pragma unroll
+            for (int k = 0; k < kInFlight; ++k)
+                if (i + k * NT < V) {
+                    xx[k] = IO::get(p + i + k * NT);
+                    yy[k] = IO::get(q + i + k * NT);
+                }
+#pragma unroll
+            for (int k = 0; k < kInFlight; ++k)
+                if (i + k * NT < V) IO::put(o + i + k * NT, f(xx[k], yy[k]));
         }
     }
 }

@@ -1035,6 +1035,44 @@ int hpc_rll_lm_linear_gemm(const void* A, int64_t lda, const void* B, int64_t ld
                            void* C_bf16, float* C_f32, int64_t ldc, void* stream);
 int hpc_rll_lm_linear_backward_last_config(int* out);
 
+/* The exact divergence over the whole vocabulary between two rows of logits (no reference counterpart; on-policy distillation /
+ * GKD, a full-KL penalty, KL-to-reference monitors).  logits ("student", x) and teacher (y): (rows, V) of the same element type
+ * `elem`; weight (rows) fp32 or NULL (= ones) only selects the rows to drop.  With a = x inv_temperature, b = y inv_temperature
+ * (entries clamped as in the entries above: -inf and NaN count as -FLT_MAX), p = softmax(a), q = softmax(b), lx = lse(a),
+ * ly = lse(b):
+ *     HPC_RLL_KL_FORWARD   kl = KL(q||p) = sum q (b - a) - ly + lx                         d kl / d a_i = p_i - q_i
+ *     HPC_RLL_KL_REVERSE   kl = KL(p||q) = sum p (a - b) - lx + ly                         p_i ((a_i - b_i) - lx + ly - kl)
+ *     HPC_RLL_KL_JSD       kl = beta KL(q||m) + (1 - beta) KL(p||m), m = beta q + (1 - beta) p,  0 < beta < 1
+ *                                                                          (1 - beta) p_i (log p_i - log m_i - KL(p||m))
+ * An entry that is -inf in both rows adds exactly nothing and has gradient exactly 0.  An entry one policy gives probability 0
+ * and the other weights makes the divergence +inf mathematically: the result is then some non-NaN number, and avoiding the
+ * case is the caller's.
+ * hpc_rll_lm_kl_forward -- one launch with the row mapping of hpc_rll_lm_head_forward; both rows are read once (jsd: twice, the
+ *   second time right after the first by the same workgroup).  kl, lse_x, lse_y (rows) and, required for jsd only, kl_pm =
+ *   KL(p||m) (rows): what the backward needs, 12 or 16 bytes per row.  A row with weight == 0 is not read: its outputs are 0.
+ * hpc_rll_lm_kl_backward -- one streaming launch: grad_logits[r,:] = g[r] inv_temperature (d kl / d a)[r,:] in the logits'
+ *   element type (bf16: round to nearest even), nontemporal stores; g (rows) fp32.  A row with weight == 0 or g == 0 is
+ *   zero-filled without reading its logits.  No atomics, the same bits on every run.
+ * hpc_rll_lm_kl_last_config -- out[HPC_RLL_LM_KL_CONFIG_INTS] = { [0..6] the forward launch last issued: launches so far,
+ *   element type, bytes per access (16, or the element's size when a base of the launch or the pitch is off 16 bytes), threads
+ *   per row (64: a wave per row; 256: a workgroup per row), rows per workgroup, workgroups, mode; [7..13] the same of the
+ *   backward launch }; each part is {0, -1 ...} before its first launch; HPC_RLL_EINVAL for out == NULL.
+ * Argument errors, before any HIP call and with nothing written: HPC_RLL_EINVAL (a mode outside the three, beta outside (0,1)
+ * for jsd, inv_temperature not positive and finite; then null operands; then negative sizes or an unknown element type),
+ * HPC_RLL_EALIGN (a float array off 4-byte alignment, logits off their element size), then HPC_RLL_EUNSUPPORTED (V > 262144);
+ * then rows == 0 or V == 0 returns 0 (V == 0 with rows: the forward's outputs are zeros). */
+#define HPC_RLL_KL_FORWARD (0)
+#define HPC_RLL_KL_REVERSE (1)
+#define HPC_RLL_KL_JSD (2)
+#define HPC_RLL_LM_KL_CONFIG_INTS (14)
+int hpc_rll_lm_kl_forward(const void* logits, const void* teacher, int elem, const float* weight, float* kl, float* lse_x,
+                          float* lse_y, float* kl_pm, int64_t rows, int V, int mode, float beta, float inv_temperature,
+                          void* stream);
+int hpc_rll_lm_kl_backward(const float* g, const void* logits, const void* teacher, int elem, const float* weight,
+                           const float* kl, const float* lse_x, const float* lse_y, const float* kl_pm, void* grad_logits,
+                           int64_t rows, int V, int mode, float beta, float inv_temperature, void* stream);
+int hpc_rll_lm_kl_last_config(int* out);
+
 /* PPO -- replaces PPOForward/Backward (rl_utils/entry.h:158-165, src/rl_utils/ppo.cu:8-111).
  * logits (B,N), action (B,), value_new/old, adv, ret, weight (B,) (weight NULL = ones).
  * out5 = policy_loss, value_loss, entropy_loss, approx_kl, clipfrac.  dual_clip < 1 disables dual clip
