@@ -26,7 +26,8 @@ Conventions, those of ``grpo`` and ``lm_ppo``:
 * ``1 <= V <= 262144``, ``temperature > 0``; no tokens gives an empty result and launches nothing;
 * contiguous GPU tensors; a base or a row pitch off 16 bytes takes the one-element path of the kernels.
 
-Out of scope: mixed element types, different vocabularies, top-k teachers, and fusing the LM head's matrix product."""
+Out of scope: mixed element types, different vocabularies, and fusing the LM head's matrix product.  A teacher kept as its top-k
+log-probabilities and indices is served by ``hpc_rll.rl_utils.lm_topk``."""
 import torch
 
 import hpc_lm_kl

@@ -1073,6 +1073,50 @@ int hpc_rll_lm_kl_backward(const float* g, const void* logits, const void* teach
                            int64_t rows, int V, int mode, float beta, float inv_temperature, void* stream);
 int hpc_rll_lm_kl_last_config(int* out);
 
+/* Distillation from a top-k teacher (no reference counterpart): the teacher's k largest log-probabilities per token with
+ * their indices stand in for its full row of logits.  Element types, clamping and the weight's meaning as above.
+ * hpc_rll_lm_topk_forward -- the producer, one launch, a workgroup per row.  topk_index (rows, k) int32 and topk_logp (rows, k):
+ *   the k entries of logits[r, :] with the largest key, the key of an entry being clampf(x) + 0 of the RAW element (independent
+ *   of inv_temperature; -0 ties with +0; NaN and -inf tie with -FLT_MAX), sorted by key descending, equal keys by index
+ *   ascending -- a stable descending sort of the clamped row, cut at k.  topk_logp = a_i - logsumexp(a), a = clampf(x
+ *   inv_temperature) over the WHOLE row, from the same read of the row as the selection; an entry whose element was NaN or
+ *   -inf carries -inf.  A row with weight == 0 is not read: index -1, logp -inf.  1 <= k <= min(V, 256).
+ * hpc_rll_lm_topk_kl_forward -- the consumer, one launch with the row mapping of hpc_rll_lm_kl_forward; the student's row is
+ *   read once.  topk_index (rows, k) int32 (index64 = 0) or int64 (1), topk_logp (rows, k); an entry with an index outside
+ *   [0, V) or logp = -inf is padding; the indices of a row are distinct (duplicates: an unspecified value, nothing out of
+ *   bounds).  With p = softmax(logits inv_temperature), q_j = exp(logp_j), S = sum q_j, Q = min(S, 1), P = sum p_(i_j):
+ *     HPC_RLL_TOPK_TAIL_RENORM   kl = sum (q_j / Q) (log(q_j / Q) - log p_(i_j))
+ *     HPC_RLL_TOPK_TAIL_BUCKET   kl = sum q_j (logp_j - log p_(i_j)) + (1 - Q) (log(1 - Q) - log(1 - P)), the last term only when
+ *                                1 - Q > 0 and the student has mass outside the entries; 1 - P is summed, not subtracted.
+ *   kl, lse, c0, c1 (rows): the value and what the backward needs, 12 bytes per row.  A row with weight == 0 or without a
+ *   live entry is not read: its outputs are 0.  1 <= k <= 256.
+ * hpc_rll_lm_topk_kl_backward -- one streaming launch: grad_logits[r, v] = g[r] inv_temperature (d kl / d a_v) in the logits'
+ *   element type (bf16: round to nearest even), every element written once, nontemporal stores:
+ *     renorm   (S / Q) p_v - [v in top] q_v / Q            bucket   p_v (S - r P) + [v in top] (r p_v - q_v),  r = (1 - Q) / (1 - P)
+ *   A row with weight == 0, g == 0 or without a live entry is zero-filled without reading its logits.
+ * No float atomics, the same bits on every run.
+ * hpc_rll_lm_topk_last_config -- out[HPC_RLL_LM_TOPK_CONFIG_INTS] = { [0..6] the producer's launch last issued: launches so
+ *   far, element type, bytes per access (16, or the element's size when a base of the launch or the pitch is off 16 bytes),
+ *   threads per row, rows per workgroup, workgroups, k; [7..13] the same of the consumer's forward; [14..20] of its backward };
+ *   each part is {0, -1 ...} before its first launch; HPC_RLL_EINVAL for out == NULL.
+ * Argument errors, before any HIP call and with nothing written: HPC_RLL_EINVAL (k outside [1, 256], an unknown tail or
+ * index64, inv_temperature not positive and finite; then null operands; then negative sizes or an unknown element type),
+ * HPC_RLL_EALIGN (a float or int32 array off 4-byte alignment, int64 indices off 8, logits off their element size), then
+ * HPC_RLL_EUNSUPPORTED (V > 262144), then HPC_RLL_EINVAL (V < 1; the producer: k > V); then rows == 0 returns 0. */
+#define HPC_RLL_LM_TOPK_MAX_K (256)
+#define HPC_RLL_TOPK_TAIL_RENORM (0)
+#define HPC_RLL_TOPK_TAIL_BUCKET (1)
+#define HPC_RLL_LM_TOPK_CONFIG_INTS (21)
+int hpc_rll_lm_topk_forward(const void* logits, int elem, const float* weight, float* topk_logp, int* topk_index,
+                            int64_t rows, int V, int k, float inv_temperature, void* stream);
+int hpc_rll_lm_topk_kl_forward(const void* logits, int elem, const void* topk_index, int index64, const float* topk_logp,
+                               const float* weight, float* kl, float* lse, float* c0, float* c1, int64_t rows, int V, int k,
+                               int tail, float inv_temperature, void* stream);
+int hpc_rll_lm_topk_kl_backward(const float* g, const void* logits, int elem, const void* topk_index, int index64,
+                                const float* topk_logp, const float* weight, const float* lse, const float* c0, const float* c1,
+                                void* grad_logits, int64_t rows, int V, int k, int tail, float inv_temperature, void* stream);
+int hpc_rll_lm_topk_last_config(int* out);
+
 /* PPO -- replaces PPOForward/Backward (rl_utils/entry.h:158-165, src/rl_utils/ppo.cu:8-111).
  * logits (B,N), action (B,), value_new/old, adv, ret, weight (B,) (weight NULL = ones).
  * out5 = policy_loss, value_loss, entropy_loss, approx_kl, clipfrac.  dual_clip < 1 disables dual clip
