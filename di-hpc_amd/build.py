@@ -6,8 +6,8 @@
 1. libhpc_rll_hip.so -- the C-ABI HIP library: one translation unit per op under csrc/*.hip, compiled with
    hipcc --offload-arch=gfx950 and linked into di-hpc_amd/hpc_rll/_lib/.  hipcc cross-compiles without a GPU.
 2. hpc_rl_utils.so, hpc_torch_utils_network.so, hpc_models.so -- the PyTorch-ROCm extension modules (the reference's
-   three pybind modules, setup.py:19-49), hpc_marl.so, hpc_twohot.so, hpc_replay.so, hpc_sac.so, hpc_tqc.so, hpc_lm_linear.so, hpc_lm_kl.so and hpc_lm_topk.so, the multi-agent ops, the categorical value
-   losses, the prioritized-replay index, continuous SAC, TQC, the fused LM head, the vocabulary divergences and the top-k teacher ops, which the reference lacks: HOST-ONLY C++ under ext/*.cpp compiled with g++ against torch's headers and
+   three pybind modules, setup.py:19-49), hpc_marl.so, hpc_twohot.so, hpc_replay.so, hpc_sac.so, hpc_tqc.so, hpc_lm_linear.so, hpc_lm_kl.so, hpc_lm_topk.so and hpc_lm_policy.so, the multi-agent ops, the categorical value
+   losses, the prioritized-replay index, continuous SAC, TQC, the fused LM head, the vocabulary divergences, the top-k teacher ops and the log-prob policy losses, which the reference lacks: HOST-ONLY C++ under ext/*.cpp compiled with g++ against torch's headers and
    linked to libtorch + libhpc_rll_hip.so (rpath $ORIGIN/hpc_rll/_lib).  No device code, no hipify.
 The object files and the .so files are git-ignored but travel to the GPU box with the tree.
 """
@@ -44,6 +44,7 @@ EXT_MODULES = {
     "hpc_lm_linear": ["lm_linear.cpp"],
     "hpc_lm_kl": ["lm_kl.cpp"],
     "hpc_lm_topk": ["lm_topk.cpp"],
+    "hpc_lm_policy": ["lm_policy.cpp"],
 }
 # translation units under csrc/ that are compiled without packed-fp32 instructions (v_pk_add / v_pk_mul / v_pk_fma_f32); the
 # host pass of hipcc does not know the feature and says that it ignores it, the gfx950 pass applies it

@@ -34,7 +34,8 @@ Conventions:
 * ``B``, ``S`` or ``V`` of size 0 gives a zero loss and launches nothing;
 * contiguous GPU tensors.
 
-Out of scope: fusing the LM head's matrix product for the differentiable ``logit_new`` (for ``old`` and ``ref``, which carry no
+Out of scope: fusing the LM head's matrix product for the differentiable ``logit_new`` (``hpc_rll.rl_utils.lm_policy`` takes the
+fused head's ``(B,S)`` ``logp`` instead; for ``old`` and ``ref``, which carry no
 gradient, ``hpc_rll.rl_utils.lm_linear.linear_token_log_prob`` gives the ``(B,S)`` log-probs from hidden states), in-place gradients, float16, and vocabularies split over ranks (tensor
 parallelism).  The entropy over the vocabulary is not formed here: ``hpc_rll.rl_utils.lm_ppo.token_log_prob_entropy`` gives it
 with the log-probability from the same single read of the logits, and ``lm_ppo_loss`` is the token-level PPO loss on top."""

@@ -50,7 +50,8 @@ Conventions (those of ``grpo``):
 * contiguous GPU tensors;
 * nothing in the op synchronises with the host, so a learner step can be captured with ``hpc_rll.graphed``.
 
-Out of scope: fusing the LM head's matrix product for the differentiable ``logit_new`` (``old_logp``, which carries no gradient,
+Out of scope: fusing the LM head's matrix product for the differentiable ``logit_new`` (``hpc_rll.rl_utils.lm_policy`` takes the
+fused head's ``(B,S)`` ``logp`` instead; ``old_logp``, which carries no gradient,
 can come from ``hpc_rll.rl_utils.lm_linear.linear_token_log_prob``), a reference-policy KL inside the loss (it goes into the reward through
 ``kl``; ``grpo`` has the in-loss form), ``old`` given as logits, bootstrapping a truncated sequence with a nonzero
 ``V_{L+1}``, whitening statistics across ranks (use ``whiten=False``), float16, vocabularies split over ranks."""

@@ -1117,6 +1117,79 @@ int hpc_rll_lm_topk_kl_backward(const float* g, const void* logits, int elem, co
                                 void* grad_logits, int64_t rows, int V, int k, int tail, float inv_temperature, void* stream);
 int hpc_rll_lm_topk_last_config(int* out);
 
+/* The policy losses of language-model RL on per-token LOG-PROBABILITIES (no reference counterpart): what consumes the (B,S)
+ * logp (and entropy) of the fused head above for the policy being trained.  Every array is (B,S) fp32; adv is (B,S), or (B)
+ * with adv_per_sequence; weight NULL = ones.  A token with w == 0 is DROPPED by selection: it adds nothing, its coefficients
+ * are exact zeros and its operands may hold NaN.  With pn = logp, po = old_logp, pr = ref_logp, A = adv, d = pn - po,
+ * W_b = sum_s w, lo = 1 - clip_low, hi = 1 + clip_high:
+ *     ratio     HPC_RLL_POLICY_RATIO_TOKEN     r = exp(d)
+ *               HPC_RLL_POLICY_RATIO_SEQUENCE  r = s_b = exp(sum_s w d / W_b) for every token of sequence b, d r / d pn = s_b
+ *                                              for that token alone (GSPO-token; with adv (B) and the sequence aggregate it is
+ *                                              GSPO's value and gradient)
+ *     objective HPC_RLL_POLICY_OBJ_CLIP        l = max(-A r, -A rc), rc = clamp(r, lo, hi); dl/dpn = -A r where the unclipped
+ *                                              term is the maximum (a tie counts as unclipped), else 0; dual_clip = c > 1 and
+ *                                              A < 0: l = min(l, -c A), no gradient where it is active (dual_clip <= 1: off)
+ *               HPC_RLL_POLICY_OBJ_CISPO       l = -rc A pn with rc detached: dl/dpn = -rc A always; dual_clip must be off
+ *     kl (only with ref_logp), e = pr - pn:
+ *               HPC_RLL_POLICY_KL_K1  k = -e               dk/dpn = 1
+ *               HPC_RLL_POLICY_KL_K2  k = e^2 / 2          dk/dpn = -e
+ *               HPC_RLL_POLICY_KL_K3  k = exp(e) - e - 1   dk/dpn = 1 - exp(e)
+ *     value (value_new, value_old, ret: all three or none)  lv = max((v - ret)^2, (vc - ret)^2) / 2, vc = v_old + clamp(v -
+ *               v_old, -value_clip, value_clip), gradient only on the unclipped branch; use_value_clip == 0: lv = (v - ret)^2 / 2
+ *     agg       HPC_RLL_POLICY_AGG_TOKEN     sum w x / sum w (0 when nothing has weight), divided on the device
+ *               HPC_RLL_POLICY_AGG_SEQUENCE  1/B sum_b (sum_s w x / W_b); a sequence without weight adds 0 and counts in B
+ *               HPC_RLL_POLICY_AGG_CONSTANT  sum w x / (B norm_len); norm_len > 0 here and 0 otherwise
+ * out8 = the aggregates of { l, k, lv, entropy, (r - 1) - log r, r, [r > hi or r < lo] }, then sum w.
+ * hpc_rll_lm_policy_forward -- mapping HPC_RLL_POLICY_MAP_RULE picks the wave mapping for S <= HPC_RLL_LM_POLICY_WAVE_SEQ_MAX
+ *   (a value nobody has measured) and the chunk mapping above; _WAVE and _CHUNK pin one.  Chunk: a 256-thread workgroup per
+ *   (sequence, chunk of HPC_RLL_LM_POLICY_CHUNK tokens), four consecutive tokens a thread, at most 512 workgroups, which loop.
+ *   When the ratio or the aggregate is per sequence a first launch leaves (sum w, sum w d) per chunk in ws, and every wave of
+ *   the token launch adds its sequence's partials in one fixed order: all of them hold the same bits of W_b and s_b.  Wave: a
+ *   wave per sequence, four sequences per workgroup, one launch.  `want` says which coefficient rows are written for the
+ *   backward: 1 = cp (d l / d pn), 2 = ck (d k / d pn; needs 1 and ref_logp), 4 = ce (entropy), 8 = cv (value_new), each
+ *   already times w and the aggregate's factor.  No atomics on floats, the same bits on every run.
+ * hpc_rll_lm_policy_workspace_floats -- 4112 + round4(2 B ceil(S / 1024)) + popcount(want) round4(B S), in this order: the sums
+ *   and the partials of the fold, the chunk statistics, the wanted coefficient rows.  ws lies on 16 bytes for 16-byte access.
+ * hpc_rll_lm_policy_backward -- one streaming launch: grad_logp = g_policy cp + g_kl ck, grad_entropy = g_entropy ce,
+ *   grad_value = g_value cv, each only when its pointer is given (its `want` bit was set in the forward); the upstream scalars
+ *   are read on the device, NULL = 0; with the token aggregate they are divided by sum w there.  A zero coefficient gives an
+ *   exact zero whatever the upstream holds.  `want` and `agg` are the forward's.
+ * hpc_rll_lm_policy_last_config -- out[HPC_RLL_LM_POLICY_CONFIG_INTS] = { [0..6] forwards that launched, the mapping of the last
+ *   (1 wave, 2 chunk), 1 when the statistics launch ran, its workgroups (0: none), the token launch's workgroups, bytes per
+ *   access (16, or 4 when a base of the launch is off 16 bytes or S % 4 != 0), chunks per sequence (0: wave mapping);
+ *   [7..9] backward launches, workgroups and bytes per access of the last }; each part {0, -1 ...} before its first launch.
+ * Argument errors, before any HIP call and with nothing written: HPC_RLL_EINVAL (out8 NULL, a negative size, an unknown ratio,
+ * objective, kl, agg, mapping or want, a clip that is negative or not finite, CISPO with a dual clip, norm_len against the rule
+ * above, a negative value_clip, value operands given in part, a want bit without its operand; then null logp, old_logp, adv
+ * or ws with B S > 0), then HPC_RLL_EALIGN (a float array off 4 bytes); then B == 0 or S == 0 returns 0 (the forward's out8
+ * is zeroed). */
+#define HPC_RLL_POLICY_RATIO_TOKEN (0)
+#define HPC_RLL_POLICY_RATIO_SEQUENCE (1)
+#define HPC_RLL_POLICY_OBJ_CLIP (0)
+#define HPC_RLL_POLICY_OBJ_CISPO (1)
+#define HPC_RLL_POLICY_KL_K1 (0)
+#define HPC_RLL_POLICY_KL_K2 (1)
+#define HPC_RLL_POLICY_KL_K3 (2)
+#define HPC_RLL_POLICY_AGG_TOKEN (0)
+#define HPC_RLL_POLICY_AGG_SEQUENCE (1)
+#define HPC_RLL_POLICY_AGG_CONSTANT (2)
+#define HPC_RLL_POLICY_MAP_RULE (0)
+#define HPC_RLL_POLICY_MAP_WAVE (1)
+#define HPC_RLL_POLICY_MAP_CHUNK (2)
+#define HPC_RLL_LM_POLICY_CHUNK (1024)
+#define HPC_RLL_LM_POLICY_WAVE_SEQ_MAX (1024)
+#define HPC_RLL_LM_POLICY_CONFIG_INTS (10)
+int64_t hpc_rll_lm_policy_workspace_floats(int B, int S, int want);
+int hpc_rll_lm_policy_forward(const float* logp, const float* old_logp, const float* adv, int adv_per_sequence,
+                              const float* weight, const float* ref_logp, const float* entropy, const float* value_new,
+                              const float* value_old, const float* ret, float* out8, float* ws, int B, int S, int ratio,
+                              int objective, float clip_low, float clip_high, float dual_clip, int kl, int agg, float norm_len,
+                              int use_value_clip, float value_clip, int want, int mapping, void* stream);
+int hpc_rll_lm_policy_backward(const float* g_policy, const float* g_kl, const float* g_value, const float* g_entropy,
+                               const float* ws, float* grad_logp, float* grad_entropy, float* grad_value, int B, int S, int want,
+                               int agg, void* stream);
+int hpc_rll_lm_policy_last_config(int* out);
+
 /* PPO -- replaces PPOForward/Backward (rl_utils/entry.h:158-165, src/rl_utils/ppo.cu:8-111).
  * logits (B,N), action (B,), value_new/old, adv, ret, weight (B,) (weight NULL = ones).
  * out5 = policy_loss, value_loss, entropy_loss, approx_kl, clipfrac.  dual_clip < 1 disables dual clip

@@ -10,7 +10,7 @@ from setuptools.command.build_ext import build_ext
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.join(ROOT, "di-hpc_amd")
-MODULES = ["hpc_rl_utils", "hpc_torch_utils_network", "hpc_models", "hpc_marl", "hpc_twohot", "hpc_replay", "hpc_sac", "hpc_tqc", "hpc_lm_linear", "hpc_lm_kl", "hpc_lm_topk"]
+MODULES = ["hpc_rl_utils", "hpc_torch_utils_network", "hpc_models", "hpc_marl", "hpc_twohot", "hpc_replay", "hpc_sac", "hpc_tqc", "hpc_lm_linear", "hpc_lm_kl", "hpc_lm_topk", "hpc_lm_policy"]
 
 
 class BuildNative(build_ext):
